@@ -40,6 +40,14 @@ Extra objects in the JSON line:
                    algorithmic fraction, dominant-kernel fraction.  The reference's 60-row criterion size grid is
                    summarised in the line (min / max fraction per size set) and printed in full on stderr / --details.
 The line's members are ordered so that metric, value, ms_per_step and the scalar roofline block come LAST.
+
+`--dump-outputs DIR` writes, after the timed steps, what the LAST timed step computed -- the (batch, N) complex output a
+caller of the batched transform receives -- as float32 / float64 arrays of (re, im) pairs, at most DUMP_BYTES in all:
+DIR/output_rows.npy holds whole transforms (all of them when they fit, else the first, the last and seeded others) and,
+when the output does not fit, DIR/output_points.npy holds seeded single points spread over the whole output.  The
+inputs and the sample are fixed by the arguments, so two builds run with the same arguments can be compared file by
+file.  Under c5 the sample spans every chunk of the last step; with more than one rank every rank writes its own shard's
+sample (`_rank<r>` in the names, the budget split between the ranks).
 """
 import argparse
 import json
@@ -82,7 +90,68 @@ def parse():
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU, no process group: print the shard ranges, chunk walk and byte counts a --gpus N run of this config "
                         "WOULD execute (every rank's view), and check that they tile the global batch exactly")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write a fixed sample of the last timed step's output to DIR/*.npy (see the module docstring)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes written per run, all ranks together (below 64 MB)
+DUMP_SEED = 0x5EED0D0D
+
+
+class OutputSample:
+    """The fixed, seeded sample of one rank's (rows, n) complex output that --dump-outputs writes.  take() copies the sampled
+    rows and points out of a block of consecutive output rows (c5 hands it one chunk at a time); write() saves them."""
+
+    def __init__(self, rows, n, esz, budget):
+        import numpy as np
+
+        self.n = n
+        row_bytes = n * esz
+        if rows * row_bytes <= budget:
+            self.rows = np.arange(rows, dtype=np.int64)
+            self.points = np.zeros(0, dtype=np.int64)
+        else:
+            k = min(rows, budget // 2 // row_bytes)
+            rng = np.random.default_rng(DUMP_SEED)
+            picked = [0, rows - 1][:k]
+            if k > 2:
+                picked += [int(r) for r in rng.choice(np.arange(1, rows - 1), size=k - 2, replace=False)]
+            self.rows = np.unique(np.array(picked, dtype=np.int64))
+            k_pts = (budget - len(self.rows) * row_bytes) // esz
+            self.points = np.unique(rng.integers(0, rows * n, size=k_pts, dtype=np.int64))
+        real = np.float32 if esz == 8 else np.float64
+        self.row_out = np.empty((len(self.rows), n, 2), dtype=real)
+        self.point_out = np.empty((len(self.points), 2), dtype=real)
+        self.taken = 0
+
+    def take(self, y, r0, nb):
+        """y[:nb] holds output rows r0 ... r0 + nb - 1 (contiguous, on the device)."""
+        import numpy as np
+        import torch
+
+        lo, hi = np.searchsorted(self.rows, [r0, r0 + nb])
+        if hi > lo:
+            sel = torch.from_numpy(self.rows[lo:hi] - r0).to(y.device)
+            self.row_out[lo:hi] = torch.view_as_real(y[:nb].index_select(0, sel)).cpu().numpy()
+        plo, phi = np.searchsorted(self.points, [r0 * self.n, (r0 + nb) * self.n])
+        if phi > plo:
+            sel = torch.from_numpy(self.points[plo:phi] - r0 * self.n).to(y.device)
+            self.point_out[plo:phi] = torch.view_as_real(y[:nb].reshape(-1).index_select(0, sel)).cpu().numpy()
+        self.taken += (hi - lo) + (phi - plo)
+
+    def write(self, directory, suffix=""):
+        import numpy as np
+
+        assert self.taken == len(self.rows) + len(self.points), "the sample did not see the whole output"
+        os.makedirs(directory, exist_ok=True)
+        if len(self.rows):
+            np.save(os.path.join(directory, f"output_rows{suffix}.npy"), self.row_out)
+        if len(self.points):
+            np.save(os.path.join(directory, f"output_points{suffix}.npy"), self.point_out)
 
 
 def emit(out, args):
@@ -619,8 +688,8 @@ def main():
         batch = chunk  # per launch (roofline leg)
         units_per_step = gbatch
 
-        def step(step_index):
-            """One pass over this rank's shard; returns the FFT-only seconds (generation bracketed out)."""
+        def step(step_index, sample=None):
+            """One pass over this rank's shard; returns the FFT-only seconds (generation and `sample` bracketed out)."""
             t_fft = 0.0
             for b0 in range(lo, hi, chunk):
                 nb = min(chunk, hi - b0)
@@ -631,6 +700,8 @@ def main():
                 plan.transform_batch_ptr(x.data_ptr(), y.data_ptr(), nb, int(Transform.Fft), stream)
                 torch.cuda.synchronize(dev)
                 t_fft += time.perf_counter() - t1
+                if sample is not None:
+                    sample.take(y, b0 - lo, nb)
             return t_fft
 
         # ---- in-run single-GPU reference: rank 0 alone times two full-size chunks (after one warm chunk) while every
@@ -656,10 +727,11 @@ def main():
         for w in range(args.warmup):
             step(-1 - w)
         sync_all()
+        sample = OutputSample(hi - lo, n, esz, DUMP_BYTES // world) if args.dump_outputs else None
         t0 = time.perf_counter()
         fft_s = 0.0
         for k in range(args.steps):
-            fft_s += step(k)
+            fft_s += step(k, sample if k == args.steps - 1 else None)
         torch.cuda.synchronize(dev)
         sync_all()
         wall = time.perf_counter() - t0
@@ -715,6 +787,10 @@ def main():
         torch.cuda.synchronize(dev)
         sync_all()
         mine = time.perf_counter() - t0
+        sample = None
+        if args.dump_outputs:  # before the roofline leg below rewrites y
+            sample = OutputSample(batch, n, esz, DUMP_BYTES // world)
+            sample.take(y, 0, batch)
         elapsed = shard.reduce_max_seconds(mine, dist, red_dev)
         if dist is not None:
             per_rank = shard.gather_seconds(mine, dist, red_dev)
@@ -753,6 +829,8 @@ def main():
         "hbm_frac_algorithmic": round(alg_gbps / (HBM_PEAK_GBPS * world), 4),
     }
     out.update(extra)
+    if sample is not None:
+        sample.write(args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     if rank == 0:
         # ---- roofline of the dominant kernel: HIP events on the launch stream, live

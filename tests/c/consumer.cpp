@@ -29,10 +29,30 @@ template <typename T> static int check() {
   return 0;
 }
 
+// The C ABI called from C++: namespace fourier::c, with std::complex<T> as the complex type.
+static int check_c_abi() {
+  using namespace fourier::c;
+  std::complex<float> inf[4] = {1, 0, 0, 0}, outf[4];
+  fourier_fft_float *f = fourier_create_float(4);
+  if (!f) return 1;
+  fourier_transform_float(f, inf, outf, FOURIER_TRANSFORM_FFT);
+  fourier_transform_in_place_float(f, outf, FOURIER_TRANSFORM_IFFT);
+  fourier_destroy_float(f);
+  std::complex<double> ind[4] = {1, 0, 0, 0}, outd[4];
+  fourier_fft_double *d = fourier_create_double(4);
+  if (!d) return 1;
+  fourier_transform_double(d, ind, outd, FOURIER_TRANSFORM_FFT);
+  fourier_transform_in_place_double(d, outd, FOURIER_TRANSFORM_IFFT);
+  fourier_destroy_double(d);
+  for (int i = 0; i < 4; i++)
+    if (std::abs(inf[i] - outf[i]) > 1e-10f || std::abs(ind[i] - outd[i]) > 1e-10) return 2;
+  return 0;
+}
+
 int main() {
-  const int a = check<float>(), b = check<double>();
-  if (a || b) {
-    std::fprintf(stderr, "consumer.cpp failed: float=%d double=%d\n", a, b);
+  const int a = check<float>(), b = check<double>(), c = check_c_abi();
+  if (a || b || c) {
+    std::fprintf(stderr, "consumer.cpp failed: float=%d double=%d c_abi=%d\n", a, b, c);
     return 1;
   }
   std::printf("Tests ran successfully.\n");

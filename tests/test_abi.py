@@ -46,15 +46,18 @@ def test_library_loads_and_every_symbol_resolves_without_a_gpu(libpath):
 
     from fourier_amd import _lib
 
-    cdll = _lib.bind(ctypes.CDLL(libpath))
-    for sym in declared_symbols():
-        assert getattr(cdll, sym) is not None
+    # torch first: it loads its own copy of the HIP runtime (SONAME libamdhip64.so.7), which the library's dependency then
+    # resolves to.  Loaded before torch, the library would bring in the system's copy, torch would add its own, and on a
+    # GPU machine every later test in this process would hold two HIP runtimes -- and fail to create plans.
     try:
         import torch
 
         has_gpu = torch.cuda.is_available()
     except Exception:
         has_gpu = False
+    cdll = _lib.bind(ctypes.CDLL(libpath))
+    for sym in declared_symbols():
+        assert getattr(cdll, sym) is not None
     if not has_gpu:
         assert not cdll.fourier_create_float(8) and not cdll.fourier_create_double(8)
         assert cdll.fourier_hip_size_float(None) == 0

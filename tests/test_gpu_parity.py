@@ -626,6 +626,59 @@ def test_bench_strong_scaling_path_with_two_ranks(torch, fa, tmp_path):
     assert 0 < ss["efficiency_vs_reference"] <= (1.25 if two else 1.05)  # two ranks on ONE shared GPU: about 0.5
 
 
+@pytest.mark.parametrize("config", ["c2", "c5"])
+def test_bench_dump_outputs_is_the_last_timed_step(torch, fa, oracle, tmp_path, config):
+    """`bench.py --dump-outputs DIR` writes a fixed sample of what its last timed step computed: the same files bit for bit
+    from two runs with the same arguments, at most 64 MB, and equal to the output of this process's own plan on the inputs
+    bench.py generates (c2: one resident batch; c5: every chunk of the last step, regenerated from its seed)."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, batch, chunk, steps = 1 << 16, 1024, 256, 3  # 512 MiB of output: more than the dump takes, so it is sampled
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--config", config, "--log2n", "16", "--batch", str(batch), "--chunk", str(chunk), "--no-cpu", "--no-other",
+               "--no-ceiling", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == steps
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == ["output_points.npy", "output_rows.npy"] == sorted(p.name for p in dirs[1].iterdir())
+    assert sum(p.stat().st_size for p in dirs[0].iterdir()) <= 64 * 10**6
+    got = {k: np.load(dirs[0] / f"output_{k}.npy") for k in ("rows", "points")}
+    for k in got:
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], np.load(dirs[1] / f"output_{k}.npy"))
+    assert got["rows"].shape[1:] == (n, 2) and got["points"].shape[1:] == (2,)
+
+    # the same transforms in this process: bench.py's inputs, the same plan
+    plan = fa.create_fft_f32(n, 0)
+    x = torch.empty((batch, n), dtype=torch.complex64, device="cuda")
+    if config == "c2":
+        torch.manual_seed(0x5EED0001)
+        torch.view_as_real(x).uniform_(0.0, 1.0)
+    else:
+        gen = torch.Generator(device="cuda")
+        for b0 in range(0, batch, chunk):
+            gen.manual_seed(0x5EED0C50 + 7919 * (steps - 1) + b0)
+            torch.view_as_real(x[b0:b0 + chunk]).uniform_(0.0, 1.0, generator=gen)
+    y = torch.empty_like(x)
+    plan.transform(x, y, fa.Transform.Fft)
+    torch.cuda.synchronize()
+    yr = torch.view_as_real(y).cpu().numpy()
+    sys.path.insert(0, root)
+    import bench
+
+    sample = bench.OutputSample(batch, n, 8, bench.DUMP_BYTES)  # the seeded sample is a function of the shape alone
+    assert sample.rows[0] == 0 and sample.rows[-1] == batch - 1 and len(sample.points) > 0
+    assert np.array_equal(got["rows"], yr[sample.rows])
+    assert np.array_equal(got["points"], yr.reshape(-1, 2)[sample.points])
+    ref = oracle.transform_batch(x[-1:].cpu().numpy(), oracle.FFT)  # and the last transform is right
+    assert rel_l2(got["rows"][-1].view(np.complex64).ravel(), ref[0]) <= 1e-6
+
+
 def test_device_and_overlap_checks_of_the_operator_layer(torch, fa):
     plan = fa.create_fft_f32(256, 0)
     assert plan.device == 0
