@@ -18,7 +18,10 @@ EXT_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES
                for op in ("create", "size", "transform_batch", "reserve", "device", "synchronize", "transform_batch_host", "last_status", "set_option", "describe", "model_bytes",
                           "profile", "slot_names")] + [
     "fourier_hip_status_string", "fourier_hip_set_default_option", "fourier_hip_get_default_option"]
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS
+# real-input transforms (fourier_hip_real_*)
+REAL_SYMBOLS = [f"fourier_hip_real_{op}_{s}" for s in SUFFIXES
+                for op in ("create", "destroy", "size", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
+ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS
 
 
 def bind(cdll, strict=True):
@@ -45,6 +48,15 @@ def bind(cdll, strict=True):
         f = getattr(cdll, f"fourier_hip_profile_{s}"); f.restype = ci
         f.argtypes = [vp, vp, vp, sz, ci, vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         f = getattr(cdll, f"fourier_hip_slot_names_{s}"); f.restype = cp; f.argtypes = [vp]
+        if strict or hasattr(cdll, f"fourier_hip_real_create_{s}"):
+            f = getattr(cdll, f"fourier_hip_real_create_{s}"); f.restype = vp; f.argtypes = [sz, ci]
+            f = getattr(cdll, f"fourier_hip_real_destroy_{s}"); f.restype = None; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_real_size_{s}"); f.restype = sz; f.argtypes = [vp]
+            for op in ("forward_batch", "inverse_batch"):
+                f = getattr(cdll, f"fourier_hip_real_{op}_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci, vp]
+            f = getattr(cdll, f"fourier_hip_real_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
+            f = getattr(cdll, f"fourier_hip_real_describe_{s}"); f.restype = cp; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_real_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
     cdll.fourier_hip_status_string.restype = cp
     cdll.fourier_hip_status_string.argtypes = [ci]
     if strict or hasattr(cdll, "fourier_hip_set_default_option"):

@@ -12,6 +12,7 @@
 // of engine_common.h.  Compiled with hipcc for gfx950; the same files build against tests/emu/hipemu.h (-DFOURIER_EMU)
 // for CPU-side logic tests only.
 #include "plan.h"
+#include "real_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -93,6 +94,41 @@ namespace fc = ::fourier::c;
 
 FOURIER_DEFINE_ABI(float, float)
 FOURIER_DEFINE_ABI(double, double)
+
+// real-input transforms (include/fourier.h, fourier_hip_real_*): the same error model as the complex handle
+#define FOURIER_DEFINE_REAL_ABI(T, SUFFIX)                                                                       \
+  extern "C" fc::fourier_real_fft_##SUFFIX* fourier_hip_real_create_##SUFFIX(size_t size, int device) {          \
+    return (fc::fourier_real_fft_##SUFFIX*)create_real_plan<T>(size, device);                                    \
+  }                                                                                                              \
+  extern "C" void fourier_hip_real_destroy_##SUFFIX(fc::fourier_real_fft_##SUFFIX* h) {                          \
+    try { delete (RealPlan<T>*)h; } catch (...) {}                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_real_size_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {                     \
+    return h ? ((const RealPlan<T>*)h)->size() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" int fourier_hip_real_forward_batch_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, const void* d_in, \
+                                                         void* d_out, size_t batch, int code, void* stream) {    \
+    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_real_inverse_batch_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, const void* d_in, \
+                                                         void* d_out, size_t batch, int code, void* stream) {    \
+    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_real_reserve_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, size_t batch) {       \
+    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
+  }                                                                                                              \
+  extern "C" const char* fourier_hip_real_describe_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {            \
+    return h ? ((const RealPlan<T>*)h)->describe() : "";                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_real_last_status_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {                 \
+    return h ? ((const RealPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                        \
+  }
+
+FOURIER_DEFINE_REAL_ABI(float, float)
+FOURIER_DEFINE_REAL_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

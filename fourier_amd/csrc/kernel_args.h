@@ -138,6 +138,23 @@ struct ChirpzArgs {
   double scale;
 };
 
+// ---- real-input transforms (kernels_real.h)
+// real_post_kernel / real_pre_kernel: one lane per mirrored pair (j, h - j) of a row, j <= h / 2, over a flat index of
+// rows x pairs; byte offsets are 32-bit (the plan launches at most REAL_LAUNCH_BYTES of either side per launch).  The odd-N sweeps
+// (plain grid-stride loops between user rows and the complex N-point work array) read in, out, n and rows only.
+enum { REAL_POST = 0, REAL_PRE = 1, REAL_WIDEN = 2, REAL_NARROW = 3, REAL_EXTEND = 4, REAL_PART = 5 };
+struct RealArgs {
+  const void* in; void* out;
+  const void* tw;             // W_N^j, j <= h / 2 (f64 on the host, cast)
+  uint32_t h;                 // N / 2: complex points of the inner transform
+  uint32_t pairs;             // h / 2 + 1 lanes per row
+  uint32_t total;             // rows * pairs
+  uint32_t div_m, div_l;      // idx / pairs = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  double scale;               // forward: the code's scale; inverse: the code's scale / N (the inner IFFT runs unscaled)
+  uint64_t n, rows;           // odd N: real length, rows in this launch
+};
+
 // ---- XCD-fused one-launch plan (kernels_experiments.h)
 struct FusedArgs {
   PassArgs a, b;       // pass A / pass B arguments; a.in, a.out, b.in, b.out are set per item

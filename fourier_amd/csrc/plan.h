@@ -907,7 +907,8 @@ template <typename T> static Plan<T>* create_plan(size_t n, int device) {
   }
 }
 
-template <typename T, typename F> static int guarded(const Plan<T>* p, F&& f) {
+// the error model of every handle (Plan, RealPlan): status of the last call, nothing unwinds into C
+template <typename H, typename F> static int guarded_handle(const H* p, F&& f) {
   if (!p) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
   p->set_status(::fourier::c::FOURIER_HIP_OK);  // last_status = status of the LAST call on this handle
   try {
@@ -925,5 +926,6 @@ template <typename T, typename F> static int guarded(const Plan<T>* p, F&& f) {
     return ::fourier::c::FOURIER_HIP_RUNTIME_ERROR;
   }
 }
+template <typename T, typename F> static int guarded(const Plan<T>* p, F&& f) { return guarded_handle(p, std::forward<F>(f)); }
 
 }  // namespace fourier_hip

@@ -198,6 +198,93 @@ class Fft:
                 pass
 
 
+class RealFft:
+    """Batched real-input transforms (include/fourier.h, fourier_hip_real_*): N reals per row <-> N//2+1 complex per row, numpy's
+    rfft / irfft layout, on device memory.  Forward codes Fft / SqrtScaledFft, inverse codes Ifft / UnscaledIfft / SqrtScaledIfft."""
+
+    def __init__(self, size, real, device=-1):
+        self._suffix = {"f32": "float", "f64": "double"}[real]
+        self.real = real
+        self._L = _lib.lib()
+        self._h = getattr(self._L, f"fourier_hip_real_create_{self._suffix}")(int(size), int(device))
+        if not self._h:
+            raise FourierError(f"cannot create real FFT plan of size {size}")
+        self._n = int(size)
+
+    def size(self):
+        return self._n
+
+    def describe(self):
+        return getattr(self._L, f"fourier_hip_real_describe_{self._suffix}")(self._h).decode()
+
+    def _check(self, st):
+        if st != 0:
+            raise FourierError(self._L.fourier_hip_status_string(st).decode())
+
+    def forward_batch_ptr(self, d_in, d_out, batch, transform=Transform.Fft, stream=0):
+        """`batch` rows of N reals at d_in -> `batch` rows of N//2+1 complex at d_out, enqueued on `stream`."""
+        self._check(getattr(self._L, f"fourier_hip_real_forward_batch_{self._suffix}")(
+            self._h, d_in, d_out, int(batch), int(transform), stream))
+
+    def inverse_batch_ptr(self, d_in, d_out, batch, transform=Transform.Ifft, stream=0):
+        """`batch` rows of N//2+1 complex at d_in -> `batch` rows of N reals at d_out (d_in is not modified)."""
+        self._check(getattr(self._L, f"fourier_hip_real_inverse_batch_{self._suffix}")(
+            self._h, d_in, d_out, int(batch), int(transform), stream))
+
+    def reserve(self, batch):
+        """Pre-size the plan-owned buffers: later calls of at most `batch` rows never allocate."""
+        self._check(getattr(self._L, f"fourier_hip_real_reserve_{self._suffix}")(self._h, int(batch)))
+
+    def _tensor(self, x, dtype, last):
+        import torch
+
+        if not (_is_torch(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous()):
+            raise TypeError(f"expected a contiguous CUDA {dtype} tensor")
+        if x.dim() == 0 or x.shape[-1] != last:
+            raise ValueError(f"last dimension must be {last}, got {tuple(x.shape)}")
+        return torch.cuda.current_stream(x.device).cuda_stream
+
+    def rfft(self, x, transform=Transform.Fft):
+        """Contiguous (..., N) float32 / float64 CUDA tensor -> new (..., N//2+1) complex tensor, on the current stream."""
+        import torch
+
+        real_dt, cpx_dt = (torch.float32, torch.complex64) if self.real == "f32" else (torch.float64, torch.complex128)
+        stream = self._tensor(x, real_dt, self._n)
+        out = torch.empty(x.shape[:-1] + (self._n // 2 + 1,), dtype=cpx_dt, device=x.device)
+        batch = x.numel() // self._n
+        if batch:
+            self.forward_batch_ptr(x.data_ptr(), out.data_ptr(), batch, transform, stream)
+        return out
+
+    def irfft(self, X, transform=Transform.Ifft):
+        """Contiguous (..., N//2+1) complex CUDA tensor -> new (..., N) real tensor, on the current stream; X is not modified."""
+        import torch
+
+        real_dt, cpx_dt = (torch.float32, torch.complex64) if self.real == "f32" else (torch.float64, torch.complex128)
+        stream = self._tensor(X, cpx_dt, self._n // 2 + 1)
+        out = torch.empty(X.shape[:-1] + (self._n,), dtype=real_dt, device=X.device)
+        batch = X.numel() // (self._n // 2 + 1)
+        if batch:
+            self.inverse_batch_ptr(X.data_ptr(), out.data_ptr(), batch, transform, stream)
+        return out
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                getattr(self._L, f"fourier_hip_real_destroy_{self._suffix}")(h)
+            except Exception:
+                pass
+
+
+def create_rfft_f32(size, device=-1):
+    return RealFft(size, "f32", device)
+
+
+def create_rfft_f64(size, device=-1):
+    return RealFft(size, "f64", device)
+
+
 def set_default_option(key, value):
     """Library-wide default for plans created afterwards (include/fourier.h: fourier_hip_set_default_option), e.g.
     ("specialise_at_create", 2): lengths whose prime factors stop at 13 get their own kernels compiled inside create_fft_*."""

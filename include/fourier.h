@@ -307,6 +307,52 @@ int fourier_hip_profile_double(const FOURIER_STRUCT fourier_fft_double *, const 
 const char *fourier_hip_slot_names_float(const FOURIER_STRUCT fourier_fft_float *);
 const char *fourier_hip_slot_names_double(const FOURIER_STRUCT fourier_fft_double *);
 
+/* ---------------- real-input transforms (extension; the reference has none) ------------------------
+ * Batched real-to-half-spectrum and half-spectrum-to-real transforms of length N >= 1 on DEVICE memory, numpy's rfft / irfft
+ * layout:
+ *   forward  d_in:  `batch` rows of N reals T, row b at element offset b*N;
+ *            d_out: `batch` rows of N/2+1 interleaved complex T (row stride N/2+1, integer division).
+ *            FOURIER_TRANSFORM_FFT: rfft(x); FOURIER_TRANSFORM_SQRT_SCALED_FFT: rfft(x) / sqrt(N).
+ *   inverse  d_in:  N/2+1 complex values per row; d_out: N reals per row.
+ *            FOURIER_TRANSFORM_IFFT: irfft(X, n=N); FOURIER_TRANSFORM_UNSCALED_IFFT: N * irfft; FOURIER_TRANSFORM_SQRT_SCALED_IFFT:
+ *            sqrt(N) * irfft.  The imaginary parts of X[0] and, for even N, X[N/2] are ignored.  d_in is NOT modified (unlike
+ *            cuFFT's c2r).
+ * A code of the other direction, d_in == d_out or any overlap of the two ranges, a NULL pointer or a pointer not aligned to
+ * 2*sizeof(T) give FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.  Stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*.  Even N runs an inner N/2-point complex plan plus one untangle sweep (about 3/4 of the bytes
+ * of the complex N-point transform); odd N runs the N-point complex plan on a widened copy (a correctness path).  The plan
+ * owns a scratch of at most 1 GiB (never less than one row) and walks larger batches in chunks of it; the first call with a
+ * batch larger than any before allocates it unless fourier_hip_real_reserve_* was called for at least that batch.
+ * fourier_hip_real_describe_* returns "real half-length: <inner plan's describe>" (even N) or "real full-length: <inner plan's
+ * describe>" (odd N).  Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_real_last_status_*. */
+struct fourier_real_fft_float;
+struct fourier_real_fft_double;
+
+/* NULL on failure (size 0 included). */
+struct fourier_real_fft_float *fourier_hip_real_create_float(FOURIER_SIZE_TYPE size, int device);
+struct fourier_real_fft_double *fourier_hip_real_create_double(FOURIER_SIZE_TYPE size, int device);
+/* NULL is a no-op. */
+void fourier_hip_real_destroy_float(FOURIER_STRUCT fourier_real_fft_float *);
+void fourier_hip_real_destroy_double(FOURIER_STRUCT fourier_real_fft_double *);
+/* N; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_real_size_float(const FOURIER_STRUCT fourier_real_fft_float *);
+FOURIER_SIZE_TYPE fourier_hip_real_size_double(const FOURIER_STRUCT fourier_real_fft_double *);
+int fourier_hip_real_forward_batch_float(const FOURIER_STRUCT fourier_real_fft_float *, const void *d_in, void *d_out,
+                                         FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_real_forward_batch_double(const FOURIER_STRUCT fourier_real_fft_double *, const void *d_in, void *d_out,
+                                          FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_real_inverse_batch_float(const FOURIER_STRUCT fourier_real_fft_float *, const void *d_in, void *d_out,
+                                         FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_real_inverse_batch_double(const FOURIER_STRUCT fourier_real_fft_double *, const void *d_in, void *d_out,
+                                          FOURIER_SIZE_TYPE batch, int transform, void *stream);
+/* Pre-size the scratch and the inner plan's buffers: afterwards calls of at most `batch` rows never allocate. */
+int fourier_hip_real_reserve_float(const FOURIER_STRUCT fourier_real_fft_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_real_reserve_double(const FOURIER_STRUCT fourier_real_fft_double *, FOURIER_SIZE_TYPE batch);
+const char *fourier_hip_real_describe_float(const FOURIER_STRUCT fourier_real_fft_float *);
+const char *fourier_hip_real_describe_double(const FOURIER_STRUCT fourier_real_fft_double *);
+int fourier_hip_real_last_status_float(const FOURIER_STRUCT fourier_real_fft_float *);
+int fourier_hip_real_last_status_double(const FOURIER_STRUCT fourier_real_fft_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -359,6 +405,48 @@ template <typename T> struct fft;
 FOURIER_DEFINE_CXX_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_WRAPPER
+
+/* real-input transforms on device memory (extension): fourier::real_fft<float> / <double> */
+template <typename T> struct real_fft;
+
+#define FOURIER_DEFINE_CXX_REAL_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct real_fft<T> {                                                                 \
+    explicit real_fft(std::size_t size, int device = -1)                                           \
+        : impl(::fourier::c::fourier_hip_real_create_##SUFFIX(size, device),                       \
+               ::fourier::c::fourier_hip_real_destroy_##SUFFIX) {}                                 \
+    real_fft() = delete;                                                                           \
+    real_fft(const real_fft &) = delete;                                                           \
+    real_fft(real_fft &&) = default;                                                               \
+    real_fft &operator=(const real_fft &) = delete;                                                \
+    real_fft &operator=(real_fft &&) = default;                                                    \
+    ~real_fft() = default;                                                                         \
+    std::size_t size() const { return ::fourier::c::fourier_hip_real_size_##SUFFIX(impl.get()); }  \
+    /* N reals per row -> N/2+1 complex per row */                                                 \
+    int forward_batch_device(const void *d_in, void *d_out, std::size_t batch,                     \
+                             ::fourier::transform t = ::fourier::transform::fft,                   \
+                             void *stream = nullptr) const {                                       \
+      return ::fourier::c::fourier_hip_real_forward_batch_##SUFFIX(impl.get(), d_in, d_out, batch, \
+                                                                   static_cast<int>(t), stream);   \
+    }                                                                                              \
+    /* N/2+1 complex per row -> N reals per row */                                                 \
+    int inverse_batch_device(const void *d_in, void *d_out, std::size_t batch,                     \
+                             ::fourier::transform t = ::fourier::transform::ifft,                  \
+                             void *stream = nullptr) const {                                       \
+      return ::fourier::c::fourier_hip_real_inverse_batch_##SUFFIX(impl.get(), d_in, d_out, batch, \
+                                                                   static_cast<int>(t), stream);   \
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_real_reserve_##SUFFIX(impl.get(), batch);                   \
+    }                                                                                              \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_real_fft_##SUFFIX,                                     \
+                      void (*)(::fourier::c::fourier_real_fft_##SUFFIX *)> impl;                   \
+  };
+FOURIER_DEFINE_CXX_REAL_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_REAL_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_REAL_WRAPPER
 
 } /* namespace fourier */
 #endif
