@@ -17,11 +17,15 @@ Workloads (`--config`, default `auto`):
         configuration BASELINE.json names for the 1/2/4/8-GPU scaling curve.
   c3 / c4   configs[2] (f64 N=2^20 x 4096) and configs[3] (Bluestein N=999983 f32 x 512), same form as c2.
 `auto` = c2 on one GPU, c5 under torch.distributed.run with more than one rank.  The line names its configuration
-(`config_key`); a c5 line carries its own single-GPU reference (`strong_scaling.single_gpu_reference`: rank 0 alone on
-two chunks while the other ranks idle), every rank's time, the process group's backend and world size, and the
-efficiency against that reference, so that one record is enough to judge batch-shard scaling.
+(`config_key`), every rank's time and the process group's backend and world size; with --full a c5 line also carries its
+own single-GPU reference (`strong_scaling.single_gpu_reference`: rank 0 alone on two chunks while the other ranks idle)
+and the efficiency against that reference, so that one record is enough to judge batch-shard scaling.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else touches the GPU or
+the host cores.  `--full` adds the legs below after the timed steps (and, under c5, the single-GPU reference before the
+warm-up); --no-cpu / --no-other / --no-ceiling leave single legs of a full run out.
+
+Extra objects in the JSON line of a --full run:
   roofline      -- dominant kernel, algorithmic bytes per launch / HIP-event duration (events on the
                    launch stream, inside this process), peak 8 TB/s; `traffic` from the committed
                    rocprofv3 PMC pass (profiles/traffic_latest.json) or null.  Also measured IN THIS RUN, on
@@ -82,10 +86,12 @@ def parse():
     p.add_argument("--chunk-bytes", type=int, default=None, help="override the plan's chunk_bytes option")
     p.add_argument("--scratch", type=int, default=None, help="override the plan's scratch option (0/1)")
     p.add_argument("--inplace", action="store_true")
-    p.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    p.add_argument("--no-other", action="store_true", help="skip the other_configs leg")
-    p.add_argument("--no-ceiling", action="store_true", help="skip the in-run streaming-ceiling measurement")
-    p.add_argument("--details", default=None, help="also write the complete record (with the reference's 60-row size grid) to this file")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure: roofline, parity + cpu_baseline, other_configs, the c5 single-GPU reference")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the parity / cpu_baseline leg")
+    p.add_argument("--no-other", action="store_true", help="with --full: skip the other_configs leg")
+    p.add_argument("--no-ceiling", action="store_true", help="with --full: skip the in-run streaming-ceiling measurement")
+    p.add_argument("--details", default=None, help="also write the complete record (with --full: the reference's 60-row size grid) to this file")
     p.add_argument("--cpu-sample", type=int, default=0, help="transforms in the CPU sample (0 = auto)")
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU, no process group: print the shard ranges, chunk walk and byte counts a --gpus N run of this config "
@@ -704,13 +710,13 @@ def main():
                     sample.take(y, b0 - lo, nb)
             return t_fft
 
-        # ---- in-run single-GPU reference: rank 0 alone times two full-size chunks (after one warm chunk) while every
-        # other rank waits at the barrier below, so that the line holds what ONE GPU does per chunk with an idle node
+        # ---- in-run single-GPU reference (--full): rank 0 alone times two full-size chunks (after one warm chunk) while
+        # every other rank waits at the barrier below, so that the line holds what ONE GPU does per chunk with an idle node
         # around it.  ideal step time = reference x chunks of the largest shard; efficiency = ideal / measured.
         ref_ms_per_chunk = None
         if dist is not None:
             dist.barrier()
-        if rank == 0:
+        if rank == 0 and args.full:
             ts_ref = []
             for i in range(3):
                 gen.manual_seed(0x5EED0AAA + i)
@@ -741,24 +747,24 @@ def main():
         extra["wall_ms_per_step_incl_regen"] = round(wall / args.steps * 1e3, 3)
         if rank == 0:
             shards = [shard.batch_shard(gbatch, world, r) for r in range(world)]
-            largest = max(h - l for l, h in shards)
-            ideal_ms = ref_ms_per_chunk * largest / chunk
             extra["strong_scaling"] = {
                 "per_rank_fft_ms_per_step": [round(t / args.steps * 1e3, 3) for t in per_rank],
                 "transforms_per_rank": [h - l for l, h in shards],
-                "single_gpu_reference": {"ms_per_chunk": round(ref_ms_per_chunk, 3), "chunk": chunk,
-                                         "how": "rank 0 alone, two timed chunks after one warm chunk, every other rank waiting at a barrier until it is done"},
-                "ideal_ms_per_step": round(ideal_ms, 3),  # reference x (largest shard / chunk): perfect batch-shard scaling
-                "efficiency_vs_reference": round(ideal_ms / (elapsed / args.steps * 1e3), 4),
             }
+            if ref_ms_per_chunk is not None:
+                ideal_ms = ref_ms_per_chunk * max(h - l for l, h in shards) / chunk
+                extra["strong_scaling"].update({
+                    "single_gpu_reference": {"ms_per_chunk": round(ref_ms_per_chunk, 3), "chunk": chunk,
+                                             "how": "rank 0 alone, two timed chunks after one warm chunk, every other rank waiting at a barrier until it is done"},
+                    "ideal_ms_per_step": round(ideal_ms, 3),  # reference x (largest shard / chunk): perfect batch-shard scaling
+                    "efficiency_vs_reference": round(ideal_ms / (elapsed / args.steps * 1e3), 4),
+                })
         workload = (f"batched 1D c2c {dtype} N={n} GLOBAL batch={gbatch} batch-sharded over {world} GPU(s) "
                     f"({hi - lo} per GPU as resident chunks of {chunk}, regenerated on the device), forward "
                     f"{'in-place' if args.inplace else 'out-of-place'} ({cfg['name']})")
         config = {"workload": workload, "n": n, "global_batch": gbatch, "batch_per_gpu": hi - lo, "chunk": chunk,
                   "parallelism": f"batch-shard x{world}", "plan": plan.describe()}
         scaling = "strong"
-        if rank == 0 and not args.no_cpu:
-            hx = None  # parity for c5: two transforms of the resident chunk, below
     else:
         batch = args.batch or cfg["batch"]
         units_per_step = world * batch
@@ -773,8 +779,8 @@ def main():
         def step():
             plan.transform_batch_ptr(x.data_ptr(), y.data_ptr(), batch, int(Transform.Fft), stream)
 
-        # host copy of the parity / CPU-baseline sample, taken before anything can overwrite the input
-        if rank == 0 and world == 1 and not args.no_cpu:
+        # host copy of the parity / CPU-baseline sample (--full), taken before anything can overwrite the input
+        if rank == 0 and world == 1 and args.full and not args.no_cpu:
             # ~20-30 s of CPU work with the AVX clone (2.8 ms per transform on one core of the round-2 box, six thread counts)
             sample = min(batch, args.cpu_sample or 1024)
             hx = x[:sample].cpu().numpy()
@@ -832,7 +838,7 @@ def main():
     if sample is not None:
         sample.write(args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: HIP events on the launch stream, live
         kernels = kernel_profile(plan, x.data_ptr(), y.data_ptr(), batch, stream)
         ceiling = skeleton = None
@@ -909,6 +915,7 @@ def main():
                     dst[f"{k}_whole_path_frac"] = o.get("hbm_frac_algorithmic")
                     dst[f"{k}_dominant_kernel_frac"] = o.get("dominant_kernel_frac")
             out["roofline"]["c1_gpu_us_per_call"] = others.get("c1", {}).get("gpu_us_per_call")
+    if rank == 0:
         emit(out, args)
 
     if dist is not None:

@@ -585,11 +585,12 @@ def test_sharded_driver_orders_against_the_callers_stream_and_returns_when_done(
 
 
 def test_bench_strong_scaling_path_with_two_ranks(torch, fa, tmp_path):
-    """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one rank per GPU): BASELINE
-    configs[4] with the global batch split over the ranks, "scaling": "strong", one JSON line from rank 0.  With two
-    GPUs it runs over RCCL; on a one-GPU box the two ranks share cuda:0 (BENCH_SHARE_DEVICES) and, because RCCL refuses
-    two ranks on one device, the group is gloo -- the data path has no collective either way.  A reduced global batch
-    keeps it short; the plan, chunking, sharding and JSON contract are the full-size ones."""
+    """`bench.py --gpus 2 --full` as the driver launches it (torch.distributed.run, one rank per GPU): BASELINE
+    configs[4] with the global batch split over the ranks, "scaling": "strong", one JSON line from rank 0, with the
+    parity, roofline and single-GPU reference legs of --full.  With two GPUs it runs over RCCL; on a one-GPU box the two
+    ranks share cuda:0 (BENCH_SHARE_DEVICES) and, because RCCL refuses two ranks on one device, the group is gloo -- the
+    data path has no collective either way.  A reduced global batch keeps it short; the plan, chunking, sharding and JSON
+    contract are the full-size ones."""
     import json
     import subprocess
     import sys
@@ -601,7 +602,7 @@ def test_bench_strong_scaling_path_with_two_ranks(torch, fa, tmp_path):
         env.update(BENCH_SHARE_DEVICES="1", BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "1536", "--chunk", "256"]
+           "--batch", "1536", "--chunk", "256", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -677,6 +678,37 @@ def test_bench_dump_outputs_is_the_last_timed_step(torch, fa, oracle, tmp_path, 
     assert np.array_equal(got["points"], yr.reshape(-1, 2)[sample.points])
     ref = oracle.transform_batch(x[-1:].cpu().numpy(), oracle.FFT)  # and the last transform is right
     assert rel_l2(got["rows"][-1].view(np.complex64).ravel(), ref[0]) <= 1e-6
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_legs(torch, fa, tmp_path):
+    """A plain `bench.py` run prints the headline line without the legs that take runs of their own (roofline, parity /
+    cpu_baseline, other_configs, the c5 single-GPU reference); `--full` adds them to the same line."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    legs = {"roofline", "parity", "cpu_baseline", "other_configs"}
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2n", "16", *extra]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    for config, extra in (("c2", ["--batch", "2048"]), ("c5", ["--batch", "2048", "--chunk", "1024"])):
+        out = run("--config", config, *extra)
+        assert not legs & set(out), sorted(legs & set(out))
+        assert out["config_key"] == config and out["steps"] == 2 and out["warmup"] == 1
+        assert out["unit"] == "GFLOP/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and "N=2^16" in out["metric"]
+        assert abs(out["value"] - 2048 * 5 * (1 << 16) * 16 / (out["ms_per_step"] * 1e-3) / 1e9) / out["value"] < 1e-2
+        if config == "c5":
+            assert out["strong_scaling"]["transforms_per_rank"] == [2048] and "single_gpu_reference" not in out["strong_scaling"]
+
+    out = run("--config", "c2", "--batch", "2048", "--full", "--cpu-sample", "4")
+    assert {"roofline", "parity", "cpu_baseline"} <= set(out)
+    assert out["parity"]["rel_l2_vs_oracle"] <= 1e-6 and out["roofline"]["frac"] > 0 and out["cpu_baseline"]["value"] > 0
 
 
 def test_device_and_overlap_checks_of_the_operator_layer(torch, fa):

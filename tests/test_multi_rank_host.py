@@ -115,3 +115,14 @@ def test_bench_dry_run_validates_the_sharding_of_the_full_c5_job():
     out = json.loads(r.stdout.strip())
     assert r.returncode == 0 and out["config_key"] == "c5" and out["transforms_per_rank"] == [333, 333, 334]
     assert out["tiles_global_batch_exactly_once"] and [rk["ragged_last_chunk"] for rk in out["ranks"]] == [77, 77, 78]
+
+
+def test_bench_full_is_an_option_off_by_default(monkeypatch):
+    """The legs beyond the headline figure run only with `bench.py --full`: a plain run's arguments leave it off."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True

@@ -1,8 +1,8 @@
 #!/bin/bash
-# Copies what tools/gpu_r06_final.sh left in gpurun_out/ (scratch) into profiles/ (tracked) under <tag>_*, and folds the PMC
+# Copies what tools/gpu_r06_final.sh left in $EVIDENCE_DIR (scratch, default evidence/) into profiles/ (tracked) under <tag>_*, and folds the PMC
 # summaries into profiles/traffic_latest.json.  usage: bash tools/collect_session.sh r05_s9
 set -u
-T=${1:?tag}; G=gpurun_out; P=profiles
+T=${1:?tag}; G=${EVIDENCE_DIR:-evidence}; P=profiles
 cd "$(dirname "$0")/.."
 cp $G/pytest_gpu.log $P/${T}_pytest_gpu.log; cp $G/bench.json $P/${T}_bench.json; cp $G/bench_details.json $P/${T}_bench_details.json
 cp $G/bench_f64.json $P/${T}_bench_f64.json; cp $G/bench_c5_dist.json $P/${T}_bench_c5_full_job_1rank_rccl.json

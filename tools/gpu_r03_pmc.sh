@@ -1,11 +1,12 @@
 #!/bin/bash
 # Round 3: HBM-side traffic counters for the BASELINE configurations that had none (C3, C4, C5 chunk), per kernel.
 # Separate rocprofv3 --pmc passes (FETCH_SIZE needs 3 of the 4 TCC slots, WRITE_SIZE 2; MI355X_MICROARCH.md), no trace
-# domains next to --pmc.  Output: gpurun_out/pmc_<cfg>_<set>/..., summary gpurun_out/pmc_traffic_<cfg>.json
+# domains next to --pmc.  Output: $EVIDENCE_DIR/pmc_<cfg>_<set>/..., summary $EVIDENCE_DIR/pmc_traffic_<cfg>.json (default evidence/)
 # (the correction of /opt/skills/guides/MI355X_MICROARCH.md: KB units, FETCH_SIZE x 2 on gfx950 for 16 B/lane streams).
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+export EVIDENCE_DIR=${EVIDENCE_DIR:-evidence}
+mkdir -p "$EVIDENCE_DIR"
 R="$PWD"
 export TMPDIR=/tmp
 cd /tmp
@@ -15,17 +16,18 @@ for cfg in "${LIST[@]}"; do
   set -- $cfg
   for cs in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "hit:TCC_HIT_sum TCC_MISS_sum" "req:TCC_REQ_sum TCC_READ_sum TCC_WRITE_sum"; do
     name=${cs%%:*}; ctrs=${cs#*:}
-    timeout 400 rocprofv3 --pmc $ctrs --output-format csv -d "$R/gpurun_out/pmc_$1_$name" -o "$name" -- python "$R/tools/run_config.py" $2 $3 $4 $5 > "$R/gpurun_out/pmc_$1_$name.log" 2>&1
+    timeout 400 rocprofv3 --pmc $ctrs --output-format csv -d "$R/$EVIDENCE_DIR/pmc_$1_$name" -o "$name" -- python "$R/tools/run_config.py" $2 $3 $4 $5 > "$R/$EVIDENCE_DIR/pmc_$1_$name.log" 2>&1
     echo "$1 $name rc=$?"
   done
 done
 cd "$R"
 python - <<'PY'
 import csv, collections, glob, json, os
-for d in sorted(set(p.split("/")[1].rsplit("_", 1)[0] for p in glob.glob("gpurun_out/pmc_*_*/"))):
+G = os.environ["EVIDENCE_DIR"]
+for d in sorted(set(os.path.basename(os.path.dirname(p)).rsplit("_", 1)[0] for p in glob.glob(f"{G}/pmc_*_*/"))):
     cfg = d[len("pmc_"):]
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
-    for f in glob.glob(f"gpurun_out/pmc_{cfg}_*/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{G}/pmc_{cfg}_*/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             if "fourier_hip" in r["Kernel_Name"]:
                 acc[r["Kernel_Name"].replace("fourier_hip::", "").replace("(fourier_hip::PassArgs)", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
@@ -41,6 +43,6 @@ for d in sorted(set(p.split("/")[1].rsplit("_", 1)[0] for p in glob.glob("gpurun
         if "TCC_HIT_sum" in row and "TCC_MISS_sum" in row and row["TCC_HIT_sum"] + row["TCC_MISS_sum"] > 0:
             row["l2_hit_rate"] = row["TCC_HIT_sum"] / (row["TCC_HIT_sum"] + row["TCC_MISS_sum"])
         out["kernels"][k] = row
-    json.dump(out, open(f"gpurun_out/pmc_traffic_{cfg}.json", "w"), indent=1)
+    json.dump(out, open(f"{G}/pmc_traffic_{cfg}.json", "w"), indent=1)
     print(cfg, json.dumps({k: {n: round(v, 4) if isinstance(v, float) and v < 10 else round(v) for n, v in r.items()} for k, r in out["kernels"].items()}, indent=1))
 PY

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Folds the per-config PMC summaries of tools/gpu_r03_pmc.sh (gpurun_out/pmc_traffic_<cfg>.json: HBM-side bytes per
+"""Folds the per-config PMC summaries of tools/gpu_r03_pmc.sh ($EVIDENCE_DIR/pmc_traffic_<cfg>.json: HBM-side bytes per
 kernel dispatch, FETCH_SIZE corrected x2 as MI355X_MICROARCH.md prescribes) into profiles/traffic_latest.json under
 "configs", keyed by bench.py's kernel slot names, and copies the raw summaries to profiles/<tag>_pmc_traffic_<cfg>.json.
 usage: python tools/pmc_to_traffic.py <tag>"""
@@ -9,7 +9,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, os.environ.get("EVIDENCE_DIR", "evidence")), os.path.join(ROOT, "profiles")
 CFG = {"c2": "c2", "c3": "c3", "c4": "c4", "c5chunk": "c5"}
 
 
