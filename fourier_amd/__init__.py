@@ -4,4 +4,4 @@ Only the hot path lives here: csrc/ (HIP kernels + the C ABI of include/fourier.
 mirror of the reference's operator interface (fft.py).
 """
 from .fft import (Fft, FourierError, RealFft, Transform, create_fft_f32, create_fft_f64, create_rfft_f32, create_rfft_f64,  # noqa: F401
-                  get_default_option, set_default_option)
+                  fft2, fftn, get_default_option, set_default_option)

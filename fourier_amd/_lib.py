@@ -21,7 +21,9 @@ EXT_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES
 # real-input transforms (fourier_hip_real_*)
 REAL_SYMBOLS = [f"fourier_hip_real_{op}_{s}" for s in SUFFIXES
                 for op in ("create", "destroy", "size", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS
+# transforms along a strided axis (methods of the complex handle)
+AXIS_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES for op in ("transform_axis", "reserve_axis", "describe_axis")]
+ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS
 
 
 def bind(cdll, strict=True):
@@ -57,6 +59,10 @@ def bind(cdll, strict=True):
             f = getattr(cdll, f"fourier_hip_real_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
             f = getattr(cdll, f"fourier_hip_real_describe_{s}"); f.restype = cp; f.argtypes = [vp]
             f = getattr(cdll, f"fourier_hip_real_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
+        if strict or hasattr(cdll, f"fourier_hip_transform_axis_{s}"):
+            f = getattr(cdll, f"fourier_hip_transform_axis_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, sz, ci, vp]
+            f = getattr(cdll, f"fourier_hip_reserve_axis_{s}"); f.restype = ci; f.argtypes = [vp, sz, sz]
+            f = getattr(cdll, f"fourier_hip_describe_axis_{s}"); f.restype = cp; f.argtypes = [vp, sz]
     cdll.fourier_hip_status_string.restype = cp
     cdll.fourier_hip_status_string.argtypes = [ci]
     if strict or hasattr(cdll, "fourier_hip_set_default_option"):

@@ -13,6 +13,7 @@
 // for CPU-side logic tests only.
 #include "plan.h"
 #include "real_plan.h"
+#include "axis_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -129,6 +130,29 @@ FOURIER_DEFINE_ABI(double, double)
 
 FOURIER_DEFINE_REAL_ABI(float, float)
 FOURIER_DEFINE_REAL_ABI(double, double)
+
+// transforms along a strided axis (include/fourier.h, fourier_hip_transform_axis_*): methods of the complex handle, its error model
+#define FOURIER_DEFINE_AXIS_ABI(T, SUFFIX)                                                                       \
+  extern "C" int fourier_hip_transform_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                     size_t outer, size_t inner, int code, void* stream) {      \
+    const Plan<T>* p = (const Plan<T>*)h;                                                                        \
+    return guarded<T>(p, [&] { AxisRoute<T>::of(*p).transform(d_in, d_out, outer, inner, code, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_reserve_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, size_t outer, size_t inner) { \
+    const Plan<T>* p = (const Plan<T>*)h;                                                                        \
+    return guarded<T>(p, [&] { AxisRoute<T>::of(*p).reserve(outer, inner); });                                   \
+  }                                                                                                              \
+  extern "C" const char* fourier_hip_describe_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, size_t inner) {   \
+    static thread_local std::string s;                                                                           \
+    s.clear();                                                                                                   \
+    if (h) {                                                                                                     \
+      try { s = AxisRoute<T>::of(*(const Plan<T>*)h).describe(inner); } catch (...) {}                           \
+    }                                                                                                            \
+    return s.c_str();                                                                                            \
+  }
+
+FOURIER_DEFINE_AXIS_ABI(float, float)
+FOURIER_DEFINE_AXIS_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -169,6 +169,7 @@ typedef void (*TinyKernel)(TinyArgs);
 typedef void (*GenKernel)(GenArgs);
 typedef void (*BluKernel)(BluArgs);
 typedef void (*RealKernel)(RealArgs);
+typedef void (*AxisKernel)(AxisArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -242,6 +243,8 @@ template <typename T> struct Real {};
   BluKernel get_blu_kernel(Real<T>, int which); /* 0 = pre, 1 = post, 2 = mul */                                       \
   /* kernels_real.cpp: the sweeps of the real-input transforms, which = REAL_POST ... REAL_PART (kernel_args.h) */        \
   RealKernel get_real_kernel(Real<T>, int which);                                                                      \
+  /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
+  AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \
   MixKernelFn get_mixed_rt_kernel(Real<T>, int maxp, int ppt, int nt);                                                 \
   /* kernels_mixed_ct.cpp, compiled FOURIER_MIX_SHARDS times per precision (-DFOURIER_MIX_SHARD=i): shard i of the  */  \

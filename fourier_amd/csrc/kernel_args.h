@@ -155,6 +155,25 @@ struct RealArgs {
   uint64_t n, rows;           // odd N: real length, rows in this launch
 };
 
+// ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
+// axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
+// base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols
+// (leading dimension ld_in, block stride bs_in) -> their transposes (leading dimension ld_out, block stride bs_out), 32 x 32
+// tiles; byte offsets are 32-bit (the plan launches at most AXIS_LAUNCH_BYTES of either side per launch).
+struct AxisArgs {
+  const void* in; void* out;
+  uint64_t block;             // lane: N * inner, elements between outer blocks
+  uint64_t inner;             // lane: elements between the rows j of a column
+  uint32_t cols, total;       // lane: columns per block, blocks * cols lanes; transpose: source columns
+  uint32_t div_m, div_l;      // lane: idx / cols = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t rows, tiles_r, tiles_c, blocks;  // transpose: source rows; 32-row / 32-column tiles per block; blocks
+  uint32_t ld_in, ld_out;     // transpose: leading dimensions (elements)
+  uint64_t bs_in, bs_out;     // transpose: block strides (elements)
+  uint32_t in_bytes, out_bytes;  // transpose: descriptor ranges of this launch
+  int swap;                   // lane: inverse = swap . DFT . swap
+  double scale;               // lane: applied on the store
+};
+
 // ---- XCD-fused one-launch plan (kernels_experiments.h)
 struct FusedArgs {
   PassArgs a, b;       // pass A / pass B arguments; a.in, a.out, b.in, b.out are set per item

@@ -68,8 +68,12 @@ static inline void host_fft_any(std::vector<double>& re, std::vector<double>& im
   }
 }
 
+template <typename T> class AxisRoute;  // transforms along a strided axis (axis_plan.h), built on first use
+
 // ---------------------------------------------------------------------------------------------
 template <typename T> class Plan {
+  friend class AxisRoute<T>;
+
  public:
   static constexpr size_t ELEM = sizeof(cpx<T>);
 
@@ -82,6 +86,9 @@ template <typename T> class Plan {
     if (device >= count) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "bad device index");
     device_ = device;
     DeviceGuard g(device_);
+    // the axis transforms' development switches (experiments library and emulator build only; axis_plan.h)
+    if (const char* e = dev_env("FOURIER_AXIS_SCRATCH_BYTES")) axis_scratch_bytes_ = (size_t)std::strtoull(e, nullptr, 10);
+    if (const char* e = dev_env("FOURIER_AXIS_ROUTE")) axis_force_transpose_ = std::string(e) == "transpose";
     if (is_pow2(n)) {
       eng_.reset(new Pow2Engine<T>(n, false, true));
       // f32 2^20 = 1024 x 1024 (BASELINE configs[1]): every XCD walks its range of transforms in bands of eight adjacent tiles
@@ -897,6 +904,9 @@ template <typename T> class Plan {
   unsigned nxcd_ = 8, nxcd_last_ = 0;
   mutable int status_ = 0;
   std::string desc_;
+  mutable std::shared_ptr<AxisRoute<T>> axis_;  // (shared_ptr: AxisRoute<T> is incomplete here)
+  size_t axis_scratch_bytes_ = 0;               // 0: AXIS_SCRATCH_BYTES
+  bool axis_force_transpose_ = false;
 };
 
 template <typename T> static Plan<T>* create_plan(size_t n, int device) {

@@ -144,6 +144,58 @@ class Fft:
     def model_bytes(self):
         return getattr(self._L, f"fourier_hip_model_bytes_{self._suffix}")(self._h)
 
+    # -- transforms along a strided axis (extension) -----------------------------------------
+    def transform_axis_ptr(self, d_in, d_out, outer, inner, transform, stream=0):
+        """Raw-pointer form: the middle axis of an [outer][size][inner] complex array on device memory, enqueued on `stream`."""
+        st = getattr(self._L, f"fourier_hip_transform_axis_{self._suffix}")(
+            self._h, d_in, d_out, int(outer), int(inner), int(transform), stream)
+        if st != 0:
+            raise FourierError(self._L.fourier_hip_status_string(st).decode())
+
+    def reserve_axis(self, outer, inner):
+        """Pre-size the plan-owned buffers so that later axis calls of at most outer x inner never allocate."""
+        st = getattr(self._L, f"fourier_hip_reserve_axis_{self._suffix}")(self._h, int(outer), int(inner))
+        if st != 0:
+            raise FourierError(self._L.fourier_hip_status_string(st).decode())
+
+    def describe_axis(self, inner):
+        """The route an axis call with this `inner` takes (include/fourier.h)."""
+        return getattr(self._L, f"fourier_hip_describe_axis_{self._suffix}")(self._h, int(inner)).decode()
+
+    def transform_axis(self, input, output, transform, dim):
+        """Transform contiguous CUDA complex tensors along dimension `dim` (shape[dim] == size()), on the current stream.
+        input may be output (in place); any other overlap is refused."""
+        import torch
+
+        want = torch.complex64 if self.real == "f32" else torch.complex128
+        for t in (input, output):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == want and t.is_contiguous()):
+                raise TypeError(f"expected contiguous CUDA {want} tensors")
+            if t.device.index != self.device:
+                raise ValueError(f"tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
+        if input.shape != output.shape:
+            raise ValueError(f"shapes {tuple(input.shape)} and {tuple(output.shape)} differ")
+        nd = input.dim()
+        if not -nd <= dim < nd:
+            raise ValueError(f"dim {dim} out of range for {nd} dimensions")
+        dim %= nd
+        if input.shape[dim] != self._n:
+            raise ValueError(f"dimension {dim} has {input.shape[dim]} elements, plan size is {self._n}")
+        a0, b0 = input.data_ptr(), output.data_ptr()
+        nbytes = input.numel() * input.element_size()
+        if a0 != b0 and a0 < b0 + nbytes and b0 < a0 + nbytes:
+            raise ValueError("input and output overlap partially")
+        outer = 1
+        for d in input.shape[:dim]:
+            outer *= d
+        inner = 1
+        for d in input.shape[dim + 1:]:
+            inner *= d
+        if outer * inner == 0:
+            return
+        stream = torch.cuda.current_stream(input.device).cuda_stream
+        self.transform_axis_ptr(a0, b0, outer, inner, int(transform), stream)
+
     # -- plumbing --------------------------------------------------------------------------
     def _dispatch(self, input, output, transform):
         code = int(transform)
@@ -304,3 +356,57 @@ def create_fft_f32(size, device=-1):
 def create_fft_f64(size, device=-1):
     """fourier/src/lib.rs:49-60."""
     return Fft(size, "f64", device)
+
+
+_PLANS = {}
+
+
+def _plan(n, real, device):
+    """Plans of fftn / fft2, cached per (length, precision, device)."""
+    key = (int(n), real, int(device))
+    p = _PLANS.get(key)
+    if p is None:
+        p = _PLANS[key] = Fft(n, real, device)
+    return p
+
+
+def fftn(x, dims=None, transform=Transform.Fft, out=None):
+    """N-dimensional transform of a contiguous CUDA complex64 / complex128 tensor over `dims` (default: all), one axis transform per
+    dimension on the current stream.  Returns a new tensor, or `out` (which may be `x`).  Scaling per axis as numpy: Ifft is ifftn,
+    the sqrt-scaled codes are norm="ortho"."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.complex64, torch.complex128) and x.is_contiguous()):
+        raise TypeError("expected a contiguous CUDA complex64 / complex128 tensor")
+    transform = Transform(transform)
+    nd = x.dim()
+    dims = tuple(range(nd)) if dims is None else tuple(dims)
+    norm = []
+    for d in dims:
+        if not -nd <= d < nd:
+            raise ValueError(f"dim {d} out of range for {nd} dimensions")
+        norm.append(d % nd)
+    if len(set(norm)) != len(norm):
+        raise ValueError(f"repeated dimension in {dims}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out is not x:
+        if not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.shape == x.shape
+                and out.device == x.device):
+            raise TypeError("out must be a contiguous CUDA tensor of the input's shape, dtype and device")
+    real = "f32" if x.dtype == torch.complex64 else "f64"
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    src = x
+    for d in norm:
+        if x.shape[d] == 1:  # a 1-point transform is the identity under every code
+            continue
+        _plan(x.shape[d], real, device).transform_axis(src, out, transform, d)
+        src = out
+    if src is x and out is not x:  # every axis skipped
+        out.copy_(x)
+    return out
+
+
+def fft2(x, transform=Transform.Fft, out=None):
+    """fftn over the last two dimensions."""
+    return fftn(x, (-2, -1), transform, out)

@@ -353,6 +353,34 @@ const char *fourier_hip_real_describe_double(const FOURIER_STRUCT fourier_real_f
 int fourier_hip_real_last_status_float(const FOURIER_STRUCT fourier_real_fft_float *);
 int fourier_hip_real_last_status_double(const FOURIER_STRUCT fourier_real_fft_double *);
 
+/* ---------------- transforms along a strided axis (extension; the reference has none) ------------------
+ * A complex plan of length N transforms along the middle axis of an [outer][N][inner] array of interleaved complex T on DEVICE
+ * memory: element (o, j, c) at element offset (o*N + j)*inner + c, the result in the same layout.  inner == 1 is
+ * fourier_hip_transform_batch_* with batch = outer (the same kernels, the same bits).  The five transform codes keep their meaning
+ * and scaling (an inverse is swap . DFT . swap, the scale computed in T).  d_in == d_out is in place; a partial overlap, a NULL
+ * pointer, a pointer not aligned to 2*sizeof(T) or an unknown code give FOURIER_HIP_INVALID_ARGUMENT (and set the handle's last
+ * status).  outer * inner == 0 is a successful no-op.  Stream-ordered on `stream` like the batched call.
+ * The route depends on N and inner only (fourier_hip_describe_axis_* names it):
+ *   inner == 1                                       the plan's own route ("<the plan's describe>")
+ *   N <= 32                                          one lane per column, one HBM round trip ("axis lane: N")
+ *   N = 2^k in 64 ... 2048, inner a power of two     the last pass of the power-of-two plans down the columns, one round trip
+ *     >= the pass's tile width (f32: 32 columns up   ("axis column tile: L=N"); also (N/16) * inner * 2*sizeof(T) <= 2^31
+ *     to N = 256, 16 above; f64: half that)
+ *   anything else                                    a tiled transpose into plan-owned scratch (at most 1 GiB, walked in chunks),
+ *                                                    the plan's transform there, the transpose back ("axis transpose: <describe>")
+ * The first call with a larger outer x inner than any before may allocate the scratch unless fourier_hip_reserve_axis_* was called
+ * for at least that outer x inner. */
+int fourier_hip_transform_axis_float(const FOURIER_STRUCT fourier_fft_float *, const void *d_in, void *d_out,
+                                     FOURIER_SIZE_TYPE outer, FOURIER_SIZE_TYPE inner, int transform, void *stream);
+int fourier_hip_transform_axis_double(const FOURIER_STRUCT fourier_fft_double *, const void *d_in, void *d_out,
+                                      FOURIER_SIZE_TYPE outer, FOURIER_SIZE_TYPE inner, int transform, void *stream);
+/* Afterwards, axis calls of at most this outer x inner (with the same inner's route) never allocate. */
+int fourier_hip_reserve_axis_float(const FOURIER_STRUCT fourier_fft_float *, FOURIER_SIZE_TYPE outer, FOURIER_SIZE_TYPE inner);
+int fourier_hip_reserve_axis_double(const FOURIER_STRUCT fourier_fft_double *, FOURIER_SIZE_TYPE outer, FOURIER_SIZE_TYPE inner);
+/* The route an axis call with this `inner` takes (see above); inner == 1 returns fourier_hip_describe_*.  "" for a NULL handle. */
+const char *fourier_hip_describe_axis_float(const FOURIER_STRUCT fourier_fft_float *, FOURIER_SIZE_TYPE inner);
+const char *fourier_hip_describe_axis_double(const FOURIER_STRUCT fourier_fft_double *, FOURIER_SIZE_TYPE inner);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -390,6 +418,12 @@ template <typename T> struct fft;
                                void *stream = nullptr) const {                                     \
       return ::fourier::c::fourier_hip_transform_batch_##SUFFIX(impl.get(), d_in, d_out, batch,    \
                                                                 static_cast<int>(t), stream);      \
+    }                                                                                              \
+    /* transform along the middle axis of an [outer][size][inner] array on device memory (extension) */ \
+    int transform_axis_device(const void *d_in, void *d_out, std::size_t outer, std::size_t inner, \
+                              ::fourier::transform t, void *stream = nullptr) const {              \
+      return ::fourier::c::fourier_hip_transform_axis_##SUFFIX(impl.get(), d_in, d_out, outer, inner, \
+                                                               static_cast<int>(t), stream);       \
     }                                                                                              \
     /* many transforms in host memory, streamed through the device (extension) */                 \
     int transform_batch_host(const ::std::complex<T> *in, ::std::complex<T> *out, std::size_t batch, \
