@@ -23,7 +23,10 @@ REAL_SYMBOLS = [f"fourier_hip_real_{op}_{s}" for s in SUFFIXES
                 for op in ("create", "destroy", "size", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
 # transforms along a strided axis (methods of the complex handle)
 AXIS_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES for op in ("transform_axis", "reserve_axis", "describe_axis")]
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS
+# real-input N-D transforms (fourier_hip_realnd_*)
+REALND_SYMBOLS = [f"fourier_hip_realnd_{op}_{s}" for s in SUFFIXES
+                  for op in ("create", "destroy", "rank", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
+ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS
 
 
 def bind(cdll, strict=True):
@@ -63,6 +66,15 @@ def bind(cdll, strict=True):
             f = getattr(cdll, f"fourier_hip_transform_axis_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, sz, ci, vp]
             f = getattr(cdll, f"fourier_hip_reserve_axis_{s}"); f.restype = ci; f.argtypes = [vp, sz, sz]
             f = getattr(cdll, f"fourier_hip_describe_axis_{s}"); f.restype = cp; f.argtypes = [vp, sz]
+        if strict or hasattr(cdll, f"fourier_hip_realnd_create_{s}"):
+            f = getattr(cdll, f"fourier_hip_realnd_create_{s}"); f.restype = vp; f.argtypes = [ci, ctypes.POINTER(sz), ci]
+            f = getattr(cdll, f"fourier_hip_realnd_destroy_{s}"); f.restype = None; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_realnd_rank_{s}"); f.restype = ci; f.argtypes = [vp]
+            for op in ("forward_batch", "inverse_batch"):
+                f = getattr(cdll, f"fourier_hip_realnd_{op}_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci, vp]
+            f = getattr(cdll, f"fourier_hip_realnd_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
+            f = getattr(cdll, f"fourier_hip_realnd_describe_{s}"); f.restype = cp; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_realnd_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
     cdll.fourier_hip_status_string.restype = cp
     cdll.fourier_hip_status_string.argtypes = [ci]
     if strict or hasattr(cdll, "fourier_hip_set_default_option"):

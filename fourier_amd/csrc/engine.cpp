@@ -14,6 +14,7 @@
 #include "plan.h"
 #include "real_plan.h"
 #include "axis_plan.h"
+#include "realnd_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -153,6 +154,41 @@ FOURIER_DEFINE_REAL_ABI(double, double)
 
 FOURIER_DEFINE_AXIS_ABI(float, float)
 FOURIER_DEFINE_AXIS_ABI(double, double)
+
+// real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*): the same error model as the real handle
+#define FOURIER_DEFINE_REALND_ABI(T, SUFFIX)                                                                     \
+  extern "C" fc::fourier_realnd_fft_##SUFFIX* fourier_hip_realnd_create_##SUFFIX(int rank, const size_t* shape, int device) { \
+    return (fc::fourier_realnd_fft_##SUFFIX*)create_realnd_plan<T>(rank, shape, device);                         \
+  }                                                                                                              \
+  extern "C" void fourier_hip_realnd_destroy_##SUFFIX(fc::fourier_realnd_fft_##SUFFIX* h) {                      \
+    try { delete (RealNdPlan<T>*)h; } catch (...) {}                                                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_realnd_rank_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {                    \
+    return h ? ((const RealNdPlan<T>*)h)->rank() : 0;                                                            \
+  }                                                                                                              \
+  extern "C" int fourier_hip_realnd_forward_batch_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, const void* d_in, \
+                                                           void* d_out, size_t batch, int code, void* stream) {  \
+    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_realnd_inverse_batch_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, const void* d_in, \
+                                                           void* d_out, size_t batch, int code, void* stream) {  \
+    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_realnd_reserve_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, size_t batch) {   \
+    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
+    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
+  }                                                                                                              \
+  extern "C" const char* fourier_hip_realnd_describe_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {        \
+    return h ? ((const RealNdPlan<T>*)h)->describe() : "";                                                       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_realnd_last_status_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {             \
+    return h ? ((const RealNdPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                      \
+  }
+
+FOURIER_DEFINE_REALND_ABI(float, float)
+FOURIER_DEFINE_REALND_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -142,7 +142,10 @@ struct ChirpzArgs {
 // real_post_kernel / real_pre_kernel: one lane per mirrored pair (j, h - j) of a row, j <= h / 2, over a flat index of
 // rows x pairs; byte offsets are 32-bit (the plan launches at most REAL_LAUNCH_BYTES of either side per launch).  The odd-N sweeps
 // (plain grid-stride loops between user rows and the complex N-point work array) read in, out, n and rows only.
-enum { REAL_POST = 0, REAL_PRE = 1, REAL_WIDEN = 2, REAL_NARROW = 3, REAL_EXTEND = 4, REAL_PART = 5 };
+// realnd_post_kernel / realnd_pre_kernel (the N-D sweeps of RealNdPlan, realnd_plan.h): one workgroup per row r of an item and
+// segment of its `lanes` lanes; workgroup index = row * segs + segment, row = item * rows + r, r = (i_a * n_b + i_b) * n_c + i_c
+// over the leading sizes nd[0 .. 2] (unused ones 1).  Row bases are 64-bit, offsets within a row 32-bit.
+enum { REAL_POST = 0, REAL_PRE = 1, REAL_WIDEN = 2, REAL_NARROW = 3, REAL_EXTEND = 4, REAL_PART = 5, REAL_ND_POST = 6, REAL_ND_PRE = 7 };
 struct RealArgs {
   const void* in; void* out;
   const void* tw;             // W_N^j, j <= h / 2 (f64 on the host, cast)
@@ -153,6 +156,10 @@ struct RealArgs {
   uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
   double scale;               // forward: the code's scale; inverse: the code's scale / N (the inner IFFT runs unscaled)
   uint64_t n, rows;           // odd N: real length, rows in this launch
+  uint32_t nd_rows, lanes;    // N-D: rows per item (product of the leading sizes), lanes per row (h / 2 rounded up)
+  uint32_t segs;              // N-D: workgroups per row
+  uint32_t nd[3];             // N-D: leading sizes n_a, n_b, n_c (unused ones 1)
+  uint32_t seg_m, seg_l, row_m, row_l, c_m, c_l, b_m, b_l;  // N-D: multiply-high dividers by segs, nd_rows, nd[2], nd[1]
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -16,6 +16,8 @@ RealKernel get_real_kernel(Real<TUReal>, int which) {
     case REAL_NARROW: return &real_narrow_kernel<T>;
     case REAL_EXTEND: return &real_extend_kernel<T>;
     case REAL_PART: return &real_part_kernel<T>;
+    case REAL_ND_POST: return &realnd_post_kernel<T>;
+    case REAL_ND_PRE: return &realnd_pre_kernel<T>;
     default: return nullptr;
   }
 }

@@ -64,6 +64,10 @@ template <typename T> class RealPlan {
     check(d_in, d_out, batch, n_ * sizeof(T), (h_ + 1) * ELEM);
     if (code != ::fourier::c::FOURIER_TRANSFORM_FFT && code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT)
       throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not a forward transform code");
+    run_forward(d_in, d_out, batch, code, stream);
+  }
+  // forward / inverse after the argument checks (RealNdPlan's composed route runs rows of odd N whose reals start on any T)
+  void run_forward(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
     if (batch == 0) return;
     Guard g(inner_->device());
     const size_t chunk = prepare(batch);
@@ -89,6 +93,9 @@ template <typename T> class RealPlan {
     if (code != ::fourier::c::FOURIER_TRANSFORM_IFFT && code != ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT &&
         code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT)
       throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not an inverse transform code");
+    run_inverse(d_in, d_out, batch, code, stream);
+  }
+  void run_inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
     if (batch == 0) return;
     Guard g(inner_->device());
     const size_t chunk = prepare(batch);

@@ -337,6 +337,60 @@ def create_rfft_f64(size, device=-1):
     return RealFft(size, "f64", device)
 
 
+class RealFftN:
+    """Batched real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*) over items of `shape` (1 ... 4 dimensions, the
+    last one real) on device memory, numpy's rfftn / irfftn layout: an item of reals has `shape`, an item of the half spectrum has
+    shape[:-1] + (shape[-1]//2+1,).  Forward codes Fft / SqrtScaledFft, inverse codes Ifft / UnscaledIfft / SqrtScaledIfft, scaled
+    over the product of the lengths."""
+
+    def __init__(self, shape, real, device=-1):
+        import ctypes
+
+        self._suffix = {"f32": "float", "f64": "double"}[real]
+        self.real = real
+        self._L = _lib.lib()
+        self.shape = tuple(int(n) for n in shape)
+        dims = (ctypes.c_size_t * max(1, len(self.shape)))(*self.shape)
+        self._h = getattr(self._L, f"fourier_hip_realnd_create_{self._suffix}")(len(self.shape), dims, int(device))
+        if not self._h:
+            raise FourierError(f"cannot create real N-D FFT plan of shape {self.shape}")
+
+    def rank(self):
+        return len(self.shape)
+
+    def half_shape(self):
+        return self.shape[:-1] + (self.shape[-1] // 2 + 1,)
+
+    def describe(self):
+        return getattr(self._L, f"fourier_hip_realnd_describe_{self._suffix}")(self._h).decode()
+
+    def _check(self, st):
+        if st != 0:
+            raise FourierError(self._L.fourier_hip_status_string(st).decode())
+
+    def forward_batch_ptr(self, d_in, d_out, batch, transform=Transform.Fft, stream=0):
+        """`batch` items of reals at d_in -> `batch` items of the half spectrum at d_out, enqueued on `stream`."""
+        self._check(getattr(self._L, f"fourier_hip_realnd_forward_batch_{self._suffix}")(
+            self._h, d_in, d_out, int(batch), int(transform), stream))
+
+    def inverse_batch_ptr(self, d_in, d_out, batch, transform=Transform.Ifft, stream=0):
+        """`batch` items of the half spectrum at d_in -> `batch` items of reals at d_out (d_in is not modified)."""
+        self._check(getattr(self._L, f"fourier_hip_realnd_inverse_batch_{self._suffix}")(
+            self._h, d_in, d_out, int(batch), int(transform), stream))
+
+    def reserve(self, batch):
+        """Pre-size the plan-owned buffers: later calls of at most `batch` items never allocate."""
+        self._check(getattr(self._L, f"fourier_hip_realnd_reserve_{self._suffix}")(self._h, int(batch)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                getattr(self._L, f"fourier_hip_realnd_destroy_{self._suffix}")(h)
+            except Exception:
+                pass
+
+
 def set_default_option(key, value):
     """Library-wide default for plans created afterwards (include/fourier.h: fourier_hip_set_default_option), e.g.
     ("specialise_at_create", 2): lengths whose prime factors stop at 13 get their own kernels compiled inside create_fft_*."""
@@ -410,3 +464,130 @@ def fftn(x, dims=None, transform=Transform.Fft, out=None):
 def fft2(x, transform=Transform.Fft, out=None):
     """fftn over the last two dimensions."""
     return fftn(x, (-2, -1), transform, out)
+
+
+_REALND_PLANS = {}
+
+
+def _realnd_plan(shape, real, device):
+    """Plans of rfftn / irfftn, cached per (shape, precision, device)."""
+    key = (tuple(int(n) for n in shape), real, int(device))
+    p = _REALND_PLANS.get(key)
+    if p is None:
+        p = _REALND_PLANS[key] = RealFftN(key[0], real, device)
+    return p
+
+
+def realnd_layout(ndim, dims):
+    """The `dims` of rfftn / irfftn on a tensor of `ndim` dimensions -> (dims normalised to 0 ... ndim-1, in the given order with
+    the real axis last; perm), where perm is None if the transformed dimensions are the trailing block (in any order) with the real
+    axis last, so that the plan runs on the tensor as it is, and otherwise the permutation (batch dimensions in order, then the
+    transformed ones with the real axis last) that movedim applies before a contiguous copy (the slow case)."""
+    dims = tuple(range(ndim)) if dims is None else tuple(dims)
+    if not dims:
+        raise ValueError("no dimension to transform")
+    if len(dims) > 4:
+        raise ValueError(f"at most 4 transformed dimensions, got {len(dims)}")
+    norm = []
+    for d in dims:
+        d = int(d)
+        if not -ndim <= d < ndim:
+            raise ValueError(f"dim {d} out of range for {ndim} dimensions")
+        norm.append(d % ndim)
+    if len(set(norm)) != len(norm):
+        raise ValueError(f"repeated dimension in {dims}")
+    k = len(norm)
+    if sorted(norm) == list(range(ndim - k, ndim)) and norm[-1] == ndim - 1:
+        return tuple(norm), None
+    batch = [d for d in range(ndim) if d not in norm]
+    return tuple(norm), tuple(batch + sorted(norm[:-1]) + [norm[-1]])
+
+
+def _realnd_run(x, dims, shape_of, forward, transform, out, out_dtype, real):
+    """rfftn / irfftn behind the layout rule of realnd_layout: the plan of the transformed shape over the batch in front."""
+    import torch
+
+    norm, perm = realnd_layout(x.dim(), dims)
+    src = x if perm is None else x.permute(perm).contiguous()
+    k = len(norm)
+    shape = shape_of(tuple(src.shape[src.dim() - k:]))  # the real-side shape of one item
+    half = shape[:-1] + (shape[-1] // 2 + 1,)
+    res_shape = tuple(src.shape[:src.dim() - k]) + (half if forward else shape)
+    if perm is None:
+        want = res_shape
+    else:
+        inv = [0] * len(perm)
+        for i, d in enumerate(perm):
+            inv[d] = i
+        want = tuple(res_shape[inv[d]] for d in range(len(perm)))
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == out_dtype and out.is_contiguous()
+                                and tuple(out.shape) == want and out.device == x.device):
+        raise TypeError(f"out must be a contiguous CUDA {out_dtype} tensor of shape {want} on the input's device")
+    res = out if (out is not None and perm is None) else torch.empty(res_shape, dtype=out_dtype, device=x.device)
+    items = 1
+    for n in src.shape[:src.dim() - k]:
+        items *= n
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    plan = _realnd_plan(shape, real, device)
+    if items:
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if forward:
+            plan.forward_batch_ptr(src.data_ptr(), res.data_ptr(), items, transform, stream)
+        else:
+            plan.inverse_batch_ptr(src.data_ptr(), res.data_ptr(), items, transform, stream)
+    if perm is None:
+        return res
+    back = res.permute(inv)
+    if out is None:
+        return back.contiguous()
+    out.copy_(back)
+    return out
+
+
+def rfftn(x, dims=None, transform=Transform.Fft, out=None):
+    """Real-input N-dimensional transform of a contiguous CUDA float32 / float64 tensor over `dims` (default: all, at most 4; the last
+    entry is the real axis, whose length L becomes L//2+1), on the current stream, numpy's rfftn layout and scaling (SqrtScaledFft is
+    norm="ortho").  Dimensions outside `dims` are the batch.  Returns a new complex tensor, or `out`.  When `dims` are not the trailing
+    block with the real axis last, the input is permuted into a contiguous copy first and the result permuted back (slower)."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.is_contiguous()):
+        raise TypeError("expected a contiguous CUDA float32 / float64 tensor")
+    transform = Transform(transform)
+    if not transform.is_forward():
+        raise ValueError(f"{transform!r} is not a forward transform")
+    real, cdt = ("f32", torch.complex64) if x.dtype == torch.float32 else ("f64", torch.complex128)
+    return _realnd_run(x, dims, lambda s: s, True, transform, out, cdt, real)
+
+
+def irfftn(X, dims=None, n=None, transform=Transform.Ifft, out=None):
+    """Inverse of rfftn: a contiguous CUDA complex64 / complex128 half spectrum over `dims` (the last entry is the half-spectrum axis)
+    -> reals, `n` (default 2 * (X.shape[last] - 1)) on the real axis, on the current stream.  numpy's irfftn scaling: Ifft is the
+    default, SqrtScaledIfft is norm="ortho", UnscaledIfft is norm="forward".  Input that is not Hermitian gives numpy's result.
+    X is not modified."""
+    import torch
+
+    if not (_is_torch(X) and X.is_cuda and X.dtype in (torch.complex64, torch.complex128) and X.is_contiguous()):
+        raise TypeError("expected a contiguous CUDA complex64 / complex128 tensor")
+    transform = Transform(transform)
+    if transform.is_forward():
+        raise ValueError(f"{transform!r} is not an inverse transform")
+    real, rdt = ("f32", torch.float32) if X.dtype == torch.complex64 else ("f64", torch.float64)
+
+    def shape_of(s):
+        m = 2 * (s[-1] - 1) if n is None else int(n)
+        if m < 1 or m // 2 + 1 != s[-1]:
+            raise ValueError(f"real length {m} does not match {s[-1]} half-spectrum values")
+        return s[:-1] + (m,)
+
+    return _realnd_run(X, dims, shape_of, False, transform, out, rdt, real)
+
+
+def rfft2(x, transform=Transform.Fft, out=None):
+    """rfftn over the last two dimensions."""
+    return rfftn(x, (-2, -1), transform, out)
+
+
+def irfft2(X, n=None, transform=Transform.Ifft, out=None):
+    """irfftn over the last two dimensions."""
+    return irfftn(X, (-2, -1), n, transform, out)

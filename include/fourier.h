@@ -353,6 +353,54 @@ const char *fourier_hip_real_describe_double(const FOURIER_STRUCT fourier_real_f
 int fourier_hip_real_last_status_float(const FOURIER_STRUCT fourier_real_fft_float *);
 int fourier_hip_real_last_status_double(const FOURIER_STRUCT fourier_real_fft_double *);
 
+/* ---------------- real-input N-D transforms (extension; the reference has none) ------------------------
+ * Batched real-input transforms over the trailing `rank` (1 ... 4) dimensions, numpy's rfftn / irfftn layout, on DEVICE memory.
+ * A handle is made for the shape [n_1, ..., n_rank] of one item; the last dimension W is the real one:
+ *   forward  d_in:  `batch` contiguous items of n_1 x ... x n_{rank-1} x W reals T;
+ *            d_out: `batch` contiguous items of n_1 x ... x n_{rank-1} x (W/2+1) interleaved complex T.
+ *            FOURIER_TRANSFORM_FFT: rfftn(x); FOURIER_TRANSFORM_SQRT_SCALED_FFT: rfftn(x) / sqrt(P), P = n_1 x ... x W.
+ *   inverse  d_in:  items of the half-spectrum shape; d_out: items of reals.
+ *            FOURIER_TRANSFORM_IFFT: irfftn(X, s=shape); FOURIER_TRANSFORM_UNSCALED_IFFT: P * irfftn; FOURIER_TRANSFORM_SQRT_SCALED_IFFT:
+ *            sqrt(P) * irfftn.  Input that is not Hermitian in columns 0 and W/2 gives numpy's result (the leading inverses run
+ *            first, the last axis drops the imaginary parts of its bins 0 and W/2).  d_in is NOT modified.
+ * The argument checks and error codes are those of fourier_hip_real_*: a code of the other direction, d_in == d_out or any overlap,
+ * a NULL pointer or a pointer not aligned to 2*sizeof(T) give FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op;
+ * stream-ordered on `stream`.  Rank 1 runs a real-input plan of length W (the same kernels and bits as fourier_hip_real_*).  Even
+ * W (rank >= 2) runs the "packed" route: the W/2-point complex plan on the rows, one axis transform per leading dimension
+ * (fourier_hip_transform_axis_*'s routes), one untangle sweep; odd W runs the "composed" route, real rows then the axis transforms
+ * (a correctness path).  The plan owns a scratch of at most 1 GiB (never less than one item) and walks larger batches in chunks of
+ * whole items; after fourier_hip_realnd_reserve_* for `batch` items, calls of at most `batch` items never allocate.
+ * fourier_hip_realnd_describe_* names the route ("realnd packed: ...", "realnd composed: ...", "realnd rank 1: ..."), the row
+ * plan and the axis route of each leading dimension.  Handles are Send, not Sync; status of the last call:
+ * fourier_hip_realnd_last_status_*. */
+struct fourier_realnd_fft_float;
+struct fourier_realnd_fft_double;
+
+/* NULL on failure: rank outside 1 ... 4, a NULL shape or a size 0. */
+struct fourier_realnd_fft_float *fourier_hip_realnd_create_float(int rank, const FOURIER_SIZE_TYPE *shape, int device);
+struct fourier_realnd_fft_double *fourier_hip_realnd_create_double(int rank, const FOURIER_SIZE_TYPE *shape, int device);
+/* NULL is a no-op. */
+void fourier_hip_realnd_destroy_float(FOURIER_STRUCT fourier_realnd_fft_float *);
+void fourier_hip_realnd_destroy_double(FOURIER_STRUCT fourier_realnd_fft_double *);
+/* rank; 0 for a NULL handle. */
+int fourier_hip_realnd_rank_float(const FOURIER_STRUCT fourier_realnd_fft_float *);
+int fourier_hip_realnd_rank_double(const FOURIER_STRUCT fourier_realnd_fft_double *);
+int fourier_hip_realnd_forward_batch_float(const FOURIER_STRUCT fourier_realnd_fft_float *, const void *d_in, void *d_out,
+                                           FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_realnd_forward_batch_double(const FOURIER_STRUCT fourier_realnd_fft_double *, const void *d_in, void *d_out,
+                                            FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_realnd_inverse_batch_float(const FOURIER_STRUCT fourier_realnd_fft_float *, const void *d_in, void *d_out,
+                                           FOURIER_SIZE_TYPE batch, int transform, void *stream);
+int fourier_hip_realnd_inverse_batch_double(const FOURIER_STRUCT fourier_realnd_fft_double *, const void *d_in, void *d_out,
+                                            FOURIER_SIZE_TYPE batch, int transform, void *stream);
+/* Pre-size every plan-owned buffer: afterwards calls of at most `batch` items never allocate. */
+int fourier_hip_realnd_reserve_float(const FOURIER_STRUCT fourier_realnd_fft_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_realnd_reserve_double(const FOURIER_STRUCT fourier_realnd_fft_double *, FOURIER_SIZE_TYPE batch);
+const char *fourier_hip_realnd_describe_float(const FOURIER_STRUCT fourier_realnd_fft_float *);
+const char *fourier_hip_realnd_describe_double(const FOURIER_STRUCT fourier_realnd_fft_double *);
+int fourier_hip_realnd_last_status_float(const FOURIER_STRUCT fourier_realnd_fft_float *);
+int fourier_hip_realnd_last_status_double(const FOURIER_STRUCT fourier_realnd_fft_double *);
+
 /* ---------------- transforms along a strided axis (extension; the reference has none) ------------------
  * A complex plan of length N transforms along the middle axis of an [outer][N][inner] array of interleaved complex T on DEVICE
  * memory: element (o, j, c) at element offset (o*N + j)*inner + c, the result in the same layout.  inner == 1 is
@@ -481,6 +529,49 @@ template <typename T> struct real_fft;
 FOURIER_DEFINE_CXX_REAL_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_REAL_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_REAL_WRAPPER
+
+/* real-input N-D transforms on device memory (extension): fourier::real_fft_nd<float> / <double> */
+template <typename T> struct real_fft_nd;
+
+#define FOURIER_DEFINE_CXX_REALND_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct real_fft_nd<T> {                                                                \
+    real_fft_nd(int rank, const std::size_t *shape, int device = -1)                                 \
+        : impl(::fourier::c::fourier_hip_realnd_create_##SUFFIX(rank, shape, device),                \
+               ::fourier::c::fourier_hip_realnd_destroy_##SUFFIX) {}                                 \
+    real_fft_nd() = delete;                                                                          \
+    real_fft_nd(const real_fft_nd &) = delete;                                                       \
+    real_fft_nd(real_fft_nd &&) = default;                                                           \
+    real_fft_nd &operator=(const real_fft_nd &) = delete;                                            \
+    real_fft_nd &operator=(real_fft_nd &&) = default;                                                \
+    ~real_fft_nd() = default;                                                                        \
+    int rank() const { return ::fourier::c::fourier_hip_realnd_rank_##SUFFIX(impl.get()); }         \
+    /* items of reals -> items of the half-spectrum shape */                                         \
+    int forward_batch_device(const void *d_in, void *d_out, std::size_t batch,                       \
+                             ::fourier::transform t = ::fourier::transform::fft,                     \
+                             void *stream = nullptr) const {                                         \
+      return ::fourier::c::fourier_hip_realnd_forward_batch_##SUFFIX(impl.get(), d_in, d_out, batch, \
+                                                                     static_cast<int>(t), stream);   \
+    }                                                                                                \
+    /* items of the half-spectrum shape -> items of reals */                                         \
+    int inverse_batch_device(const void *d_in, void *d_out, std::size_t batch,                       \
+                             ::fourier::transform t = ::fourier::transform::ifft,                    \
+                             void *stream = nullptr) const {                                         \
+      return ::fourier::c::fourier_hip_realnd_inverse_batch_##SUFFIX(impl.get(), d_in, d_out, batch, \
+                                                                     static_cast<int>(t), stream);   \
+    }                                                                                                \
+    int reserve(std::size_t batch) const {                                                           \
+      return ::fourier::c::fourier_hip_realnd_reserve_##SUFFIX(impl.get(), batch);                   \
+    }                                                                                                \
+    const char *describe() const { return ::fourier::c::fourier_hip_realnd_describe_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                               \
+                                                                                                     \
+  private:                                                                                           \
+    ::std::unique_ptr<::fourier::c::fourier_realnd_fft_##SUFFIX,                                     \
+                      void (*)(::fourier::c::fourier_realnd_fft_##SUFFIX *)> impl;                   \
+  };
+FOURIER_DEFINE_CXX_REALND_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_REALND_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_REALND_WRAPPER
 
 } /* namespace fourier */
 #endif
