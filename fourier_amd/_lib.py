@@ -26,7 +26,10 @@ AXIS_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES for op in ("transform_
 # real-input N-D transforms (fourier_hip_realnd_*)
 REALND_SYMBOLS = [f"fourier_hip_realnd_{op}_{s}" for s in SUFFIXES
                   for op in ("create", "destroy", "rank", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS
+# convolution with a prepared filter bank (fourier_hip_conv_*)
+CONV_SYMBOLS = [f"fourier_hip_conv_{op}_{s}" for s in SUFFIXES
+                for op in ("create", "destroy", "size", "filters", "set_filters", "apply", "reserve", "set_option", "describe", "last_status")]
+ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS
 
 
 def bind(cdll, strict=True):
@@ -75,6 +78,17 @@ def bind(cdll, strict=True):
             f = getattr(cdll, f"fourier_hip_realnd_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
             f = getattr(cdll, f"fourier_hip_realnd_describe_{s}"); f.restype = cp; f.argtypes = [vp]
             f = getattr(cdll, f"fourier_hip_realnd_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
+        if strict or hasattr(cdll, f"fourier_hip_conv_create_{s}"):
+            f = getattr(cdll, f"fourier_hip_conv_create_{s}"); f.restype = vp; f.argtypes = [sz, ci, ci]
+            f = getattr(cdll, f"fourier_hip_conv_destroy_{s}"); f.restype = None; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_conv_size_{s}"); f.restype = sz; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_conv_filters_{s}"); f.restype = sz; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_conv_set_filters_{s}"); f.restype = ci; f.argtypes = [vp, vp, sz, sz, ci, vp]
+            f = getattr(cdll, f"fourier_hip_conv_apply_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, vp]
+            f = getattr(cdll, f"fourier_hip_conv_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
+            f = getattr(cdll, f"fourier_hip_conv_set_option_{s}"); f.restype = ci; f.argtypes = [vp, cp, ll]
+            f = getattr(cdll, f"fourier_hip_conv_describe_{s}"); f.restype = cp; f.argtypes = [vp]
+            f = getattr(cdll, f"fourier_hip_conv_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
     cdll.fourier_hip_status_string.restype = cp
     cdll.fourier_hip_status_string.argtypes = [ci]
     if strict or hasattr(cdll, "fourier_hip_set_default_option"):

@@ -15,6 +15,7 @@
 #include "real_plan.h"
 #include "axis_plan.h"
 #include "realnd_plan.h"
+#include "conv_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -189,6 +190,48 @@ FOURIER_DEFINE_AXIS_ABI(double, double)
 
 FOURIER_DEFINE_REALND_ABI(float, float)
 FOURIER_DEFINE_REALND_ABI(double, double)
+
+// convolution with a prepared filter bank (include/fourier.h, fourier_hip_conv_*): the same error model as the real handle
+#define FOURIER_DEFINE_CONV_ABI(T, SUFFIX)                                                                       \
+  extern "C" fc::fourier_conv_##SUFFIX* fourier_hip_conv_create_##SUFFIX(size_t size, int real_data, int device) { \
+    return (fc::fourier_conv_##SUFFIX*)create_conv_plan<T>(size, real_data != 0, device);                        \
+  }                                                                                                              \
+  extern "C" void fourier_hip_conv_destroy_##SUFFIX(fc::fourier_conv_##SUFFIX* h) {                              \
+    try { delete (ConvPlan<T>*)h; } catch (...) {}                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_conv_size_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                         \
+    return h ? ((const ConvPlan<T>*)h)->size() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_conv_filters_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                      \
+    return h ? ((const ConvPlan<T>*)h)->filters() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" int fourier_hip_conv_set_filters_##SUFFIX(fc::fourier_conv_##SUFFIX* h, const void* d_taps, size_t taps, \
+                                                       size_t filters, int correlate, void* stream) {            \
+    ConvPlan<T>* p = (ConvPlan<T>*)h;                                                                            \
+    return guarded_handle(p, [&] { p->set_filters(d_taps, taps, filters, correlate != 0, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_conv_apply_##SUFFIX(const fc::fourier_conv_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                 size_t batch, void* stream) {                                   \
+    const ConvPlan<T>* p = (const ConvPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->apply(d_in, d_out, batch, (hipStream_t)stream); });                        \
+  }                                                                                                              \
+  extern "C" int fourier_hip_conv_reserve_##SUFFIX(const fc::fourier_conv_##SUFFIX* h, size_t batch) {           \
+    const ConvPlan<T>* p = (const ConvPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
+  }                                                                                                              \
+  extern "C" int fourier_hip_conv_set_option_##SUFFIX(fc::fourier_conv_##SUFFIX* h, const char* key, long long v) { \
+    if (!h || !key) return fc::FOURIER_HIP_INVALID_ARGUMENT;                                                     \
+    try { return ((ConvPlan<T>*)h)->set_option(key, v); } catch (...) { return fc::FOURIER_HIP_INVALID_ARGUMENT; } \
+  }                                                                                                              \
+  extern "C" const char* fourier_hip_conv_describe_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                \
+    return h ? ((const ConvPlan<T>*)h)->describe() : "";                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_conv_last_status_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                     \
+    return h ? ((const ConvPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                        \
+  }
+
+FOURIER_DEFINE_CONV_ABI(float, float)
+FOURIER_DEFINE_CONV_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -170,6 +170,7 @@ typedef void (*GenKernel)(GenArgs);
 typedef void (*BluKernel)(BluArgs);
 typedef void (*RealKernel)(RealArgs);
 typedef void (*AxisKernel)(AxisArgs);
+typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -233,9 +234,13 @@ template <typename T> struct Real {};
   /* kernels_pass.cpp: one tile shape (CG) per pass length L; conv = forward LAST + (.) w + inverse FIRST */           \
   KernelInfo get_kernel(Real<T>, int L, int mode, int io);                                                             \
   KernelInfo get_conv_kernel(Real<T>, int L);                                                                          \
+  /* ... the same kernel reading one table of a filter bank per transform (ConvPlan) */                                 \
+  KernelInfo get_conv_bank_kernel(Real<T>, int L);                                                                     \
   /* kernels_onelaunch.cpp: 2^11..2^15 in one launch; whole chirp-z in one launch for M = 2^k <= 2^15 */                \
   bool get_twolevel_kernel(Real<T>, int k, KernelInfo& info, int& l1, int& l2);                                        \
   bool get_blu_small_kernel(Real<T>, int k, KernelInfo& info);                                                         \
+  /* ... and the circular convolution with a filter bank in one launch for the two-level plans of 2^11 ... 2^15 */       \
+  bool get_conv_small_kernel(Real<T>, int k, KernelInfo& info);                                                        \
   /* kernels_misc.cpp */                                                                                               \
   TinyKernel get_tiny_kernel(Real<T>, size_t n);                                                                       \
   OddKernel get_odd_kernel(Real<T>, int r);                                                                            \
@@ -243,6 +248,8 @@ template <typename T> struct Real {};
   BluKernel get_blu_kernel(Real<T>, int which); /* 0 = pre, 1 = post, 2 = mul */                                       \
   /* kernels_real.cpp: the sweeps of the real-input transforms, which = REAL_POST ... REAL_PART (kernel_args.h) */        \
   RealKernel get_real_kernel(Real<T>, int which);                                                                      \
+  /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_PAD (kernel_args.h) */             \
+  ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

@@ -263,6 +263,41 @@ template <typename T> class Pow2Engine {
     PROF_END(prof);
   }
 
+  // Convolution with a filter bank in one launch (conv_small_kernel; the convolution handle): available when this plan is a one-launch
+  // two-level plan of 2^11 ... 2^15; like the chirp-z kernel it needs the inter-pass table of the role-swapped L2 x L1 problem.
+  bool enable_conv_small() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    if (conv_small_.fn) return true;
+    if (!get_conv_small_kernel(Real<T>{}, ilog2(n_), conv_small_)) return false;
+    if (!passes_[0]->tw_hi.p) {  // (enable_bluestein_small uploads the same table)
+      std::vector<cpx<T>> tw(n_);
+      for (int k1 = 0; k1 < tl2_; ++k1)
+        for (int i = 0; i < tl1_; ++i) {
+          double re, im;
+          unit_root((uint64_t)i * (uint64_t)k1, n_, re, im);
+          tw[(size_t)k1 * tl1_ + i] = {(T)re, (T)im};
+        }
+      passes_[0]->tw_hi.upload(tw);
+    }
+    set_smem_attribute(conv_small_);
+    return true;
+  }
+  // in == out allowed; bank: `filters` tables of n entries, transform b of the launch multiplies by table (first_row + b) mod filters
+  void run_conv_small(const cpx<T>* in, cpx<T>* out, size_t batch, const void* bank, uint32_t filters, uint32_t first_row,
+                      hipStream_t stream, unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.mul = bank; a.bank_filters = filters; a.bank_first = first_row;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    if (batch > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
+    FOURIER_LAUNCH(conv_small_.fn, batch, conv_small_.NT, conv_small_.smem, stream, a);
+  }
+
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
   void init_l2fused(int k) {
     FusedInfo fi;
@@ -625,13 +660,23 @@ template <typename T> class Pow2Engine {
     }
     conv_st_ = it->second.get();
   }
+  // the same launch with a filter bank (ConvPlan): enable_conv plus the kernel that picks one table per transform
+  void enable_conv_bank() {
+    if (!can_conv()) return;
+    enable_conv();
+    conv_bank_ = get_conv_bank_kernel(Real<T>{}, passes_.back()->k.L);
+    set_smem_attribute(conv_bank_);
+  }
+  bool has_conv_bank() const { return conv_bank_.fn != nullptr; }
+  int pass_len(size_t p) const { return passes_[p]->mode == MODE_ODD_LAST ? passes_[p]->odd_r : passes_[p]->k.L; }
   bool palindromic() const {
     for (size_t p = 0; p < passes_.size(); ++p)
       if (passes_[p]->k.L != passes_[passes_.size() - 1 - p]->k.L) return false;
     return true;
   }
+  // filters != 0: wtab is a bank of `filters` tables of n entries, transform b of the launch multiplies by table (first_row + b) mod filters
   void launch_conv(const cpx<T>* src, cpx<T>* dst, size_t batch, const void* wtab, hipStream_t stream, Profiler* prof, int slot,
-                   unsigned nxcd) const {
+                   unsigned nxcd, uint32_t filters = 0, uint32_t first_row = 0) const {
     const Pass& first = *passes_.front();
     const Pass& last = *passes_.back();
     PassArgs a;
@@ -651,10 +696,12 @@ template <typename T> class Pow2Engine {
     static const bool sliced = dev_env("FOURIER_CONV_XCD_PLAIN") == nullptr;  // development switch, read once
     if (sliced && a.nxcd == 8 && a.xcd_interleave == 0 && a.tiles % 8 == 0) a.xcd_interleave = 2;
     a.scale = 1.0;
+    a.bank_filters = filters; a.bank_first = first_row;
+    const KernelInfo& ck = filters ? conv_bank_ : conv_;
     const uint64_t grid = (uint64_t)batch * a.tiles;
     if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
     PROF_BEGIN(prof, slot);
-    FOURIER_LAUNCH(conv_.fn, grid, conv_.NT, conv_.smem, stream, a);
+    FOURIER_LAUNCH(ck.fn, grid, ck.NT, ck.smem, stream, a);
     PROF_END(prof);
   }
 
@@ -662,7 +709,7 @@ template <typename T> class Pow2Engine {
   size_t n_;
   bool tiny_ = false;
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
-  KernelInfo blu_small_, conv_;
+  KernelInfo blu_small_, conv_, conv_bank_, conv_small_;
   StageTables<T>* conv_st_ = nullptr;
   FusedInfo fused_;
   bool fused_on_ = false;

@@ -55,6 +55,10 @@ struct PassArgs {
   int blu_swap;       // user-level inverse: swap re/im of the user data
   int swap_in, swap_out;
   double scale;       // applied on the final store (LAST / ROWS)
+  // fft_conv_kernel with a filter bank (ConvPlan, conv_plan.h): transform b of this launch multiplies by the table at
+  // mul + ((bank_first + b) mod bank_filters) * n; the Bluestein instantiations read neither field
+  uint32_t bank_filters;
+  uint32_t bank_first;  // (the first row of the launch) mod bank_filters
 };
 
 
@@ -160,6 +164,31 @@ struct RealArgs {
   uint32_t segs;              // N-D: workgroups per row
   uint32_t nd[3];             // N-D: leading sizes n_a, n_b, n_c (unused ones 1)
   uint32_t seg_m, seg_l, row_m, row_l, c_m, c_l, b_m, b_l;  // N-D: multiply-high dividers by segs, nd_rows, nd[2], nd[1]
+};
+
+// ---- convolution with a filter bank (kernels_conv.h; ConvPlan, conv_plan.h)
+// conv_mul_kernel: Z[b][k] *= H[(first + b) mod filters][k] over a flat index of rows x len, one lane per element.
+// real_conv_mid_kernel: one lane per mirrored pair (j, h - j) of a row of the inner plan's output, as the real sweeps (`len` = h / 2 + 1
+// lanes per row); untangle, multiply by the half spectrum H (rows of h + 1), retangle, in place.  Byte offsets into the data are
+// 32-bit (at most REAL_LAUNCH_BYTES per launch), the bank is addressed with 64-bit indices.
+// conv_finish_kernel: bank[i] = scale * bank[i] (conjugated where conj != 0), i < count.  conv_pad_kernel: `rows` rows of `taps`
+// words T -> rows of `n` words, zero-extended (a complex value is two words).
+enum { CONV_MUL = 0, CONV_REAL_MID = 1, CONV_FINISH = 2, CONV_PAD = 3 };
+struct ConvArgs {
+  const void* in; void* out;  // the sweeps run in place: in == out
+  const void* tw;             // real mid sweep: W_N^j, j <= h / 2
+  const void* bank;           // H: `filters` rows of `len` (mul) or h + 1 (real mid) complex values
+  uint32_t h;                 // real mid sweep: N / 2
+  uint32_t len;               // lanes per row: complex values per row (mul), h / 2 + 1 pairs (real mid)
+  uint32_t total;             // rows * len
+  uint32_t div_m, div_l;      // idx / len = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t filters, first;    // row b of this launch uses filter (first + b) mod filters, first < filters
+  uint32_t f_m, f_l;          // the same divider for `filters`
+  uint32_t bytes;             // descriptor range of this launch
+  uint64_t n, taps, rows;     // pad: words per output row, words per input row, rows
+  uint64_t count;             // finish: complex values
+  int conj;
+  double scale;
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -78,4 +78,24 @@ bool get_blu_small_kernel(Real<TUReal>, int k, KernelInfo& info) {
   }
 }
 
+// conv_small_kernel: the convolution handle's one-launch route, the shapes of the two-level plans of 2^11 ... 2^15 (f64: ... 2^14)
+template <typename T, int L1, int L2> static KernelInfo make_conv_small_info() {
+  KernelInfo k = make_twolevel_info<T, L1, L2>();
+  k.fn = &conv_small_kernel<T, L1, L2>;
+  return k;
+}
+bool get_conv_small_kernel(Real<TUReal>, int k, KernelInfo& info) {
+  typedef TUReal T;
+  switch (k) {
+    case 11: info = make_conv_small_info<T, 64, 32>(); return true;
+    case 12: info = make_conv_small_info<T, 64, 64>(); return true;
+    case 13: info = make_conv_small_info<T, 128, 64>(); return true;
+    case 14: info = make_conv_small_info<T, 128, 128>(); return true;
+    case 15:
+      if constexpr (sizeof(T) == 4) { info = make_conv_small_info<T, 256, 128>(); return true; }
+      return false;
+    default: return false;
+  }
+}
+
 }  // namespace fourier_hip

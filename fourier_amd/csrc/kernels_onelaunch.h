@@ -408,4 +408,73 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
   }
 }
 
+// ---- circular convolution with a filter bank in ONE launch for N = L1 x L2 <= 2^15 (the convolution handle, conv_plan.h) ----
+// The chirp-z kernel above with the chirp multiplies and the zero padding compiled out and N == M: load, two-level FFT, (.) H of the
+// row's filter (spectrum order, the inverse's 1/N folded in), the same core with the roles of L1 and L2 exchanged as the unscaled
+// inverse, store.  All 16 register rows carry data to and from HBM (the chirp-z kernels move BLU_ROWS = 8 of them, because 2n <= M).
+// One workgroup reads its whole transform before it stores any of it, so in == out is allowed.  Transform b of the launch multiplies
+// by the table at mul + ((bank_first + b) mod bank_filters) * N.
+template <typename T, int L1, int L2>
+__global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SMALL_MIN_WAVES(FOURIER_TWOLEVEL_NT(T, L1, L2)))
+    conv_small_kernel(PassArgs a) {
+  constexpr int VEC = 16 / (2 * (int)sizeof(T));
+  constexpr int CG1 = L2 / VEC, CG2 = L1 / VEC, Q1 = L1 / 16, Q2 = L2 / 16, N = L1 * L2;
+  FOURIER_DYN_SMEM(smem);
+  const int tid = (int)threadIdx.x;
+  uint64_t blk = blockIdx.x;
+  if (a.nxcd > 1) {
+    const uint64_t nwg = gridDim.x, nx = a.nxcd, xcd = blk % nx, q = nwg / nx, r = nwg % nx;
+    blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blk / nx;
+  }
+  constexpr uint32_t NBYTES = (uint32_t)(N * sizeof(cpx<T>));
+  const BufRsrc ri = make_rsrc((const cpx<T>*)a.in + blk * N, NBYTES), ro = make_rsrc((cpx<T>*)a.out + blk * N, NBYTES);
+  constexpr uint32_t ROWB = (uint32_t)(Q1 * L2 * sizeof(cpx<T>));  // register r holds index (th + Q1*r)*L2 + cg*VEC + v
+  cpx<T> x[VEC][16];
+  {
+    const int th = tid / CG1, cg = tid % CG1;
+    const uint32_t voff = (uint32_t)((th * L2 + cg * VEC) * sizeof(cpx<T>));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const Unit16<T> u = buf_load_unit<T, BUF_NT>(ri, voff, (uint32_t)r * ROWB);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) x[v][r] = {u.a[2 * v], u.a[2 * v + 1]};
+    }
+  }
+  twolevel_core<T, L1, L2>(x, tid, smem, (const cpx<T>*)a.tw1, (const cpx<T>*)a.tw2, (const cpx<T>*)a.tw_lo, 0);
+  {  // register r holds X[k1 + L1*k2], k2 = th2 + Q2*r, k1 = cg2*VEC + v: (.) H, then the inverse's leading swap
+    int tb = tid;
+    FOURIER_LAUNDER(tb);
+    const cpx<T>* wt = (const cpx<T>*)a.mul + (uint64_t)((a.bank_first + (uint32_t)blk) % a.bank_filters) * N;
+    const BufRsrc rw = make_rsrc(wt, NBYTES);
+    const uint32_t woff = (uint32_t)(((tb / CG2) * L1 + (tb % CG2) * VEC) * sizeof(cpx<T>));
+    units_batched<T, 8>([&](int r) { return buf_load_unit<T>(rw, woff, (uint32_t)((Q2 * r) * L1 * sizeof(cpx<T>))); },
+                        [&](int r, const Unit16<T>& u) {
+#pragma unroll
+                          for (int v = 0; v < VEC; ++v) {
+                            const cpx<T> y = cmul(x[v][r], cpx<T>{u.a[2 * v], u.a[2 * v + 1]});
+                            x[v][r] = {y.im, y.re};
+                          }
+                        });
+  }
+  __syncthreads();
+  {
+    int t2 = tid;
+    FOURIER_LAUNDER(t2);  // the inverse's lane mappings are derived here, not carried through the forward transform
+    twolevel_core<T, L2, L1>(x, t2, smem, (const cpx<T>*)a.tw2, (const cpx<T>*)a.tw1, (const cpx<T>*)a.tw_hi, 32);
+  }
+  // back in the input's layout: the trailing swap, streaming stores
+  {
+    int tb = tid;
+    FOURIER_LAUNDER(tb);
+    const uint32_t soff = (uint32_t)(((tb / CG1) * L2 + (tb % CG1) * VEC) * sizeof(cpx<T>));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      Unit16<T> u;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) { u.a[2 * v] = x[v][r].im; u.a[2 * v + 1] = x[v][r].re; }
+      buf_store_unit<T, BUF_NT>(ro, soff + (uint32_t)r * ROWB, u);
+    }
+  }
+}
+
 FOURIER_KERNELS_END  // namespace fourier_hip

@@ -69,10 +69,10 @@ KernelInfo get_kernel(Real<TUReal>, int L, int mode, int io) {
 }
 
 // fft_conv_kernel: forward LAST + (.) w + inverse FIRST of a Bluestein plan, same tile shapes as the passes
-template <typename T, int L, int CG> static KernelInfo make_conv_info() {
+template <typename T, int L, int CG, bool BANK = false> static KernelInfo make_conv_info() {
   using C = TileCfg<T, L, CG>;
   KernelInfo k;
-  k.fn = &fft_conv_kernel<T, L, CG>;
+  k.fn = &fft_conv_kernel<T, L, CG, BANK>;
   k.L = L; k.CG = CG; k.NT = C::NT; k.COLS = C::COLS; k.R3 = C::R3;
   k.smem = C::smem_bytes(MODE_FIRST);
   return k;
@@ -86,6 +86,20 @@ KernelInfo get_conv_kernel(Real<TUReal>, int L) {
     case 512: return make_conv_info<T, 512, FOURIER_CG_512>();
     case 1024: return make_conv_info<T, 1024, FOURIER_CG_1024>();
     case 2048: return make_conv_info<T, 2048, FOURIER_CG_2048>();
+    default: break;
+  }
+  throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "no conv kernel for pass length " + std::to_string(L));
+}
+// ... with a filter bank (the convolution handle): one table per transform
+KernelInfo get_conv_bank_kernel(Real<TUReal>, int L) {
+  typedef TUReal T;
+  switch (L) {
+    case 64: return make_conv_info<T, 64, 16, true>();
+    case 128: return make_conv_info<T, 128, 16, true>();
+    case 256: return make_conv_info<T, 256, 16, true>();
+    case 512: return make_conv_info<T, 512, FOURIER_CG_512, true>();
+    case 1024: return make_conv_info<T, 1024, FOURIER_CG_1024, true>();
+    case 2048: return make_conv_info<T, 2048, FOURIER_CG_2048, true>();
     default: break;
   }
   throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "no conv kernel for pass length " + std::to_string(L));

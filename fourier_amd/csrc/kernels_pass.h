@@ -724,7 +724,9 @@ __global__ void __launch_bounds__((L / 16) * CG, FOURIER_MIN_WAVES((L / 16) * CG
 // exactly those elements as its columns i = j, so the M-point spectrum never goes back to HBM: one read and
 // one write of the work array instead of two of each.  The inverse is swap . DFT . swap (mod.rs:366-387):
 // the leading swap happens here, the trailing one in the inverse plan's last pass.
-template <typename T, int L, int CG>
+// BANK (the convolution handle, conv_plan.h): the table is one of a bank of a.bank_filters tables of a.n entries, chosen per
+// transform; the Bluestein instantiations (BANK = false) read one table and compile as before.
+template <typename T, int L, int CG, bool BANK = false>
 __global__ void __launch_bounds__((L / 16) * CG, FOURIER_MIN_WAVES((L / 16) * CG)) fft_conv_kernel(PassArgs a) {
   using C = TileCfg<T, L, CG>;
   constexpr int VEC = C::VEC, Q = C::Q, COLS = C::COLS;
@@ -770,7 +772,9 @@ __global__ void __launch_bounds__((L / 16) * CG, FOURIER_MIN_WAVES((L / 16) * CG
   {
     int t = tid;
     FOURIER_LAUNDER(t);
-    const BufRsrc rw = make_rsrc(a.mul);
+    const cpx<T>* wt = (const cpx<T>*)a.mul;
+    if constexpr (BANK) wt += (uint64_t)((a.bank_first + (uint32_t)b) % a.bank_filters) * a.n;
+    const BufRsrc rw = make_rsrc(wt);
     const uint32_t voff = (uint32_t)(((uint64_t)(t / CG) * a.cn + c0 + (uint64_t)((t % CG) * VEC)) * sizeof(cpx<T>));
     // (eight loads of the w table in flight per thread: 4 and 16 measured slower, as did a streaming hint on them -- the XCD's slice of
     // the table is meant to stay in its L2)

@@ -588,6 +588,64 @@ template <typename T> class Plan {
     }
   }
 
+  // ---- the hook of the convolution handle (ConvPlan, conv_plan.h); exec() is not affected.  enable_conv_bank sets up and returns the
+  // route this plan has for a convolution with a filter bank: CONV_NONE; CONV_ONE_LAUNCH (a one-launch two-level plan, 2^11 ... 2^15: load,
+  // FFT, product, inverse FFT, store in conv_small_kernel); CONV_PASSES (a power-of-two plan of two or more tile passes whose mirror image
+  // exists: forward passes 0 ... np-2, fft_conv_kernel with the bank -- last forward pass, the product with the row's filter, first inverse
+  // pass --, inverse passes 1 ... np-1: the Bluestein sequence below without the chirp I/O).  exec_conv runs `batch` rows; d_in may be
+  // d_out; CONV_PASSES needs two caller-owned work arrays of batch * n elements each.  bank: `filters` tables of n entries in spectrum
+  // order (the inverse's 1/n folded in), row b of the call uses table (first + b) mod filters.  The caller bounds `batch` (ConvPlan's
+  // scratch): the option "chunk_bytes" of exec() does not apply here.
+  enum { CONV_NONE = 0, CONV_ONE_LAUNCH = 1, CONV_PASSES = 2 };
+  int enable_conv_bank() {
+    if (conv_route_ != CONV_NONE || blu_ || !eng_) return conv_route_;
+    DeviceGuard g(device_);
+    if (eng_->enable_conv_small()) return conv_route_ = CONV_ONE_LAUNCH;
+    if (!eng_->can_conv()) return CONV_NONE;
+    const size_t np = eng_->num_passes();
+    std::unique_ptr<Pow2Engine<T>> inv;
+    if (!eng_->palindromic()) {
+      inv.reset(new Pow2Engine<T>(n_, true));
+      if (inv->num_passes() != np) return CONV_NONE;
+      for (size_t p = 0; p < np; ++p)
+        if (inv->pass_len(p) != eng_->pass_len(np - 1 - p)) return CONV_NONE;  // (a plan that is not built from the default lengths)
+    }
+    eng_->enable_conv_bank();
+    if (!eng_->has_conv_bank()) return CONV_NONE;
+    eng_inv_ = std::move(inv);
+    return conv_route_ = CONV_PASSES;
+  }
+  bool exec_conv(const void* d_in, void* d_out, size_t batch, const void* bank, size_t filters, size_t first, void* work_a, void* work_b,
+                 hipStream_t stream) const {
+    if (conv_route_ == CONV_NONE) return false;
+    if (batch == 0) return true;
+    DeviceGuard g(device_);
+    if (conv_route_ == CONV_ONE_LAUNCH) {
+      eng_->run_conv_small((const cpx<T>*)d_in, (cpx<T>*)d_out, batch, bank, (uint32_t)filters, (uint32_t)(first % filters), stream, nxcd_);
+      return true;
+    }
+    const int np = (int)eng_->num_passes();
+    const Pow2Engine<T>& inv = eng_inv_ ? *eng_inv_ : *eng_;
+    cpx<T>* bufs[2] = {(cpx<T>*)work_a, (cpx<T>*)work_b};
+    const cpx<T>* src = (const cpx<T>*)d_in;
+    int cur = 0;
+    for (int p = 0; p + 1 < np; ++p) {
+      eng_->launch_pass((size_t)p, src, bufs[cur], batch, false, 1.0, stream, nullptr, 0, nxcd_);
+      src = bufs[cur]; cur ^= 1;
+    }
+    // (the conv kernel in the tile order every Bluestein plan runs it in, 8 XCDs and launch_conv's slicing -- not this plan's nxcd_, which at
+    // f32 2^20 is the band walk of the plain passes, an order the conv kernel has never been measured or tested in)
+    eng_->launch_conv(src, bufs[cur], batch, bank, stream, nullptr, 0, 8, (uint32_t)filters, (uint32_t)(first % filters));
+    src = bufs[cur]; cur ^= 1;
+    for (int p = 1; p < np; ++p) {
+      const bool last = (p + 1 == np);
+      cpx<T>* dst = last ? (cpx<T>*)d_out : bufs[cur];
+      inv.launch_pass((size_t)p, src, dst, batch, true, 1.0, stream, nullptr, 0, (last && nxcd_last_) ? nxcd_last_ : nxcd_);
+      src = dst; cur ^= 1;
+    }
+    return true;
+  }
+
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).
   void synchronize(hipStream_t stream) const {
     DeviceGuard g(device_);
@@ -876,7 +934,7 @@ template <typename T> class Plan {
   size_t n_, m_ = 0;
   int device_ = 0;
   bool blu_ = false;
-  std::unique_ptr<Pow2Engine<T>> eng_, eng_inv_;  // eng_inv_: mirrored inverse plan of a conv-fused Bluestein
+  std::unique_ptr<Pow2Engine<T>> eng_, eng_inv_;  // eng_inv_: mirrored inverse plan of a conv-fused Bluestein, or of the convolution handle's fused passes (enable_conv_bank)
   std::unique_ptr<BluTiledEngine<T>> blut_;       // Bluestein on a smooth M (then eng_ is empty)
   std::unique_ptr<BluRegEngine<T>> blur_;         // ... of a short transform: one launch, transforms in registers (then eng_ is empty)
   std::unique_ptr<BluRegEngine<T>> regf_;         // a length with factors 5 ... 13 as a direct transform on the same register stages
@@ -901,6 +959,7 @@ template <typename T> class Plan {
   bool fused_ = false;  // Bluestein: chirp steps fused into the inner passes
   bool small_fused_ = false;  // Bluestein with M <= 2^15: everything in one launch
   bool conv_ = false, conv_ok_ = false;  // Bluestein: forward LAST + (.)w + inverse FIRST in one launch
+  int conv_route_ = 0;  // enable_conv_bank: the convolution handle's route on this plan (CONV_NONE ...)
   unsigned nxcd_ = 8, nxcd_last_ = 0;
   mutable int status_ = 0;
   std::string desc_;

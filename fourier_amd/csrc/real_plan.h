@@ -46,6 +46,10 @@ template <typename T> class RealPlan {
   const char* describe() const { return desc_.c_str(); }
   int last_status() const { return status_; }
   void set_status(int s) const { status_ = s; }
+  // the pieces the convolution handle's fused untangle route runs by itself (conv_plan.h): the inner plan, W_N^j (even N)
+  bool even() const { return even_; }
+  const Plan<T>& inner() const { return *inner_; }
+  const void* twiddles() const { return tw_.p; }
 
   // rows per chunk for a call of `batch` rows; sizes the scratch and the inner plan's buffers for it (reserve: ahead of time, so
   // that later calls of at most `batch` rows never allocate)

@@ -337,6 +337,133 @@ def create_rfft_f64(size, device=-1):
     return RealFft(size, "f64", device)
 
 
+class FftConv:
+    """Batched circular convolution / correlation with a prepared filter bank (include/fourier.h, fourier_hip_conv_*) on device
+    memory: rows of N complex values (real_data=False) or N reals (real_data=True) in, rows of the same shape out, row b with filter
+    b mod F.  The filters are given in the time domain (set_filters) and transformed once."""
+
+    def __init__(self, size, real, real_data=False, device=-1):
+        self._suffix = {"f32": "float", "f64": "double"}[real]
+        self.real = real
+        self.real_data = bool(real_data)
+        self._L = _lib.lib()
+        self._h = getattr(self._L, f"fourier_hip_conv_create_{self._suffix}")(int(size), int(self.real_data), int(device))
+        if not self._h:
+            raise FourierError(f"cannot create convolution plan of size {size}")
+        self._n = int(size)
+
+    def size(self):
+        return self._n
+
+    def filters(self):
+        return int(getattr(self._L, f"fourier_hip_conv_filters_{self._suffix}")(self._h))
+
+    def describe(self):
+        return getattr(self._L, f"fourier_hip_conv_describe_{self._suffix}")(self._h).decode()
+
+    def _check(self, st):
+        if st != 0:
+            raise FourierError(self._L.fourier_hip_status_string(st).decode())
+
+    def set_option(self, key, value):
+        """"fusion": 1 (default) / 0 = the composed route (forward transform, product sweep, inverse transform)."""
+        self._check(getattr(self._L, f"fourier_hip_conv_set_option_{self._suffix}")(self._h, key.encode(), int(value)))
+
+    def reserve(self, batch):
+        """Pre-size the plan-owned buffers: later apply calls of at most `batch` rows never allocate."""
+        self._check(getattr(self._L, f"fourier_hip_conv_reserve_{self._suffix}")(self._h, int(batch)))
+
+    def set_filters_ptr(self, d_taps, taps, filters=1, correlate=False, stream=0):
+        """`filters` rows of `taps` values of the handle's kind at d_taps -> the bank, enqueued on `stream`."""
+        self._check(getattr(self._L, f"fourier_hip_conv_set_filters_{self._suffix}")(
+            self._h, d_taps, int(taps), int(filters), int(bool(correlate)), stream))
+
+    def apply_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of N values at d_in -> `batch` rows at d_out (d_out may be d_in), enqueued on `stream`."""
+        self._check(getattr(self._L, f"fourier_hip_conv_apply_{self._suffix}")(self._h, d_in, d_out, int(batch), stream))
+
+    def _dtype(self):
+        import torch
+
+        if self.real_data:
+            return torch.float32 if self.real == "f32" else torch.float64
+        return torch.complex64 if self.real == "f32" else torch.complex128
+
+    def set_filters(self, taps, correlate=False):
+        """Contiguous CUDA tensor of shape (taps,) or (F, taps), of the handle's dtype, 1 <= taps <= N; on the current stream."""
+        import torch
+
+        dtype = self._dtype()
+        if not (_is_torch(taps) and taps.is_cuda and taps.dtype == dtype and taps.is_contiguous()):
+            raise TypeError(f"expected a contiguous CUDA {dtype} tensor")
+        if taps.dim() not in (1, 2) or taps.numel() == 0 or taps.shape[-1] > self._n:
+            raise ValueError(f"taps must have shape (taps,) or (F, taps) with 1 <= taps <= {self._n}, got {tuple(taps.shape)}")
+        stream = torch.cuda.current_stream(taps.device).cuda_stream
+        self.set_filters_ptr(taps.data_ptr(), taps.shape[-1], taps.numel() // taps.shape[-1], correlate, stream)
+
+    def apply(self, x, out=None):
+        """Contiguous (..., N) CUDA tensor of the handle's dtype -> a new tensor of the same shape, or `out` (which may be `x`), on
+        the current stream.  Row b of the flattened leading dimensions uses filter b mod F."""
+        import torch
+
+        dtype = self._dtype()
+        if not (_is_torch(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous()):
+            raise TypeError(f"expected a contiguous CUDA {dtype} tensor")
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out is not x:
+            if not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.shape == x.shape
+                    and out.device == x.device):
+                raise TypeError("out must be a contiguous CUDA tensor of the input's shape, dtype and device")
+        batch = x.numel() // self._n
+        if batch:
+            self.apply_ptr(x.data_ptr(), out.data_ptr(), batch, torch.cuda.current_stream(x.device).cuda_stream)
+        return out
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                getattr(self._L, f"fourier_hip_conv_destroy_{self._suffix}")(h)
+            except Exception:
+                pass
+
+
+def create_conv_f32(size, real_data=False, device=-1):
+    return FftConv(size, "f32", real_data, device)
+
+
+def create_conv_f64(size, real_data=False, device=-1):
+    return FftConv(size, "f64", real_data, device)
+
+
+_CONV_PLANS = {}
+
+
+def fftconv(x, taps, correlate=False, out=None):
+    """Circular convolution (or correlation) of the rows of a contiguous (..., N) CUDA tensor with `taps` of shape (taps,) or
+    (F, taps) and the same dtype: complex64 / complex128 rows, or float32 / float64 rows (real data).  Handles are cached per
+    (N, dtype, device) and the filters are set on EVERY call -- the slow way to apply the same filters repeatedly; keep an FftConv
+    for that."""
+    import torch
+
+    kinds = {torch.complex64: ("f32", False), torch.complex128: ("f64", False), torch.float32: ("f32", True), torch.float64: ("f64", True)}
+    if not (_is_torch(x) and x.is_cuda and x.dtype in kinds and x.is_contiguous()):
+        raise TypeError("expected a contiguous CUDA complex64 / complex128 / float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    real, real_data = kinds[x.dtype]
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (int(x.shape[-1]), x.dtype, int(device))
+    p = _CONV_PLANS.get(key)
+    if p is None:
+        p = _CONV_PLANS[key] = FftConv(x.shape[-1], real, real_data, device)
+    p.set_filters(taps, correlate)
+    return p.apply(x, out)
+
+
 class RealFftN:
     """Batched real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*) over items of `shape` (1 ... 4 dimensions, the
     last one real) on device memory, numpy's rfftn / irfftn layout: an item of reals has `shape`, an item of the half spectrum has

@@ -429,6 +429,79 @@ int fourier_hip_reserve_axis_double(const FOURIER_STRUCT fourier_fft_double *, F
 const char *fourier_hip_describe_axis_float(const FOURIER_STRUCT fourier_fft_float *, FOURIER_SIZE_TYPE inner);
 const char *fourier_hip_describe_axis_double(const FOURIER_STRUCT fourier_fft_double *, FOURIER_SIZE_TYPE inner);
 
+/* ---------------- convolution with a prepared filter bank (extension; the reference has none) ----------
+ * A handle is made for a length N >= 1, a kind of data (real_data == 0: rows of N interleaved complex T, else rows of N reals T) and
+ * a device.  It holds a bank of F >= 1 filters, given in the time domain as `filters` contiguous rows of `taps` values of the
+ * handle's kind (1 <= taps <= N, zero-extended to N) and transformed once by fourier_hip_conv_set_filters_*.
+ * fourier_hip_conv_apply_* then maps `batch` contiguous rows at d_in to `batch` rows at d_out on DEVICE memory, row b with filter
+ * b mod F (b counted over the whole call):
+ *   convolution (circular, length N)   y[b] = ifft(fft(x[b]) * fft(h[b mod F], N))
+ *   correlation (correlate != 0)       y[b] = ifft(fft(x[b]) * conj(fft(h[b mod F], N))),  y[b][n] = sum_m x[b][(n+m) mod N] conj(h[m])
+ * scaled as numpy's ifft / irfft (the 1/N lives in the stored spectra).  Real data: real taps, real rows in and out; the half
+ * spectrum never leaves the library.  A linear ("full", "same", causal) convolution is the caller's zero padding to a length
+ * N >= len(x) + taps - 1.
+ * d_in == d_out is in place and allowed; any other overlap, a NULL pointer, a pointer not aligned to 2*sizeof(T) (also for real
+ * rows; taps: one value of their kind), taps == 0, taps > N, filters == 0, or apply before any filters were set give
+ * FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.  Both calls are stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*: set_filters reads the taps and enqueues the filter transforms there; it may allocate (and so
+ * synchronise) when the bank grows.  It may be called again to replace the bank, not while a call on the handle is in flight.
+ * Routes, chosen at create (fourier_hip_conv_describe_* names the route and the plan under it):
+ *   complex, N = 2^k on two or more tile passes   "conv fused passes: ..."  forward passes but the last, ONE launch for the last
+ *     (2^16 and up; f64 2^15 and up)                forward pass, the product and the first inverse pass, the remaining inverse
+ *                                                   passes: with two passes 3 round trips of HBM per row instead of 5
+ *   complex, N = 2^11 ... 2^15 (f64: ... 2^14),   "conv one-launch: ..."    ONE launch: load, two-level FFT, product, two-level inverse, store on
+ *     the one-launch two-level plans                register-resident data: 1 round trip of HBM per row instead of 3; no scratch
+ *   complex, any other N                          "conv composed: ..."      forward transform into scratch, one product sweep in
+ *                                                   place, unscaled inverse transform
+ *   real, even N                                  "conv real fused untangle: ..."  the N/2-point plan forward into scratch, ONE sweep
+ *                                                   (untangle, product with the half spectrum, retangle) in place, the N/2-point
+ *                                                   plan's unscaled inverse
+ *   real, odd N                                   "conv real composed: ..." rfft into scratch, product sweep, unscaled irfft
+ * Option "fusion" (fourier_hip_conv_set_option_*): 1 (default) as above, 0 = the composed route of the handle's kind.
+ * Bytes per row, algorithmic, the bank not counted (with one filter it stays in the L2; with many every row reads one more
+ * spectrum): complex two-pass fused 6 N E against 10 N E composed (E = 2*sizeof(T)); real fused 5 (N/2) E against 7 (N/2) E.
+ * Device memory the handle owns: the bank, F x N complex (real data: F x (N/2+1)), the plans' own tables and buffers, and a scratch
+ * of at most 1 GiB (never less than one row); larger batches are walked in chunks of it.  A real-data handle sits on a whole
+ * real-input plan (fourier_hip_real_*), which transforms the filters and runs the composed route, and so also keeps that plan's own
+ * scratch, sized by the largest number of filters set so far (at most 1 GiB more).  After fourier_hip_conv_reserve_* for `batch`
+ * rows, apply calls of at most `batch` rows on the route of that moment never allocate; after a change of "fusion" call reserve
+ * again.  The taps are read with plain loads and need the alignment of one value of their kind only.  Handles are Send, not Sync; the status of the last call that
+ * did work (set_filters, apply, reserve) is fourier_hip_conv_last_status_*. */
+struct fourier_conv_float;
+struct fourier_conv_double;
+
+/* NULL on failure (size 0 included). */
+struct fourier_conv_float *fourier_hip_conv_create_float(FOURIER_SIZE_TYPE size, int real_data, int device);
+struct fourier_conv_double *fourier_hip_conv_create_double(FOURIER_SIZE_TYPE size, int real_data, int device);
+/* NULL is a no-op. */
+void fourier_hip_conv_destroy_float(FOURIER_STRUCT fourier_conv_float *);
+void fourier_hip_conv_destroy_double(FOURIER_STRUCT fourier_conv_double *);
+/* N; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_conv_size_float(const FOURIER_STRUCT fourier_conv_float *);
+FOURIER_SIZE_TYPE fourier_hip_conv_size_double(const FOURIER_STRUCT fourier_conv_double *);
+/* F; 0 before set_filters and for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_conv_filters_float(const FOURIER_STRUCT fourier_conv_float *);
+FOURIER_SIZE_TYPE fourier_hip_conv_filters_double(const FOURIER_STRUCT fourier_conv_double *);
+int fourier_hip_conv_set_filters_float(FOURIER_STRUCT fourier_conv_float *, const void *d_taps, FOURIER_SIZE_TYPE taps,
+                                       FOURIER_SIZE_TYPE filters, int correlate, void *stream);
+int fourier_hip_conv_set_filters_double(FOURIER_STRUCT fourier_conv_double *, const void *d_taps, FOURIER_SIZE_TYPE taps,
+                                        FOURIER_SIZE_TYPE filters, int correlate, void *stream);
+int fourier_hip_conv_apply_float(const FOURIER_STRUCT fourier_conv_float *, const void *d_in, void *d_out,
+                                 FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_conv_apply_double(const FOURIER_STRUCT fourier_conv_double *, const void *d_in, void *d_out,
+                                  FOURIER_SIZE_TYPE batch, void *stream);
+/* Pre-size the scratch and the plans' buffers: afterwards apply calls of at most `batch` rows never allocate. */
+int fourier_hip_conv_reserve_float(const FOURIER_STRUCT fourier_conv_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_conv_reserve_double(const FOURIER_STRUCT fourier_conv_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 1 (default) / 0 = the composed route.  FOURIER_HIP_INVALID_ARGUMENT for anything else. */
+int fourier_hip_conv_set_option_float(FOURIER_STRUCT fourier_conv_float *, const char *key, long long value);
+int fourier_hip_conv_set_option_double(FOURIER_STRUCT fourier_conv_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_conv_describe_float(const FOURIER_STRUCT fourier_conv_float *);
+const char *fourier_hip_conv_describe_double(const FOURIER_STRUCT fourier_conv_double *);
+int fourier_hip_conv_last_status_float(const FOURIER_STRUCT fourier_conv_float *);
+int fourier_hip_conv_last_status_double(const FOURIER_STRUCT fourier_conv_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -529,6 +602,50 @@ template <typename T> struct real_fft;
 FOURIER_DEFINE_CXX_REAL_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_REAL_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_REAL_WRAPPER
+
+/* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
+template <typename T> struct conv;
+
+#define FOURIER_DEFINE_CXX_CONV_WRAPPER(T, SUFFIX)                                                  \
+  template <> struct conv<T> {                                                                      \
+    explicit conv(std::size_t size, bool real_data = false, int device = -1)                        \
+        : impl(::fourier::c::fourier_hip_conv_create_##SUFFIX(size, real_data ? 1 : 0, device),     \
+               ::fourier::c::fourier_hip_conv_destroy_##SUFFIX) {}                                  \
+    conv() = delete;                                                                                \
+    conv(const conv &) = delete;                                                                    \
+    conv(conv &&) = default;                                                                        \
+    conv &operator=(const conv &) = delete;                                                         \
+    conv &operator=(conv &&) = default;                                                             \
+    ~conv() = default;                                                                              \
+    std::size_t size() const { return ::fourier::c::fourier_hip_conv_size_##SUFFIX(impl.get()); }   \
+    std::size_t filters() const { return ::fourier::c::fourier_hip_conv_filters_##SUFFIX(impl.get()); } \
+    /* `filters` rows of `taps` values of the handle's kind -> the bank */                          \
+    int set_filters_device(const void *d_taps, std::size_t taps, std::size_t filters = 1,           \
+                           bool correlate = false, void *stream = nullptr) {                        \
+      return ::fourier::c::fourier_hip_conv_set_filters_##SUFFIX(impl.get(), d_taps, taps, filters, \
+                                                                 correlate ? 1 : 0, stream);        \
+    }                                                                                               \
+    /* `batch` rows of N values -> `batch` rows of N values, row b with filter b mod F */           \
+    int apply_device(const void *d_in, void *d_out, std::size_t batch, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_conv_apply_##SUFFIX(impl.get(), d_in, d_out, batch, stream); \
+    }                                                                                               \
+    int reserve(std::size_t batch) const {                                                          \
+      return ::fourier::c::fourier_hip_conv_reserve_##SUFFIX(impl.get(), batch);                    \
+    }                                                                                               \
+    int set_option(const char *key, long long value) {                                              \
+      return ::fourier::c::fourier_hip_conv_set_option_##SUFFIX(impl.get(), key, value);            \
+    }                                                                                               \
+    const char *describe() const { return ::fourier::c::fourier_hip_conv_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_conv_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                              \
+                                                                                                    \
+  private:                                                                                          \
+    ::std::unique_ptr<::fourier::c::fourier_conv_##SUFFIX,                                          \
+                      void (*)(::fourier::c::fourier_conv_##SUFFIX *)> impl;                        \
+  };
+FOURIER_DEFINE_CXX_CONV_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_CONV_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_CONV_WRAPPER
 
 /* real-input N-D transforms on device memory (extension): fourier::real_fft_nd<float> / <double> */
 template <typename T> struct real_fft_nd;
