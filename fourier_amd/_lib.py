@@ -12,90 +12,59 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfourier.so")
 
 SUFFIXES = ("float", "double")
 
-# every symbol include/fourier.h declares
-LEGACY_SYMBOLS = [f"fourier_{op}_{s}" for s in SUFFIXES for op in ("create", "destroy", "transform_in_place", "transform")]
-EXT_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES
-               for op in ("create", "size", "transform_batch", "reserve", "device", "synchronize", "transform_batch_host", "last_status", "set_option", "describe", "model_bytes",
-                          "profile", "slot_names")] + [
-    "fourier_hip_status_string", "fourier_hip_set_default_option", "fourier_hip_get_default_option"]
-# real-input transforms (fourier_hip_real_*)
-REAL_SYMBOLS = [f"fourier_hip_real_{op}_{s}" for s in SUFFIXES
-                for op in ("create", "destroy", "size", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
-# transforms along a strided axis (methods of the complex handle)
-AXIS_SYMBOLS = [f"fourier_hip_{op}_{s}" for s in SUFFIXES for op in ("transform_axis", "reserve_axis", "describe_axis")]
-# real-input N-D transforms (fourier_hip_realnd_*)
-REALND_SYMBOLS = [f"fourier_hip_realnd_{op}_{s}" for s in SUFFIXES
-                  for op in ("create", "destroy", "rank", "forward_batch", "inverse_batch", "reserve", "describe", "last_status")]
-# convolution with a prepared filter bank (fourier_hip_conv_*)
-CONV_SYMBOLS = [f"fourier_hip_conv_{op}_{s}" for s in SUFFIXES
-                for op in ("create", "destroy", "size", "filters", "set_filters", "apply", "reserve", "set_option", "describe", "last_status")]
+vp, sz, ci, ll, cp = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p
+_BATCH = (ci, [vp, vp, vp, sz, ci, vp])  # handle, d_in, d_out, batch, code, stream
+
+# Every entry point include/fourier.h declares, written once: (prefix, {symbol stem: (restype, argtypes)}) per handle family.  A symbol
+# is <prefix><stem>_<float|double>; the lists of names below and bind() are both derived from these tables.
+_LEGACY = ("fourier_", {  # the reference's FFI
+    "create": (vp, [sz]), "destroy": (None, [vp]), "transform_in_place": (None, [vp, vp, ci]), "transform": (None, [vp, vp, vp, ci])})
+_EXT = ("fourier_hip_", {  # the complex handle's extensions
+    "create": (vp, [sz, ci]), "size": (sz, [vp]), "transform_batch": _BATCH, "reserve": (ci, [vp, sz, ci]), "device": (ci, [vp]),
+    "synchronize": (ci, [vp, vp]), "transform_batch_host": (ci, [vp, vp, vp, sz, ci]), "last_status": (ci, [vp]),
+    "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "model_bytes": (ctypes.c_double, [vp]),
+    "profile": (ci, [vp, vp, vp, sz, ci, vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]), "slot_names": (cp, [vp])})
+_REAL = ("fourier_hip_real_", {  # real-input transforms
+    "create": (vp, [sz, ci]), "destroy": (None, [vp]), "size": (sz, [vp]), "forward_batch": _BATCH, "inverse_batch": _BATCH,
+    "reserve": (ci, [vp, sz]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_AXIS = ("fourier_hip_", {  # transforms along a strided axis (methods of the complex handle)
+    "transform_axis": (ci, [vp, vp, vp, sz, sz, ci, vp]), "reserve_axis": (ci, [vp, sz, sz]), "describe_axis": (cp, [vp, sz])})
+_REALND = ("fourier_hip_realnd_", {  # real-input N-D transforms
+    "create": (vp, [ci, ctypes.POINTER(sz), ci]), "destroy": (None, [vp]), "rank": (ci, [vp]), "forward_batch": _BATCH,
+    "inverse_batch": _BATCH, "reserve": (ci, [vp, sz]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_CONV = ("fourier_hip_conv_", {  # convolution with a prepared filter bank
+    "create": (vp, [sz, ci, ci]), "destroy": (None, [vp]), "size": (sz, [vp]), "filters": (sz, [vp]),
+    "set_filters": (ci, [vp, vp, sz, sz, ci, vp]), "apply": (ci, [vp, vp, vp, sz, vp]), "reserve": (ci, [vp, sz]),
+    "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_GLOBAL = {  # no handle, no precision suffix
+    "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
+    "fourier_hip_get_default_option": (ll, [cp])}
+
+
+def _signatures(family):
+    prefix, table = family
+    return {f"{prefix}{op}_{s}": table[op] for s in SUFFIXES for op in table}
+
+
+LEGACY_SYMBOLS = list(_signatures(_LEGACY))
+EXT_SYMBOLS = list(_signatures(_EXT)) + list(_GLOBAL)
+REAL_SYMBOLS = list(_signatures(_REAL))
+AXIS_SYMBOLS = list(_signatures(_AXIS))
+REALND_SYMBOLS = list(_signatures(_REALND))
+CONV_SYMBOLS = list(_signatures(_CONV))
 ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS
 
 
 def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
-    vp, sz, ci, ll, cp = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p
-    for s in SUFFIXES:
-        f = getattr(cdll, f"fourier_create_{s}"); f.restype = vp; f.argtypes = [sz]
-        f = getattr(cdll, f"fourier_destroy_{s}"); f.restype = None; f.argtypes = [vp]
-        f = getattr(cdll, f"fourier_transform_in_place_{s}"); f.restype = None; f.argtypes = [vp, vp, ci]
-        f = getattr(cdll, f"fourier_transform_{s}"); f.restype = None; f.argtypes = [vp, vp, vp, ci]
-        f = getattr(cdll, f"fourier_hip_create_{s}"); f.restype = vp; f.argtypes = [sz, ci]
-        f = getattr(cdll, f"fourier_hip_size_{s}"); f.restype = sz; f.argtypes = [vp]
-        f = getattr(cdll, f"fourier_hip_transform_batch_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci, vp]
-        f = getattr(cdll, f"fourier_hip_transform_batch_host_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci]
-        f = getattr(cdll, f"fourier_hip_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz, ci]
-        f = getattr(cdll, f"fourier_hip_device_{s}"); f.restype = ci; f.argtypes = [vp]
-        if strict or hasattr(cdll, f"fourier_hip_synchronize_{s}"):
-            f = getattr(cdll, f"fourier_hip_synchronize_{s}"); f.restype = ci; f.argtypes = [vp, vp]
-        f = getattr(cdll, f"fourier_hip_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
-        f = getattr(cdll, f"fourier_hip_set_option_{s}"); f.restype = ci; f.argtypes = [vp, cp, ll]
-        f = getattr(cdll, f"fourier_hip_describe_{s}"); f.restype = cp; f.argtypes = [vp]
-        f = getattr(cdll, f"fourier_hip_model_bytes_{s}"); f.restype = ctypes.c_double; f.argtypes = [vp]
-        f = getattr(cdll, f"fourier_hip_profile_{s}"); f.restype = ci
-        f.argtypes = [vp, vp, vp, sz, ci, vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
-        f = getattr(cdll, f"fourier_hip_slot_names_{s}"); f.restype = cp; f.argtypes = [vp]
-        if strict or hasattr(cdll, f"fourier_hip_real_create_{s}"):
-            f = getattr(cdll, f"fourier_hip_real_create_{s}"); f.restype = vp; f.argtypes = [sz, ci]
-            f = getattr(cdll, f"fourier_hip_real_destroy_{s}"); f.restype = None; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_real_size_{s}"); f.restype = sz; f.argtypes = [vp]
-            for op in ("forward_batch", "inverse_batch"):
-                f = getattr(cdll, f"fourier_hip_real_{op}_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci, vp]
-            f = getattr(cdll, f"fourier_hip_real_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
-            f = getattr(cdll, f"fourier_hip_real_describe_{s}"); f.restype = cp; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_real_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
-        if strict or hasattr(cdll, f"fourier_hip_transform_axis_{s}"):
-            f = getattr(cdll, f"fourier_hip_transform_axis_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, sz, ci, vp]
-            f = getattr(cdll, f"fourier_hip_reserve_axis_{s}"); f.restype = ci; f.argtypes = [vp, sz, sz]
-            f = getattr(cdll, f"fourier_hip_describe_axis_{s}"); f.restype = cp; f.argtypes = [vp, sz]
-        if strict or hasattr(cdll, f"fourier_hip_realnd_create_{s}"):
-            f = getattr(cdll, f"fourier_hip_realnd_create_{s}"); f.restype = vp; f.argtypes = [ci, ctypes.POINTER(sz), ci]
-            f = getattr(cdll, f"fourier_hip_realnd_destroy_{s}"); f.restype = None; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_realnd_rank_{s}"); f.restype = ci; f.argtypes = [vp]
-            for op in ("forward_batch", "inverse_batch"):
-                f = getattr(cdll, f"fourier_hip_realnd_{op}_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, ci, vp]
-            f = getattr(cdll, f"fourier_hip_realnd_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
-            f = getattr(cdll, f"fourier_hip_realnd_describe_{s}"); f.restype = cp; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_realnd_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
-        if strict or hasattr(cdll, f"fourier_hip_conv_create_{s}"):
-            f = getattr(cdll, f"fourier_hip_conv_create_{s}"); f.restype = vp; f.argtypes = [sz, ci, ci]
-            f = getattr(cdll, f"fourier_hip_conv_destroy_{s}"); f.restype = None; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_conv_size_{s}"); f.restype = sz; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_conv_filters_{s}"); f.restype = sz; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_conv_set_filters_{s}"); f.restype = ci; f.argtypes = [vp, vp, sz, sz, ci, vp]
-            f = getattr(cdll, f"fourier_hip_conv_apply_{s}"); f.restype = ci; f.argtypes = [vp, vp, vp, sz, vp]
-            f = getattr(cdll, f"fourier_hip_conv_reserve_{s}"); f.restype = ci; f.argtypes = [vp, sz]
-            f = getattr(cdll, f"fourier_hip_conv_set_option_{s}"); f.restype = ci; f.argtypes = [vp, cp, ll]
-            f = getattr(cdll, f"fourier_hip_conv_describe_{s}"); f.restype = cp; f.argtypes = [vp]
-            f = getattr(cdll, f"fourier_hip_conv_last_status_{s}"); f.restype = ci; f.argtypes = [vp]
-    cdll.fourier_hip_status_string.restype = cp
-    cdll.fourier_hip_status_string.argtypes = [ci]
-    if strict or hasattr(cdll, "fourier_hip_set_default_option"):
-        cdll.fourier_hip_set_default_option.restype = ci
-        cdll.fourier_hip_set_default_option.argtypes = [cp, ll]
-        cdll.fourier_hip_get_default_option.restype = ll
-        cdll.fourier_hip_get_default_option.argtypes = [cp]
+    signatures = dict(_GLOBAL)
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV):
+        signatures.update(_signatures(family))
+    for name, (restype, argtypes) in signatures.items():
+        if strict or hasattr(cdll, name):
+            f = getattr(cdll, name)
+            f.restype, f.argtypes = restype, argtypes
     return cdll
 
 

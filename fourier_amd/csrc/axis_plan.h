@@ -17,7 +17,7 @@
 
 namespace fourier_hip {
 
-// Scratch bound of the transpose route, as REAL_SCRATCH_BYTES (real_plan.h).  The experiments library and the emulator build read
+// Scratch bound of the transpose route, the size of REAL_SCRATCH_BYTES (real_plan.h).  The experiments library and the emulator build read
 // FOURIER_AXIS_SCRATCH_BYTES at create instead (the chunk-walk tests); FOURIER_AXIS_ROUTE=transpose sends every call with
 // inner > 1 through the transpose route (the A/B of the bench tool, the route-agreement tests).
 constexpr size_t AXIS_SCRATCH_BYTES = (size_t)1 << 30;
@@ -54,7 +54,7 @@ template <typename T> class AxisRoute {
 
   void reserve(size_t outer, size_t inner) const {
     if (outer == 0 || inner == 0) return;
-    typename Plan<T>::DeviceGuard g(p_.device());
+    DeviceGuard g(p_.device());
     switch (route(inner)) {
       case ROWS: p_.reserve_for(outer, false); p_.reserve_for(outer, true); return;
       case TRANSPOSE: (void)prepare(outer, inner); return;
@@ -63,20 +63,15 @@ template <typename T> class AxisRoute {
   }
 
   void transform(const void* d_in, void* d_out, size_t outer, size_t inner, int code, hipStream_t stream) const {
-    if (!d_in || !d_out) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "null buffer");
-    if ((uintptr_t)d_in % ELEM || (uintptr_t)d_out % ELEM) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "misaligned buffer");
     if (code < 0 || code > 4) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "unknown transform code");
-    if (outer == 0 || inner == 0) return;
     const double total = (double)outer * (double)inner * (double)n_;
     if (total * ELEM >= 9.2e18) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "array too large");
-    const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, bytes = (uintptr_t)(outer * inner * n_ * ELEM);
-    if (a != b && a < b + bytes && b < a + bytes) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "input and output overlap");
-    typename Plan<T>::DeviceGuard g(p_.device());
-    const bool inverse = !(code == ::fourier::c::FOURIER_TRANSFORM_FFT || code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT);
-    double scale = 1.0;  // in T, as Plan::exec
-    if (code == ::fourier::c::FOURIER_TRANSFORM_IFFT) scale = (double)((T)1 / (T)n_);
-    else if (code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT || code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT)
-      scale = (double)((T)1 / std::sqrt((T)n_));
+    const size_t bytes = outer * inner * n_ * ELEM;
+    check_buffers(d_in, d_out, bytes, bytes, ELEM, true);
+    if (outer == 0 || inner == 0) return;
+    DeviceGuard g(p_.device());
+    const bool inverse = !is_forward(code);
+    const double scale = code_scale<T>(code, (T)n_);
     const cpx<T>* in = (const cpx<T>*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
     switch (route(inner)) {
@@ -90,7 +85,7 @@ template <typename T> class AxisRoute {
  private:
   explicit AxisRoute(const Plan<T>& p) : p_(p), n_(p.size()) {
     cap_ = std::min(p.axis_scratch_bytes_ ? p.axis_scratch_bytes_ : AXIS_SCRATCH_BYTES, AXIS_LAUNCH_BYTES);
-    typename Plan<T>::DeviceGuard g(p.device());
+    DeviceGuard g(p.device());
     if (is_pow2(n_) && n_ >= 64 && n_ <= 2048) {
       col_ = get_kernel(Real<T>{}, (int)n_, MODE_LAST, IO_PLAIN);
       if (col_.split) col_ = KernelInfo();  // (experiments: the half-tile form of 2048 takes other arguments; transpose route then)
@@ -154,7 +149,7 @@ template <typename T> class AxisRoute {
   Chunk prepare(size_t outer, size_t inner) const {
     const size_t blk = n_ * inner * ELEM;
     Chunk c{0, 0};
-    if (blk <= cap_) c.blocks = std::min(outer, cap_ / blk);
+    if (blk <= cap_) c.blocks = chunk_rows(outer, cap_, blk);
     else c.cols = std::max<size_t>(1, cap_ / (n_ * ELEM));
     const size_t rows = c.blocks ? c.blocks * inner : c.cols;
     scratch_.ensure(rows * n_ * ELEM);
@@ -203,13 +198,6 @@ template <typename T> class AxisRoute {
           transpose(work + r0, out + o * blk + r0 * inner + c0, 1, cw, std::min(band, n_ - r0), n_, inner, 0, 0, stream);
       }
     }
-  }
-
-  // x / d = (umulhi(x, m) + x) >> l for every 32-bit x (as RealPlan::sweep)
-  static void divider(uint32_t d, uint32_t& m, uint32_t& l) {
-    l = 0;
-    while ((1ull << l) < d) ++l;
-    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
   }
 
   static constexpr unsigned AXIS_THREADS_H = 256;  // AXIS_THREADS of kernels_axis.h

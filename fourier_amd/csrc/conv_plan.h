@@ -19,12 +19,10 @@
 
 namespace fourier_hip {
 
-// Scratch bound of a ConvPlan, as RealPlan's (REAL_SCRATCH_BYTES): rows per chunk such that the scratch stays at most this many bytes,
-// never less than one row.  The experiments library and the emulator build read FOURIER_CONV_SCRATCH_BYTES at create instead (the
-// chunk-walk test).
-constexpr size_t CONV_SCRATCH_BYTES = (size_t)1 << 30;
-
-template <typename T> class ConvPlan {
+// The scratch bound of a ConvPlan is RealPlan's (REAL_SCRATCH_BYTES): rows per chunk such that the scratch stays at most this many
+// bytes, never less than one row.  The experiments library and the emulator build read FOURIER_CONV_SCRATCH_BYTES at create instead
+// (the chunk-walk test).
+template <typename T> class ConvPlan : public HandleBase {
  public:
   static constexpr size_t ELEM = sizeof(cpx<T>);
   enum Route { ONE_LAUNCH, FUSED_PASSES, COMPOSED, REAL_FUSED, REAL_COMPOSED };
@@ -40,20 +38,15 @@ template <typename T> class ConvPlan {
       plan_.reset(new Plan<T>(n, device));
       device_ = plan_->device();
       blen_ = n;
-      Guard g(device_);
+      DeviceGuard g(device_);
       fused_route_ = plan_->enable_conv_bank();
     }
-    if (const char* e = dev_env("FOURIER_CONV_SCRATCH_BYTES")) scratch_cap_ = (size_t)std::strtoull(e, nullptr, 10);
+    scratch_cap_ = scratch_bound("FOURIER_CONV_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     set_fusion(true);
   }
-  ConvPlan(const ConvPlan&) = delete;
-  ConvPlan& operator=(const ConvPlan&) = delete;
 
   size_t size() const { return n_; }
   size_t filters() const { return filters_; }
-  const char* describe() const { return desc_.c_str(); }
-  int last_status() const { return status_; }
-  void set_status(int s) const { status_ = s; }
 
   int set_option(const std::string& key, long long v) {
     if (key == "fusion" && (v == 0 || v == 1)) { set_fusion(v == 1); return ::fourier::c::FOURIER_HIP_OK; }
@@ -65,8 +58,8 @@ template <typename T> class ConvPlan {
     if (batch == 0) return 0;
     if (route_ == ONE_LAUNCH) return batch;  // no scratch, no plan buffers
     const size_t per = row_bytes();
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, scratch_cap_ / per));
-    Guard g(device_);
+    const size_t chunk = chunk_rows(batch, scratch_cap_, per);
+    DeviceGuard g(device_);
     scratch_.ensure(chunk * per);
     if (route_ == REAL_COMPOSED) rplan_->reserve(chunk);
     else if (route_ == REAL_FUSED) rplan_->inner().reserve_for(chunk, false);
@@ -81,13 +74,13 @@ template <typename T> class ConvPlan {
     if ((uintptr_t)d_taps % (real_ ? sizeof(T) : ELEM)) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "misaligned taps");
     if (taps == 0 || taps > n_ || filters == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "taps outside 1 ... N, or no filters");
     if (filters > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "more than 2^31 filters");
-    Guard g(device_);
+    DeviceGuard g(device_);
     bank_.ensure(filters * blen_ * ELEM);
     // the zero-extended taps of a chunk of filters in the scratch (a row of N values fits a scratch row on every route), the plan's
     // own forward transform in T into the bank, then 1/N and the conjugate in place
     const size_t words = real_ ? 1 : 2;
     const size_t per = real_ ? (h_ + 1) * ELEM : n_ * ELEM;  // (N reals fit N/2 + 1 complex)
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(filters, scratch_cap_ / per));
+    const size_t chunk = chunk_rows(filters, scratch_cap_, per);
     scratch_.ensure(chunk * per);
     if (real_) rplan_->reserve(chunk);  // (RealPlan's own scratch: rows of the filter transforms, kept)
     else plan_->reserve_for(chunk, false);
@@ -98,29 +91,25 @@ template <typename T> class ConvPlan {
       a.in = (const T*)d_taps + f0 * taps * words;
       a.out = scratch_.p;
       a.n = n_ * words; a.taps = taps * words; a.rows = nf;
-      FOURIER_LAUNCH(get_conv_sweep_kernel(Real<T>{}, CONV_PAD), small_grid(nf * n_ * words), 256, 0, stream, a);
+      FOURIER_LAUNCH(get_conv_sweep_kernel(Real<T>{}, CONV_PAD), elementwise_grid(nf * n_ * words), 256, 0, stream, a);
       if (real_) rplan_->run_forward(scratch_.p, bank + f0 * blen_, nf, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
       else plan_->exec(scratch_.p, bank + f0 * blen_, nf, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
     }
     ConvArgs a{};
     a.out = bank;
     a.count = filters * blen_;
-    a.scale = (double)((T)1 / (T)n_);  // in T, as Plan::exec
+    a.scale = code_scale<T>(::fourier::c::FOURIER_TRANSFORM_IFFT, (T)n_);  // the inverse's 1/N, folded into the bank
     a.conj = correlate;
-    FOURIER_LAUNCH(get_conv_sweep_kernel(Real<T>{}, CONV_FINISH), small_grid(a.count), 256, 0, stream, a);
+    FOURIER_LAUNCH(get_conv_sweep_kernel(Real<T>{}, CONV_FINISH), elementwise_grid(a.count), 256, 0, stream, a);
     filters_ = filters;
   }
 
   void apply(const void* d_in, void* d_out, size_t batch, hipStream_t stream) const {
-    if (!d_in || !d_out) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "null buffer");
-    if ((uintptr_t)d_in % ELEM || (uintptr_t)d_out % ELEM) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "misaligned buffer");
-    const uintptr_t p = (uintptr_t)d_in, q = (uintptr_t)d_out;
     const size_t row = n_ * (real_ ? sizeof(T) : ELEM);
-    if (p != q && batch && p < q + batch * row && q < p + batch * row)
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "input and output overlap");
+    check_buffers(d_in, d_out, batch * row, batch * row, ELEM, true);
     if (filters_ == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "no filters set");
     if (batch == 0) return;
-    Guard g(device_);
+    DeviceGuard g(device_);
     const size_t chunk = prepare(batch);
     const char* in = (const char*)d_in;
     char* out = (char*)d_out;
@@ -158,24 +147,6 @@ template <typename T> class ConvPlan {
   }
 
  private:
-  struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-      if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-      if (prev != dev) (void)hipSetDevice(dev);
-      else prev = -1;
-    }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  };
-  static unsigned small_grid(size_t elems) {
-    return (unsigned)std::min<size_t>(std::max<size_t>((elems + 255) / 256, 1), 256 * 32);
-  }
-  static void divider(uint32_t d, uint32_t& m, uint32_t& l) {  // x / d = (umulhi(x, m) + x) >> l for every 32-bit x
-    l = 0;
-    while ((1ull << l) < d) ++l;
-    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
-  }
-
   void set_fusion(bool on) {
     if (real_) route_ = (on && rplan_->even()) ? REAL_FUSED : REAL_COMPOSED;
     else route_ = !on ? COMPOSED : fused_route_ == Plan<T>::CONV_ONE_LAUNCH ? ONE_LAUNCH : fused_route_ == Plan<T>::CONV_PASSES ? FUSED_PASSES : COMPOSED;
@@ -225,17 +196,7 @@ template <typename T> class ConvPlan {
   size_t filters_ = 0;
   DevBuf bank_;
   mutable DevBuf scratch_;
-  size_t scratch_cap_ = CONV_SCRATCH_BYTES;
-  mutable int status_ = 0;
-  std::string desc_;
+  size_t scratch_cap_ = REAL_SCRATCH_BYTES;
 };
-
-template <typename T> static ConvPlan<T>* create_conv_plan(size_t n, bool real_data, int device) {
-  try {
-    return new ConvPlan<T>(n, real_data, device);
-  } catch (...) {
-    return nullptr;
-  }
-}
 
 }  // namespace fourier_hip

@@ -22,24 +22,33 @@
 using namespace fourier_hip;
 namespace fc = ::fourier::c;
 
+// what every handle family's entry points do in the same way; H = the handle class behind the opaque pointer
+template <typename H> static void destroy_handle(void* h) {
+  try { delete (H*)h; } catch (...) {}
+}
+template <typename H> static const char* describe_handle(const void* h) { return h ? ((const H*)h)->describe() : ""; }
+template <typename H> static int last_status_of(const void* h) { return h ? ((const H*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT; }
+template <typename H> static int set_handle_option(void* h, const char* key, long long v) {
+  if (!h || !key) return fc::FOURIER_HIP_INVALID_ARGUMENT;
+  try { return ((H*)h)->set_option(key, v); } catch (...) { return fc::FOURIER_HIP_INVALID_ARGUMENT; }
+}
+
 #define FOURIER_DEFINE_ABI(T, SUFFIX)                                                                            \
   extern "C" fc::fourier_fft_##SUFFIX* fourier_create_##SUFFIX(size_t size) {                                    \
-    return (fc::fourier_fft_##SUFFIX*)create_plan<T>(size, -1);                                                  \
+    return (fc::fourier_fft_##SUFFIX*)create_handle<Plan<T>>(size, -1);                                          \
   }                                                                                                              \
   extern "C" fc::fourier_fft_##SUFFIX* fourier_hip_create_##SUFFIX(size_t size, int device) {                    \
-    return (fc::fourier_fft_##SUFFIX*)create_plan<T>(size, device);                                              \
+    return (fc::fourier_fft_##SUFFIX*)create_handle<Plan<T>>(size, device);                                      \
   }                                                                                                              \
-  extern "C" void fourier_destroy_##SUFFIX(fc::fourier_fft_##SUFFIX* h) {                                        \
-    try { delete (Plan<T>*)h; } catch (...) {}                                                                   \
-  }                                                                                                              \
+  extern "C" void fourier_destroy_##SUFFIX(fc::fourier_fft_##SUFFIX* h) { destroy_handle<Plan<T>>(h); }          \
   extern "C" void fourier_transform_in_place_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, std::complex<T>* x, int code) { \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    (void)guarded<T>(p, [&] { p->exec_host(x, x, code); });                                                      \
+    (void)guarded_handle(p, [&] { p->exec_host(x, x, code); });                                                  \
   }                                                                                                              \
   extern "C" void fourier_transform_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const std::complex<T>* in,       \
                                              std::complex<T>* out, int code) {                                   \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    (void)guarded<T>(p, [&] { p->exec_host(in, out, code); });                                                   \
+    (void)guarded_handle(p, [&] { p->exec_host(in, out, code); });                                               \
   }                                                                                                              \
   extern "C" size_t fourier_hip_size_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) {                               \
     return h ? ((const Plan<T>*)h)->size() : 0;                                                                  \
@@ -47,30 +56,30 @@ namespace fc = ::fourier::c;
   extern "C" int fourier_hip_transform_batch_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const void* d_in,       \
                                                       void* d_out, size_t batch, int code, void* stream) {       \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { p->exec(d_in, d_out, batch, code, (hipStream_t)stream); });                       \
+    return guarded_handle(p, [&] { p->exec(d_in, d_out, batch, code, (hipStream_t)stream); });                   \
   }                                                                                                              \
   extern "C" int fourier_hip_reserve_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, size_t batch, int in_place) {   \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { p->reserve_for(batch, in_place != 0); });                                         \
+    return guarded_handle(p, [&] { p->reserve_for(batch, in_place != 0); });                                     \
   }                                                                                                              \
   extern "C" int fourier_hip_device_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) {                                \
     return h ? ((const Plan<T>*)h)->device() : -1;                                                               \
   }                                                                                                              \
   extern "C" int fourier_hip_synchronize_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, void* stream) {            \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { p->synchronize((hipStream_t)stream); });                                          \
+    return guarded_handle(p, [&] { p->synchronize((hipStream_t)stream); });                                      \
   }                                                                                                              \
   extern "C" int fourier_hip_transform_batch_host_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const std::complex<T>* in, \
                                                            std::complex<T>* out, size_t batch, int code) {      \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { p->exec_host_batch(in, out, batch, code); });                                     \
+    return guarded_handle(p, [&] { p->exec_host_batch(in, out, batch, code); });                                 \
   }                                                                                                              \
   extern "C" int fourier_hip_profile_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const void* d_in, void* d_out,  \
                                               size_t batch, int code, void* stream, int nslots, float* ms_sum,   \
                                               int* launches) {                                                   \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
     if (!ms_sum || !launches || nslots <= 0) return fc::FOURIER_HIP_INVALID_ARGUMENT;                            \
-    return guarded<T>(p, [&] {                                                                                   \
+    return guarded_handle(p, [&] {                                                                               \
       Profiler prof((hipStream_t)stream);                                                                        \
       p->exec(d_in, d_out, batch, code, (hipStream_t)stream, &prof);                                             \
       prof.collect(nslots, ms_sum, launches);                                                                    \
@@ -81,16 +90,11 @@ namespace fc = ::fourier::c;
     s = h ? ((const Plan<T>*)h)->slot_names() : "";                                                              \
     return s.c_str();                                                                                            \
   }                                                                                                              \
-  extern "C" int fourier_hip_last_status_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) {                           \
-    return h ? ((const Plan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                            \
-  }                                                                                                              \
+  extern "C" int fourier_hip_last_status_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) { return last_status_of<Plan<T>>(h); } \
   extern "C" int fourier_hip_set_option_##SUFFIX(fc::fourier_fft_##SUFFIX* h, const char* key, long long v) {    \
-    if (!h || !key) return fc::FOURIER_HIP_INVALID_ARGUMENT;                                                     \
-    try { return ((Plan<T>*)h)->set_option(key, v); } catch (...) { return fc::FOURIER_HIP_INVALID_ARGUMENT; }   \
+    return set_handle_option<Plan<T>>(h, key, v);                                                                \
   }                                                                                                              \
-  extern "C" const char* fourier_hip_describe_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) {                      \
-    return h ? ((const Plan<T>*)h)->describe() : "";                                                             \
-  }                                                                                                              \
+  extern "C" const char* fourier_hip_describe_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) { return describe_handle<Plan<T>>(h); } \
   extern "C" double fourier_hip_model_bytes_##SUFFIX(const fc::fourier_fft_##SUFFIX* h) {                        \
     return h ? ((const Plan<T>*)h)->model_bytes() : 0.0;                                                         \
   }
@@ -98,51 +102,16 @@ namespace fc = ::fourier::c;
 FOURIER_DEFINE_ABI(float, float)
 FOURIER_DEFINE_ABI(double, double)
 
-// real-input transforms (include/fourier.h, fourier_hip_real_*): the same error model as the complex handle
-#define FOURIER_DEFINE_REAL_ABI(T, SUFFIX)                                                                       \
-  extern "C" fc::fourier_real_fft_##SUFFIX* fourier_hip_real_create_##SUFFIX(size_t size, int device) {          \
-    return (fc::fourier_real_fft_##SUFFIX*)create_real_plan<T>(size, device);                                    \
-  }                                                                                                              \
-  extern "C" void fourier_hip_real_destroy_##SUFFIX(fc::fourier_real_fft_##SUFFIX* h) {                          \
-    try { delete (RealPlan<T>*)h; } catch (...) {}                                                               \
-  }                                                                                                              \
-  extern "C" size_t fourier_hip_real_size_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {                     \
-    return h ? ((const RealPlan<T>*)h)->size() : 0;                                                              \
-  }                                                                                                              \
-  extern "C" int fourier_hip_real_forward_batch_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, const void* d_in, \
-                                                         void* d_out, size_t batch, int code, void* stream) {    \
-    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
-    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, code, (hipStream_t)stream); });                \
-  }                                                                                                              \
-  extern "C" int fourier_hip_real_inverse_batch_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, const void* d_in, \
-                                                         void* d_out, size_t batch, int code, void* stream) {    \
-    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
-    return guarded_handle(p, [&] { p->inverse(d_in, d_out, batch, code, (hipStream_t)stream); });                \
-  }                                                                                                              \
-  extern "C" int fourier_hip_real_reserve_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h, size_t batch) {       \
-    const RealPlan<T>* p = (const RealPlan<T>*)h;                                                                \
-    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
-  }                                                                                                              \
-  extern "C" const char* fourier_hip_real_describe_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {            \
-    return h ? ((const RealPlan<T>*)h)->describe() : "";                                                         \
-  }                                                                                                              \
-  extern "C" int fourier_hip_real_last_status_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {                 \
-    return h ? ((const RealPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                        \
-  }
-
-FOURIER_DEFINE_REAL_ABI(float, float)
-FOURIER_DEFINE_REAL_ABI(double, double)
-
 // transforms along a strided axis (include/fourier.h, fourier_hip_transform_axis_*): methods of the complex handle, its error model
 #define FOURIER_DEFINE_AXIS_ABI(T, SUFFIX)                                                                       \
   extern "C" int fourier_hip_transform_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, const void* d_in, void* d_out, \
                                                      size_t outer, size_t inner, int code, void* stream) {      \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { AxisRoute<T>::of(*p).transform(d_in, d_out, outer, inner, code, (hipStream_t)stream); }); \
+    return guarded_handle(p, [&] { AxisRoute<T>::of(*p).transform(d_in, d_out, outer, inner, code, (hipStream_t)stream); }); \
   }                                                                                                              \
   extern "C" int fourier_hip_reserve_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, size_t outer, size_t inner) { \
     const Plan<T>* p = (const Plan<T>*)h;                                                                        \
-    return guarded<T>(p, [&] { AxisRoute<T>::of(*p).reserve(outer, inner); });                                   \
+    return guarded_handle(p, [&] { AxisRoute<T>::of(*p).reserve(outer, inner); });                               \
   }                                                                                                              \
   extern "C" const char* fourier_hip_describe_axis_##SUFFIX(const fc::fourier_fft_##SUFFIX* h, size_t inner) {   \
     static thread_local std::string s;                                                                           \
@@ -156,48 +125,61 @@ FOURIER_DEFINE_REAL_ABI(double, double)
 FOURIER_DEFINE_AXIS_ABI(float, float)
 FOURIER_DEFINE_AXIS_ABI(double, double)
 
-// real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*): the same error model as the real handle
-#define FOURIER_DEFINE_REALND_ABI(T, SUFFIX)                                                                     \
-  extern "C" fc::fourier_realnd_fft_##SUFFIX* fourier_hip_realnd_create_##SUFFIX(int rank, const size_t* shape, int device) { \
-    return (fc::fourier_realnd_fft_##SUFFIX*)create_realnd_plan<T>(rank, shape, device);                         \
+// The handle families built on the complex plan (include/fourier.h): the same error model.  fourier_hip_<STEM>_destroy / reserve /
+// describe / last_status _<SUFFIX> on the opaque type fc::CTYPE behind which the class H stands ...
+#define FOURIER_DEFINE_HANDLE_ABI(STEM, CTYPE, H, SUFFIX)                                                        \
+  extern "C" void fourier_hip_##STEM##_destroy_##SUFFIX(fc::CTYPE* h) { destroy_handle<H>(h); }                  \
+  extern "C" int fourier_hip_##STEM##_reserve_##SUFFIX(const fc::CTYPE* h, size_t batch) {                       \
+    const H* p = (const H*)h;                                                                                    \
+    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
   }                                                                                                              \
-  extern "C" void fourier_hip_realnd_destroy_##SUFFIX(fc::fourier_realnd_fft_##SUFFIX* h) {                      \
-    try { delete (RealNdPlan<T>*)h; } catch (...) {}                                                             \
+  extern "C" const char* fourier_hip_##STEM##_describe_##SUFFIX(const fc::CTYPE* h) { return describe_handle<H>(h); } \
+  extern "C" int fourier_hip_##STEM##_last_status_##SUFFIX(const fc::CTYPE* h) { return last_status_of<H>(h); }
+// ... and forward_batch / inverse_batch of the two real-input families
+#define FOURIER_DEFINE_R2C_ABI(STEM, CTYPE, H, SUFFIX)                                                           \
+  FOURIER_DEFINE_HANDLE_ABI(STEM, CTYPE, H, SUFFIX)                                                              \
+  extern "C" int fourier_hip_##STEM##_forward_batch_##SUFFIX(const fc::CTYPE* h, const void* d_in, void* d_out, size_t batch, \
+                                                             int code, void* stream) {                           \
+    const H* p = (const H*)h;                                                                                    \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_##STEM##_inverse_batch_##SUFFIX(const fc::CTYPE* h, const void* d_in, void* d_out, size_t batch, \
+                                                             int code, void* stream) {                           \
+    const H* p = (const H*)h;                                                                                    \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, batch, code, (hipStream_t)stream); });                \
+  }
+
+// real-input transforms (fourier_hip_real_*)
+#define FOURIER_DEFINE_REAL_ABI(T, SUFFIX)                                                                       \
+  FOURIER_DEFINE_R2C_ABI(real, fourier_real_fft_##SUFFIX, RealPlan<T>, SUFFIX)                                   \
+  extern "C" fc::fourier_real_fft_##SUFFIX* fourier_hip_real_create_##SUFFIX(size_t size, int device) {          \
+    return (fc::fourier_real_fft_##SUFFIX*)create_handle<RealPlan<T>>(size, device);                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_real_size_##SUFFIX(const fc::fourier_real_fft_##SUFFIX* h) {                     \
+    return h ? ((const RealPlan<T>*)h)->size() : 0;                                                              \
+  }
+
+FOURIER_DEFINE_REAL_ABI(float, float)
+FOURIER_DEFINE_REAL_ABI(double, double)
+
+// real-input N-D transforms (fourier_hip_realnd_*)
+#define FOURIER_DEFINE_REALND_ABI(T, SUFFIX)                                                                     \
+  FOURIER_DEFINE_R2C_ABI(realnd, fourier_realnd_fft_##SUFFIX, RealNdPlan<T>, SUFFIX)                             \
+  extern "C" fc::fourier_realnd_fft_##SUFFIX* fourier_hip_realnd_create_##SUFFIX(int rank, const size_t* shape, int device) { \
+    return (fc::fourier_realnd_fft_##SUFFIX*)create_handle<RealNdPlan<T>>(rank, shape, device);                  \
   }                                                                                                              \
   extern "C" int fourier_hip_realnd_rank_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {                    \
     return h ? ((const RealNdPlan<T>*)h)->rank() : 0;                                                            \
-  }                                                                                                              \
-  extern "C" int fourier_hip_realnd_forward_batch_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, const void* d_in, \
-                                                           void* d_out, size_t batch, int code, void* stream) {  \
-    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
-    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, code, (hipStream_t)stream); });                \
-  }                                                                                                              \
-  extern "C" int fourier_hip_realnd_inverse_batch_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, const void* d_in, \
-                                                           void* d_out, size_t batch, int code, void* stream) {  \
-    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
-    return guarded_handle(p, [&] { p->inverse(d_in, d_out, batch, code, (hipStream_t)stream); });                \
-  }                                                                                                              \
-  extern "C" int fourier_hip_realnd_reserve_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h, size_t batch) {   \
-    const RealNdPlan<T>* p = (const RealNdPlan<T>*)h;                                                            \
-    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
-  }                                                                                                              \
-  extern "C" const char* fourier_hip_realnd_describe_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {        \
-    return h ? ((const RealNdPlan<T>*)h)->describe() : "";                                                       \
-  }                                                                                                              \
-  extern "C" int fourier_hip_realnd_last_status_##SUFFIX(const fc::fourier_realnd_fft_##SUFFIX* h) {             \
-    return h ? ((const RealNdPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                      \
   }
 
 FOURIER_DEFINE_REALND_ABI(float, float)
 FOURIER_DEFINE_REALND_ABI(double, double)
 
-// convolution with a prepared filter bank (include/fourier.h, fourier_hip_conv_*): the same error model as the real handle
+// convolution with a prepared filter bank (fourier_hip_conv_*)
 #define FOURIER_DEFINE_CONV_ABI(T, SUFFIX)                                                                       \
+  FOURIER_DEFINE_HANDLE_ABI(conv, fourier_conv_##SUFFIX, ConvPlan<T>, SUFFIX)                                    \
   extern "C" fc::fourier_conv_##SUFFIX* fourier_hip_conv_create_##SUFFIX(size_t size, int real_data, int device) { \
-    return (fc::fourier_conv_##SUFFIX*)create_conv_plan<T>(size, real_data != 0, device);                        \
-  }                                                                                                              \
-  extern "C" void fourier_hip_conv_destroy_##SUFFIX(fc::fourier_conv_##SUFFIX* h) {                              \
-    try { delete (ConvPlan<T>*)h; } catch (...) {}                                                               \
+    return (fc::fourier_conv_##SUFFIX*)create_handle<ConvPlan<T>>(size, real_data != 0, device);                 \
   }                                                                                                              \
   extern "C" size_t fourier_hip_conv_size_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                         \
     return h ? ((const ConvPlan<T>*)h)->size() : 0;                                                              \
@@ -215,19 +197,8 @@ FOURIER_DEFINE_REALND_ABI(double, double)
     const ConvPlan<T>* p = (const ConvPlan<T>*)h;                                                                \
     return guarded_handle(p, [&] { p->apply(d_in, d_out, batch, (hipStream_t)stream); });                        \
   }                                                                                                              \
-  extern "C" int fourier_hip_conv_reserve_##SUFFIX(const fc::fourier_conv_##SUFFIX* h, size_t batch) {           \
-    const ConvPlan<T>* p = (const ConvPlan<T>*)h;                                                                \
-    return guarded_handle(p, [&] { p->reserve(batch); });                                                        \
-  }                                                                                                              \
   extern "C" int fourier_hip_conv_set_option_##SUFFIX(fc::fourier_conv_##SUFFIX* h, const char* key, long long v) { \
-    if (!h || !key) return fc::FOURIER_HIP_INVALID_ARGUMENT;                                                     \
-    try { return ((ConvPlan<T>*)h)->set_option(key, v); } catch (...) { return fc::FOURIER_HIP_INVALID_ARGUMENT; } \
-  }                                                                                                              \
-  extern "C" const char* fourier_hip_conv_describe_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                \
-    return h ? ((const ConvPlan<T>*)h)->describe() : "";                                                         \
-  }                                                                                                              \
-  extern "C" int fourier_hip_conv_last_status_##SUFFIX(const fc::fourier_conv_##SUFFIX* h) {                     \
-    return h ? ((const ConvPlan<T>*)h)->last_status() : fc::FOURIER_HIP_INVALID_ARGUMENT;                        \
+    return set_handle_option<ConvPlan<T>>(h, key, v);                                                            \
   }
 
 FOURIER_DEFINE_CONV_ABI(float, float)

@@ -5,6 +5,7 @@
 #include "engine_mixed.h"
 #include "engine_generic.h"
 #include "engine_tiled.h"
+#include "handle_common.h"
 
 namespace fourier_hip {
 
@@ -71,7 +72,7 @@ static inline void host_fft_any(std::vector<double>& re, std::vector<double>& im
 template <typename T> class AxisRoute;  // transforms along a strided axis (axis_plan.h), built on first use
 
 // ---------------------------------------------------------------------------------------------
-template <typename T> class Plan {
+template <typename T> class Plan : public HandleBase {
   friend class AxisRoute<T>;
 
  public:
@@ -87,7 +88,7 @@ template <typename T> class Plan {
     device_ = device;
     DeviceGuard g(device_);
     // the axis transforms' development switches (experiments library and emulator build only; axis_plan.h)
-    if (const char* e = dev_env("FOURIER_AXIS_SCRATCH_BYTES")) axis_scratch_bytes_ = (size_t)std::strtoull(e, nullptr, 10);
+    axis_scratch_bytes_ = scratch_bound("FOURIER_AXIS_SCRATCH_BYTES", 0);
     if (const char* e = dev_env("FOURIER_AXIS_ROUTE")) axis_force_transpose_ = std::string(e) == "transpose";
     if (is_pow2(n)) {
       eng_.reset(new Pow2Engine<T>(n, false, true));
@@ -207,14 +208,9 @@ template <typename T> class Plan {
       (void)hipStreamDestroy(legacy_stream_);
     }
   }
-  Plan(const Plan&) = delete;
-  Plan& operator=(const Plan&) = delete;
 
   size_t size() const { return n_; }
   int device() const { return device_; }
-  const char* describe() const { return desc_.c_str(); }
-  int last_status() const { return status_; }
-  void set_status(int s) const { status_ = s; }
 
   // kernel "slots" in launch order, as reported by profile(): names for bench.py / rocprof matching
   std::string slot_names() const {
@@ -401,7 +397,7 @@ template <typename T> class Plan {
     if (mix_ || regf_ || batch == 0) return batch;
     if (tiled_) {  // one scratch of a chunk for in-place calls and three-pass plans
       size_t chunk = batch;
-      if (chunk_bytes_) chunk = std::max<size_t>(1, std::min<size_t>(batch, chunk_bytes_ / (n_ * ELEM)));
+      if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, n_ * ELEM);
       while (chunk > 1 && (double)chunk * (double)n_ / 8.0 > 2.0e9) chunk = (chunk + 1) / 2;
       if (!(tiled_->needs_scratch(in_place) || force_scratch_)) return chunk;
       for (;;) {
@@ -415,7 +411,7 @@ template <typename T> class Plan {
     }
     if (gen_) {  // two scratch halves of one chunk each; chunked so that a launch stays below 2^31 workgroups
       size_t chunk = batch;
-      if (chunk_bytes_) chunk = std::max<size_t>(1, std::min<size_t>(batch, chunk_bytes_ / (n_ * ELEM)));
+      if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, n_ * ELEM);
       while (chunk > 1 && (double)chunk * (double)n_ / 256.0 > 2.0e9) chunk = (chunk + 1) / 2;
       for (;;) {
         try { scratch_.ensure(2 * chunk * n_ * ELEM); return chunk; }
@@ -428,7 +424,7 @@ template <typename T> class Plan {
     }
     const size_t per = (blu_ ? m_ : n_) * ELEM;
     size_t chunk = batch;
-    if (chunk_bytes_) chunk = std::max<size_t>(1, std::min<size_t>(batch, chunk_bytes_ / per));
+    if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, per);
     // keep every launch's grid below 2^31 blocks
     while (chunk > 1 && (double)chunk * (double)(blu_ ? m_ : n_) / 16.0 > 2.0e9) chunk = (chunk + 1) / 2;
     // The plan's scratch (and the Bluestein work array) hold one chunk.  If the device cannot give that much -- an
@@ -469,12 +465,8 @@ template <typename T> class Plan {
     if (code < 0 || code > 4) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "unknown transform code");
     if (batch == 0) return;
     DeviceGuard g(device_);
-    // fft.rs:20-25 is_forward; autosort/mod.rs:381-385 scale computed in T
-    const bool inverse = !(code == ::fourier::c::FOURIER_TRANSFORM_FFT || code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT);
-    double scale = 1.0;
-    if (code == ::fourier::c::FOURIER_TRANSFORM_IFFT) scale = (double)((T)1 / (T)n_);
-    else if (code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT || code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT)
-      scale = (double)((T)1 / std::sqrt((T)n_));
+    const bool inverse = !is_forward(code);
+    const double scale = code_scale<T>(code, (T)n_);
     const cpx<T>* in = (const cpx<T>*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
     const bool in_place = (d_in == d_out);
@@ -696,7 +688,7 @@ template <typename T> class Plan {
     if (batch == 0) return;
     DeviceGuard g(device_);
     const size_t per = n_ * ELEM;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, host_chunk_bytes_ / per));
+    const size_t chunk = chunk_rows(batch, host_chunk_bytes_, per);
     const size_t nchunks = (batch + chunk - 1) / chunk;
     pipe_.ensure(chunk * per);
     const char* src = (const char*)h_in;
@@ -729,20 +721,6 @@ template <typename T> class Plan {
   static constexpr size_t NSLOTS = 4;  // chunks in flight: copy-in, H2D, kernels, D2H + copy-out each take about one chunk time
 
  private:
-  struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-      if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-      if (prev != dev) (void)hipSetDevice(dev);
-      else prev = -1;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  };
-  static unsigned elementwise_grid(size_t elems) {
-    const size_t blocks = (elems + 255) / 256;
-    return (unsigned)std::min<size_t>(std::max<size_t>(blocks, 1), 256 * 32);
-  }
-
   // option "bluestein_smooth_m" (and "bluestein_fusion" = 0 on the register route): the Bluestein route chosen again under another rule
   void rebuild_bluestein(int mode) {
     HIP_CHECK(hipDeviceSynchronize());
@@ -961,40 +939,9 @@ template <typename T> class Plan {
   bool conv_ = false, conv_ok_ = false;  // Bluestein: forward LAST + (.)w + inverse FIRST in one launch
   int conv_route_ = 0;  // enable_conv_bank: the convolution handle's route on this plan (CONV_NONE ...)
   unsigned nxcd_ = 8, nxcd_last_ = 0;
-  mutable int status_ = 0;
-  std::string desc_;
   mutable std::shared_ptr<AxisRoute<T>> axis_;  // (shared_ptr: AxisRoute<T> is incomplete here)
   size_t axis_scratch_bytes_ = 0;               // 0: AXIS_SCRATCH_BYTES
   bool axis_force_transpose_ = false;
 };
-
-template <typename T> static Plan<T>* create_plan(size_t n, int device) {
-  try {
-    return new Plan<T>(n, device);
-  } catch (...) {
-    return nullptr;  // never unwind into C (fourier-ffi/src/lib.rs:18-19)
-  }
-}
-
-// the error model of every handle (Plan, RealPlan): status of the last call, nothing unwinds into C
-template <typename H, typename F> static int guarded_handle(const H* p, F&& f) {
-  if (!p) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
-  p->set_status(::fourier::c::FOURIER_HIP_OK);  // last_status = status of the LAST call on this handle
-  try {
-    f();
-    return ::fourier::c::FOURIER_HIP_OK;
-  } catch (const EngineError& e) {
-    p->set_status(e.status);
-    if (getenv("FOURIER_HIP_VERBOSE")) fprintf(stderr, "libfourier: %s\n", e.what());
-    return e.status;
-  } catch (const std::bad_alloc&) {
-    p->set_status(::fourier::c::FOURIER_HIP_OUT_OF_MEMORY);
-    return ::fourier::c::FOURIER_HIP_OUT_OF_MEMORY;
-  } catch (...) {
-    p->set_status(::fourier::c::FOURIER_HIP_RUNTIME_ERROR);
-    return ::fourier::c::FOURIER_HIP_RUNTIME_ERROR;
-  }
-}
-template <typename T, typename F> static int guarded(const Plan<T>* p, F&& f) { return guarded_handle(p, std::forward<F>(f)); }
 
 }  // namespace fourier_hip

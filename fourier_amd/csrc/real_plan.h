@@ -22,7 +22,7 @@ constexpr size_t REAL_SCRATCH_BYTES = (size_t)1 << 30;
 // default scratch bound; a row may take at most half of it, RealPlan's constructor)
 constexpr size_t REAL_LAUNCH_BYTES = ((size_t)1 << 31) - 1;
 
-template <typename T> class RealPlan {
+template <typename T> class RealPlan : public HandleBase {
  public:
   static constexpr size_t ELEM = sizeof(cpx<T>);
 
@@ -30,22 +30,13 @@ template <typename T> class RealPlan {
     if (n == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "size 0 is invalid");
     if ((h_ + 1) * ELEM > REAL_LAUNCH_BYTES / 2) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "real transforms above 2^30 bytes of half spectrum");
     inner_.reset(new Plan<T>(even_ ? h_ : n_, device));
-    Guard g(inner_->device());
-    if (even_) {  // W_N^j, j <= N/4: f64 trigonometry, cast (twiddle.rs:7-19)
-      std::vector<cpx<T>> tw(h_ / 2 + 1);
-      for (size_t j = 0; j < tw.size(); ++j) { double re, im; unit_root(j, n_, re, im); tw[j] = {(T)re, (T)im}; }
-      tw_.upload(tw);
-    }
-    if (const char* e = dev_env("FOURIER_REAL_SCRATCH_BYTES")) scratch_cap_ = (size_t)std::strtoull(e, nullptr, 10);
+    DeviceGuard g(inner_->device());
+    if (even_) tw_.upload(real_untangle_twiddles<T>(n_));
+    scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     desc_ = std::string(even_ ? "real half-length: " : "real full-length: ") + inner_->describe();
   }
-  RealPlan(const RealPlan&) = delete;
-  RealPlan& operator=(const RealPlan&) = delete;
 
   size_t size() const { return n_; }
-  const char* describe() const { return desc_.c_str(); }
-  int last_status() const { return status_; }
-  void set_status(int s) const { status_ = s; }
   // the pieces the convolution handle's fused untangle route runs by itself (conv_plan.h): the inner plan, W_N^j (even N)
   bool even() const { return even_; }
   const Plan<T>& inner() const { return *inner_; }
@@ -56,8 +47,8 @@ template <typename T> class RealPlan {
   size_t prepare(size_t batch) const {
     if (batch == 0) return 0;
     const size_t per = (even_ ? h_ : n_) * ELEM;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, scratch_cap_ / per));
-    Guard g(inner_->device());
+    const size_t chunk = chunk_rows(batch, scratch_cap_, per);
+    DeviceGuard g(inner_->device());
     scratch_.ensure(chunk * per);
     inner_->reserve_for(chunk, !even_);
     return chunk;
@@ -65,17 +56,16 @@ template <typename T> class RealPlan {
   void reserve(size_t batch) const { (void)prepare(batch); }
 
   void forward(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
-    check(d_in, d_out, batch, n_ * sizeof(T), (h_ + 1) * ELEM);
-    if (code != ::fourier::c::FOURIER_TRANSFORM_FFT && code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT)
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not a forward transform code");
+    check_buffers(d_in, d_out, batch * n_ * sizeof(T), batch * (h_ + 1) * ELEM, ELEM, false);
+    if (!is_forward(code)) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not a forward transform code");
     run_forward(d_in, d_out, batch, code, stream);
   }
   // forward / inverse after the argument checks (RealNdPlan's composed route runs rows of odd N whose reals start on any T)
   void run_forward(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
     if (batch == 0) return;
-    Guard g(inner_->device());
+    DeviceGuard g(inner_->device());
     const size_t chunk = prepare(batch);
-    const double scale = code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT ? (double)((T)1 / std::sqrt((T)n_)) : 1.0;  // in T, as Plan::exec
+    const double scale = code_scale<T>(code, (T)n_);
     const T* in = (const T*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
@@ -93,20 +83,17 @@ template <typename T> class RealPlan {
   }
 
   void inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
-    check(d_in, d_out, batch, (h_ + 1) * ELEM, n_ * sizeof(T));
-    if (code != ::fourier::c::FOURIER_TRANSFORM_IFFT && code != ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT &&
-        code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT)
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not an inverse transform code");
+    check_buffers(d_in, d_out, batch * (h_ + 1) * ELEM, batch * n_ * sizeof(T), ELEM, false);
+    if (!is_inverse(code)) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not an inverse transform code");
     run_inverse(d_in, d_out, batch, code, stream);
   }
   void run_inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
     if (batch == 0) return;
-    Guard g(inner_->device());
+    DeviceGuard g(inner_->device());
     const size_t chunk = prepare(batch);
     // the code's scale over N: the inner h-point IFFT runs unscaled and returns h (x[2m] + i x[2m+1]) times what the sweep wrote,
     // and the sweep's S +- iT carry a factor 2
-    const double fac = code == ::fourier::c::FOURIER_TRANSFORM_IFFT ? (double)((T)1 / (T)n_)
-                       : code == ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT ? (double)((T)1 / std::sqrt((T)n_)) : 1.0;
+    const double fac = code_scale<T>(code, (T)n_);
     const cpx<T>* in = (const cpx<T>*)d_in;
     T* out = (T*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
@@ -124,33 +111,11 @@ template <typename T> class RealPlan {
   }
 
  private:
-  struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-      if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-      if (prev != dev) (void)hipSetDevice(dev);
-      else prev = -1;
-    }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  };
-
-  // out of place only, no overlap, both pointers aligned to one complex element
-  static void check(const void* d_in, void* d_out, size_t batch, size_t in_row, size_t out_row) {
-    if (!d_in || !d_out) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "null buffer");
-    if ((uintptr_t)d_in % ELEM || (uintptr_t)d_out % ELEM) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "misaligned buffer");
-    const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
-    if (a == b || (batch && a < b + batch * out_row && b < a + batch * in_row))
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "input and output overlap");
-  }
-
   // the untangle sweep over nb rows, in launches of at most REAL_LAUNCH_BYTES per side
   void sweep(int which, const cpx<T>* in, cpx<T>* out, size_t nb, double scale, hipStream_t stream) const {
     const size_t zrow = h_ * ELEM, xrow = (h_ + 1) * ELEM;
     const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / xrow);
     const uint32_t pairs = (uint32_t)(h_ / 2 + 1);
-    uint32_t l = 0;
-    while ((1ull << l) < pairs) ++l;
-    const uint32_t m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - pairs)) / pairs + 1);
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
       RealArgs a{};
@@ -161,8 +126,7 @@ template <typename T> class RealPlan {
       a.h = (uint32_t)h_;
       a.pairs = pairs;
       a.total = (uint32_t)(rows * pairs);
-      a.div_m = m;
-      a.div_l = l;
+      divider(pairs, a.div_m, a.div_l);
       a.in_bytes = (uint32_t)(rows * (post ? zrow : xrow));
       a.out_bytes = (uint32_t)(rows * (post ? xrow : zrow));
       a.scale = scale;
@@ -175,8 +139,7 @@ template <typename T> class RealPlan {
     a.out = out;
     a.n = n_;
     a.rows = nb;
-    const size_t blocks = (nb * n_ + 255) / 256;
-    FOURIER_LAUNCH(get_real_kernel(Real<T>{}, which), std::min<size_t>(blocks, 256 * 32), 256, 0, stream, a);
+    FOURIER_LAUNCH(get_real_kernel(Real<T>{}, which), elementwise_grid(nb * n_), 256, 0, stream, a);
   }
 
   size_t n_, h_;
@@ -185,16 +148,6 @@ template <typename T> class RealPlan {
   DevBuf tw_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
-  mutable int status_ = 0;
-  std::string desc_;
 };
-
-template <typename T> static RealPlan<T>* create_real_plan(size_t n, int device) {
-  try {
-    return new RealPlan<T>(n, device);
-  } catch (...) {
-    return nullptr;
-  }
-}
 
 }  // namespace fourier_hip

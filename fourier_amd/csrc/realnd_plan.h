@@ -18,12 +18,11 @@
 
 namespace fourier_hip {
 
-// Scratch bound, as REAL_SCRATCH_BYTES; the experiments library and the emulator build read FOURIER_REALND_SCRATCH_BYTES at create
+// The scratch bound is REAL_SCRATCH_BYTES; the experiments library and the emulator build read FOURIER_REALND_SCRATCH_BYTES at create
 // instead (the chunk-walk tests)
-constexpr size_t REALND_SCRATCH_BYTES = (size_t)1 << 30;
 constexpr int REALND_MAX_RANK = 4;
 
-template <typename T> class RealNdPlan {
+template <typename T> class RealNdPlan : public HandleBase {
  public:
   static constexpr size_t ELEM = sizeof(cpx<T>);
 
@@ -58,13 +57,9 @@ template <typename T> class RealNdPlan {
     if (packed_) device_ = row_->device();
     else if (device >= 0) device_ = device;
     else if (hipGetDevice(&device_) != hipSuccess) device_ = 0;
-    Guard g(device_);
-    if (packed_) {  // W_W^j, j <= W/4: f64 trigonometry, cast (as RealPlan)
-      std::vector<cpx<T>> tw(h_ / 2 + 1);
-      for (size_t j = 0; j < tw.size(); ++j) { double re, im; unit_root(j, w_, re, im); tw[j] = {(T)re, (T)im}; }
-      tw_.upload(tw);
-    }
-    if (const char* e = dev_env("FOURIER_REALND_SCRATCH_BYTES")) scratch_cap_ = (size_t)std::strtoull(e, nullptr, 10);
+    DeviceGuard g(device_);
+    if (packed_) tw_.upload(real_untangle_twiddles<T>(w_));
+    scratch_cap_ = scratch_bound("FOURIER_REALND_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     desc_ = std::string(packed_ ? "realnd packed: rows " : "realnd composed: rows ") + (packed_ ? row_->describe() : rows1d_->describe());
     const size_t cols = packed_ ? h_ : h_ + 1;
     for (size_t d = 0; d < axis_.size(); ++d) {
@@ -72,22 +67,17 @@ template <typename T> class RealNdPlan {
       desc_ += axis_[d] ? AxisRoute<T>::of(*axis_[d]).describe(inner(d, cols)) : std::string("identity");
     }
   }
-  RealNdPlan(const RealNdPlan&) = delete;
-  RealNdPlan& operator=(const RealNdPlan&) = delete;
 
   int rank() const { return (int)shape_.size(); }
-  const char* describe() const { return desc_.c_str(); }
-  int last_status() const { return status_; }
-  void set_status(int s) const { status_ = s; }
 
   // items per chunk for a call of `batch` items; sizes the scratch, the row plan's and the axis routes' buffers for it (reserve:
   // ahead of time, so that later calls of at most `batch` items never allocate)
   size_t prepare(size_t batch) const {
     if (batch == 0) return 0;
     if (rank() == 1) { rows1d_->reserve(batch); return batch; }
-    Guard g(device_);
+    DeviceGuard g(device_);
     const size_t cols = packed_ ? h_ : h_ + 1, per = rows_ * cols * ELEM;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, scratch_cap_ / per));
+    const size_t chunk = chunk_rows(batch, scratch_cap_, per);
     scratch_.ensure(chunk * per);
     if (packed_) {
       row_->reserve_for(chunk * rows_, false);
@@ -101,14 +91,11 @@ template <typename T> class RealNdPlan {
   void reserve(size_t batch) const { (void)prepare(batch); }
 
   void forward(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
-    if (code != ::fourier::c::FOURIER_TRANSFORM_FFT && code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT) {
-      check(d_in, d_out, batch, rows_ * w_ * sizeof(T), rows_ * (h_ + 1) * ELEM);
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not a forward transform code");
-    }
-    if (rank() == 1) return rows1d_->forward(d_in, d_out, batch, code, stream);
-    check(d_in, d_out, batch, rows_ * w_ * sizeof(T), rows_ * (h_ + 1) * ELEM);
+    check_buffers(d_in, d_out, batch * rows_ * w_ * sizeof(T), batch * rows_ * (h_ + 1) * ELEM, ELEM, false);
+    if (!is_forward(code)) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not a forward transform code");
+    if (rank() == 1) return rows1d_->run_forward(d_in, d_out, batch, code, stream);
     if (batch == 0) return;
-    Guard g(device_);
+    DeviceGuard g(device_);
     const size_t chunk = prepare(batch);
     const T* in = (const T*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
@@ -119,7 +106,7 @@ template <typename T> class RealNdPlan {
       if (packed_) {
         row_->exec(in + b0 * rows_ * w_, work, nb * rows_, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
         axes(work, work, nb, h_, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
-        sweep(REAL_ND_POST, work, out + b0 * xi, nb, code_scale(code), stream);
+        sweep(REAL_ND_POST, work, out + b0 * xi, nb, item_scale(code), stream);
       } else {
         rows1d_->run_forward(in + b0 * rows_ * w_, out + b0 * xi, nb * rows_, code, stream);
         axes(out + b0 * xi, out + b0 * xi, nb, h_ + 1, code, stream);
@@ -128,15 +115,11 @@ template <typename T> class RealNdPlan {
   }
 
   void inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
-    if (code != ::fourier::c::FOURIER_TRANSFORM_IFFT && code != ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT &&
-        code != ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT) {
-      check(d_in, d_out, batch, rows_ * (h_ + 1) * ELEM, rows_ * w_ * sizeof(T));
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not an inverse transform code");
-    }
-    if (rank() == 1) return rows1d_->inverse(d_in, d_out, batch, code, stream);
-    check(d_in, d_out, batch, rows_ * (h_ + 1) * ELEM, rows_ * w_ * sizeof(T));
+    check_buffers(d_in, d_out, batch * rows_ * (h_ + 1) * ELEM, batch * rows_ * w_ * sizeof(T), ELEM, false);
+    if (!is_inverse(code)) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "not an inverse transform code");
+    if (rank() == 1) return rows1d_->run_inverse(d_in, d_out, batch, code, stream);
     if (batch == 0) return;
-    Guard g(device_);
+    DeviceGuard g(device_);
     const size_t chunk = prepare(batch);
     const cpx<T>* in = (const cpx<T>*)d_in;
     T* out = (T*)d_out;
@@ -146,8 +129,8 @@ template <typename T> class RealNdPlan {
       const size_t nb = std::min(chunk, batch - b0);
       if (packed_) {
         // the code's scale over P = W x R: the unscaled inverses of Z return P/2 times what the sweep wrote, and the sweep's S +- iT
-        // carry a factor 2 (as RealPlan with N = P)
-        sweep(REAL_ND_PRE, in + b0 * xi, work, nb, code_scale(code), stream);
+        // carry a factor 2 (RealPlan::run_inverse with N = P)
+        sweep(REAL_ND_PRE, in + b0 * xi, work, nb, item_scale(code), stream);
         axes(work, work, nb, h_, ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT, stream);
         row_->exec(work, out + b0 * rows_ * w_, nb * rows_, ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT, stream);
       } else {
@@ -158,16 +141,6 @@ template <typename T> class RealNdPlan {
   }
 
  private:
-  struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-      if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-      if (prev != dev) (void)hipSetDevice(dev);
-      else prev = -1;
-    }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  };
-
   // one complex plan per distinct length
   const Plan<T>* plan_of(size_t n, int device) {
     for (auto& p : plans_)
@@ -199,32 +172,8 @@ template <typename T> class RealNdPlan {
     if (src != out) HIP_CHECK(hipMemcpyAsync(out, in, nb * rows_ * cols * ELEM, hipMemcpyDeviceToDevice, stream));
   }
 
-  // the code's scale over the product P of the transformed lengths, in T as Plan::exec
-  double code_scale(int code) const {
-    const T p = (T)((double)rows_ * (double)w_);
-    switch (code) {
-      case ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT:
-      case ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_IFFT: return (double)((T)1 / std::sqrt(p));
-      case ::fourier::c::FOURIER_TRANSFORM_IFFT: return (double)((T)1 / p);
-      default: return 1.0;
-    }
-  }
-
-  // out of place only, no overlap, both pointers aligned to one complex element
-  static void check(const void* d_in, void* d_out, size_t batch, size_t in_item, size_t out_item) {
-    if (!d_in || !d_out) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "null buffer");
-    if ((uintptr_t)d_in % ELEM || (uintptr_t)d_out % ELEM) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "misaligned buffer");
-    const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out;
-    if (a == b || (batch && a < b + batch * out_item && b < a + batch * in_item))
-      throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "input and output overlap");
-  }
-
-  // x / d = (umulhi(x, m) + x) >> l for every 32-bit x (as RealPlan::sweep)
-  static void divider(uint32_t d, uint32_t& m, uint32_t& l) {
-    l = 0;
-    while ((1ull << l) < d) ++l;
-    m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
-  }
+  // the code's scale over the product P of the transformed lengths
+  double item_scale(int code) const { return code_scale<T>(code, (T)((double)rows_ * (double)w_)); }
 
   // the N-D sweep over nb items: one workgroup per row and segment of lanes, launches of whole items with fewer than 2^31 workgroups
   void sweep(int which, const cpx<T>* in, cpx<T>* out, size_t nb, double scale, hipStream_t stream) const {
@@ -268,17 +217,7 @@ template <typename T> class RealNdPlan {
   std::unique_ptr<RealPlan<T>> rows1d_;
   DevBuf tw_;
   mutable DevBuf scratch_;
-  size_t scratch_cap_ = REALND_SCRATCH_BYTES;
-  mutable int status_ = 0;
-  std::string desc_;
+  size_t scratch_cap_ = REAL_SCRATCH_BYTES;
 };
-
-template <typename T> static RealNdPlan<T>* create_realnd_plan(int rank, const size_t* shape, int device) {
-  try {
-    return new RealNdPlan<T>(rank, shape, device);
-  } catch (...) {
-    return nullptr;
-  }
-}
 
 }  // namespace fourier_hip
