@@ -85,8 +85,7 @@ template <typename T> class ConvPlan : public HandleBase {
     if (real_) rplan_->reserve(chunk);  // (RealPlan's own scratch: rows of the filter transforms, kept)
     else plan_->reserve_for(chunk, false);
     cpx<T>* bank = (cpx<T>*)bank_.p;
-    for (size_t f0 = 0; f0 < filters; f0 += chunk) {
-      const size_t nf = std::min(chunk, filters - f0);
+    for_chunks(filters, chunk, [&](size_t f0, size_t nf) {
       ConvArgs a{};
       a.in = (const T*)d_taps + f0 * taps * words;
       a.out = scratch_.p;
@@ -94,7 +93,7 @@ template <typename T> class ConvPlan : public HandleBase {
       FOURIER_LAUNCH(get_conv_sweep_kernel(Real<T>{}, CONV_PAD), elementwise_grid(nf * n_ * words), 256, 0, stream, a);
       if (real_) rplan_->run_forward(scratch_.p, bank + f0 * blen_, nf, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
       else plan_->exec(scratch_.p, bank + f0 * blen_, nf, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
-    }
+    });
     ConvArgs a{};
     a.out = bank;
     a.count = filters * blen_;
@@ -116,8 +115,7 @@ template <typename T> class ConvPlan : public HandleBase {
     cpx<T>* work = (cpx<T>*)scratch_.p;
     const cpx<T>* bank = (const cpx<T>*)bank_.p;
     const int FWD = ::fourier::c::FOURIER_TRANSFORM_FFT, INV = ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT;
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
       const void* src = in + b0 * row;
       void* dst = out + b0 * row;
       switch (route_) {
@@ -143,7 +141,7 @@ template <typename T> class ConvPlan : public HandleBase {
           rplan_->run_inverse(work, dst, nb, INV, stream);
           break;
       }
-    }
+    });
   }
 
  private:

@@ -1,7 +1,7 @@
 // engine_generic.h -- 2^a * 3^b with a < 12 beyond the LDS kernels' reach: the reference's Stockham autosort pass by pass in global
 // memory (autosort/mod.rs:203-284).
 #pragma once
-#include "engine_common.h"
+#include "engine_host.h"
 
 namespace fourier_hip {
 
@@ -31,15 +31,7 @@ template <typename T> class GenericEngine {
       ps.r = r; ps.s = (uint32_t)s; ps.m = (uint32_t)(size / (size_t)r);
       ps.tw_lo.reset(new DevBuf());
       ps.tw_hi.reset(new DevBuf());
-      if (ps.m > 1) {  // W_size^{e} as a two-level table: lo[e & mask] * hi[e >> bits] (f64 trig, cast: twiddle.rs:7-19)
-        const int lb = (ilog2(size) + 1) / 2;
-        ps.lo_bits = (uint32_t)lb;
-        std::vector<cpx<T>> lo((size_t)1 << lb), hi((size >> lb) + 1);
-        for (size_t e = 0; e < lo.size(); ++e) { double re, im; unit_root(e, size, re, im); lo[e] = {(T)re, (T)im}; }
-        for (size_t h = 0; h < hi.size(); ++h) { double re, im; unit_root((uint64_t)h << lb, size, re, im); hi[h] = {(T)re, (T)im}; }
-        ps.tw_lo->upload(lo);
-        ps.tw_hi->upload(hi);
-      }
+      if (ps.m > 1) ps.lo_bits = upload_two_level<T>(size, *ps.tw_lo, *ps.tw_hi);  // W_size^{e}
       ps.fn = get_stockham_pass_kernel(Real<T>{}, r);
       ps.smem = s == 1 ? (size_t)r * 256 * sizeof(cpx<T>) : 0;  // first pass: the workgroup's outputs are staged in LDS
       raise_smem_limit((const void*)ps.fn, ps.smem);
@@ -72,11 +64,7 @@ template <typename T> class GenericEngine {
       a.swap_in = (p == 0) && inverse; a.swap_out = (p + 1 == np) && inverse; a.final_pass = (p + 1 == np);
       a.scale = (p + 1 == np) ? scale : 1.0;
       for (int e = 0; e < ps.r && e < 27; ++e) unit_root((uint64_t)e, (uint64_t)ps.r, a.wr[e], a.wi[e]);
-      const uint64_t grid = (uint64_t)a.blocks_per * batch;
-      if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-      PROF_BEGIN(prof, (int)p);
-      FOURIER_LAUNCH(ps.fn, grid, 256, ps.smem, stream, a);
-      PROF_END(prof);
+      launch(prof, (int)p, ps.fn, (uint64_t)a.blocks_per * batch, 256, ps.smem, stream, a);
       src = dst;
     }
   }

@@ -1,7 +1,7 @@
 // engine_mixed.h -- small mixed-radix sizes in LDS: 2^a * 3^b (b > 0) on the reference's own schedule and tables
 // (autosort/mod.rs:20-46,104-116); lengths with factors 5..13 on the same pass.
 #pragma once
-#include "engine_common.h"
+#include "engine_host.h"
 #include "mixed_schedule.h"
 
 namespace fourier_hip {
@@ -59,29 +59,11 @@ template <typename T> class MixedEngine {
     if (dev_env("FOURIER_MIX_REFERENCE_RADICES") && mix_extended((uint32_t)n)) return false;  // A/B against Bluestein
     return pick_kernel(n).fn != nullptr;  // no per-length kernel and beyond the runtime kernel's 8192 points: Bluestein
   }
-  // twiddle.rs:7-19 verbatim: theta = (index*2) as f64 * PI / size as f64; (cos, -sin) cast to T.
-  // cos and sin stay two separate libm calls, as in Rust (a merged sincos() differs in the last bit).
-  __attribute__((noinline)) static double libm_cos(double t) { return std::cos(t); }
-  __attribute__((noinline)) static double libm_sin(double t) { return std::sin(t); }
-  static cpx<T> ref_twiddle(size_t index, size_t size) {
-    const double theta = (double)(index * 2) * M_PI / (double)size;
-    return {(T)libm_cos(theta), (T)(-libm_sin(theta))};
-  }
-
   // deferred_kernel: a length without any ahead-of-time kernel (beyond the runtime kernel's reach); the plan is usable only
   // after specialise() has succeeded (Plan::set_option "specialise" on a Bluestein plan)
   explicit MixedEngine(size_t n, bool deferred_kernel = false) : n_(n) {
     if (!factor(n, radices_)) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "length does not factor over 2, 3, 5, 7, 11, 13");
-    std::vector<cpx<T>> tw;
-    size_t cur = n;
-    for (const size_t R : radices_) {  // mod.rs:24-46
-      const size_t m = cur / R;
-      for (size_t i = 0; i < m; ++i) {
-        tw.push_back({(T)1, (T)0});
-        for (size_t j = 1; j < R; ++j) tw.push_back(ref_twiddle(i * j, cur));
-      }
-      cur /= R;
-    }
+    std::vector<cpx<T>> tw = ref_schedule_table<T>(n, radices_, ref_twiddle<T>);
     if (tw.empty()) tw.push_back({(T)1, (T)0});
     tw_.upload(tw);
     // transforms per workgroup: about 1024 points (16 KiB of LDS in f32: several workgroups per CU; larger groups that
@@ -137,21 +119,9 @@ template <typename T> class MixedEngine {
     a.npass = (uint32_t)radices_.size();
     for (size_t r = 0; r < radices_.size(); ++r) a.radix[r] = (uint8_t)radices_[r];
     a.forward = forward; a.scaled = scaled; a.scale = scale;
-    const cpx<T> w3 = ref_twiddle(1, 3), w8 = ref_twiddle(1, 8);  // butterfly.rs:12,50
+    const cpx<T> w3 = ref_twiddle<T>(1, 3), w8 = ref_twiddle<T>(1, 8);  // butterfly.rs:12,50
     a.w3re = w3.re; a.w3im = w3.im; a.w8re = w8.re; a.w8im = w8.im;
-    const uint64_t grid = (batch + group_ - 1) / group_;
-    if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-    PROF_BEGIN(prof, 0);
-#ifndef FOURIER_EMU
-    if (rtc_.fn) {  // the kernel specialised at run time: a module function
-      void* params[] = {&a};
-      HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)rtc_.fn, (unsigned)grid, 1, 1, threads_, 1, 1, (unsigned)smem_, stream, params, nullptr));
-    } else
-#endif
-    {
-      FOURIER_LAUNCH(fn_, grid, threads_, smem_, stream, a);
-    }
-    PROF_END(prof);
+    launch(prof, 0, fn_, (batch + group_ - 1) / group_, threads_, smem_, stream, a, rtc_);  // rtc_: the kernel specialised at run time
   }
 
  private:

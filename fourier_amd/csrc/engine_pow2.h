@@ -1,7 +1,7 @@
 // engine_pow2.h -- batched power-of-two FFT (and 2^a*3^b with a >= 12): the schedule of big-radix Stockham passes, its tables
 // and launches.  Counterpart of Autosort::new / initialize_twiddles / apply_stages (autosort/mod.rs:24-46,104-134,313-404).
 #pragma once
-#include "engine_common.h"
+#include "engine_host.h"
 
 namespace fourier_hip {
 
@@ -11,24 +11,8 @@ template <typename T> struct StageTables {
 
 template <typename T> static void make_stage_tables(int L, StageTables<T>& st) {
   const int Q = L / 16, R2 = Q >= 16 ? 16 : Q, R3 = Q / (R2 ? R2 : 1);
-  std::vector<cpx<T>> t1((size_t)Q * 16);
-  for (int th = 0; th < Q; ++th)
-    for (int k = 0; k < 16; ++k) {
-      double re, im;
-      unit_root((uint64_t)th * k, (uint64_t)L, re, im);
-      t1[(size_t)th * 16 + k] = {(T)re, (T)im};
-    }
-  st.tw1.upload(t1);
-  if (Q > 1 && R3 > 1) {
-    std::vector<cpx<T>> t2((size_t)R3 * 16);
-    for (int i = 0; i < R3; ++i)
-      for (int k = 0; k < 16; ++k) {
-        double re, im;
-        unit_root((uint64_t)i * k, (uint64_t)Q, re, im);
-        t2[(size_t)i * 16 + k] = {(T)re, (T)im};
-      }
-    st.tw2.upload(t2);
-  }
+  st.tw1.upload(product_table<T>(L, Q, 16));                        // W_L^{th * k} as [th < Q][k < 16]
+  if (Q > 1 && R3 > 1) st.tw2.upload(product_table<T>(Q, R3, 16));  // W_Q^{i * k} as [i < R3][k < 16]
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -82,25 +66,9 @@ template <typename T> class Pow2Engine {
       pass->mode = MODE_TWOLEVEL;
       pass->k = tl;
       pass->s = 1; pass->size = n; pass->cn = 1;
-      for (int L : {tl1, tl2}) {
-        if (stage_.find(L) == stage_.end()) {
-          auto st = std::unique_ptr<StageTables<T>>(new StageTables<T>());
-          make_stage_tables<T>(L, *st);
-          stage_.emplace(L, std::move(st));
-        }
-      }
-      pass->st = stage_[tl1].get();
-      pass->st2 = stage_[tl2].get();
-      {  // full inter-pass twiddle table W_N^{i*k1}, laid out [k1][i] (f64 trig, cast: twiddle.rs:7-19)
-        std::vector<cpx<T>> tw((size_t)n);
-        for (int k1 = 0; k1 < tl1; ++k1)
-          for (int i = 0; i < tl2; ++i) {
-            double re, im;
-            unit_root((uint64_t)i * (uint64_t)k1, n, re, im);
-            tw[(size_t)k1 * tl2 + i] = {(T)re, (T)im};
-          }
-        pass->tw_lo.upload(tw);
-      }
+      pass->st = stage_tables(tl1);
+      pass->st2 = stage_tables(tl2);
+      pass->tw_lo.upload(product_table<T>(n, tl1, tl2));  // full inter-pass twiddle table W_N^{i*k1}, laid out [k1 < L1][i < L2]
       tl1_ = tl1; tl2_ = tl2;
       set_smem_attribute(pass->k);
       desc_override_ = std::to_string(tl1) + "x" + std::to_string(tl2) + " one-launch";
@@ -148,19 +116,14 @@ template <typename T> class Pow2Engine {
         if (!is_pow2(s)) throw EngineError(::fourier::c::FOURIER_HIP_RUNTIME_ERROR, "tile pass behind an odd-radix pass");  // kernels shift by log2(s)
       }
       const int Lt = pass->k.split ? L / 2 : L;  // length of the in-tile FFT (a split pass runs a half-length tile)
-      auto it = stage_.find(Lt);
-      if (it == stage_.end()) {
-        auto st = std::unique_ptr<StageTables<T>>(new StageTables<T>());
-        make_stage_tables<T>(Lt, *st);
-        it = stage_.emplace(Lt, std::move(st)).first;
-      }
-      pass->st = it->second.get();
+      pass->st = stage_tables(Lt);
       if (pass->k.split) {
         std::vector<cpx<T>> wh((size_t)Lt);
-        for (int nn = 0; nn < Lt; ++nn) { double re, im; unit_root((uint64_t)nn, (uint64_t)L, re, im); wh[(size_t)nn] = {(T)re, (T)im}; }
+        for (int nn = 0; nn < Lt; ++nn) wh[(size_t)nn] = root<T>((uint64_t)nn, (uint64_t)L);
         pass->tw_half.upload(wh);
       }
-      if (pass->mode == MODE_FIRST || pass->mode == MODE_MID) make_two_level(*pass, size);
+      // two-level table of W_size^{e}: e = (e >> lo_bits) << lo_bits | (e & mask)
+      if (pass->mode == MODE_FIRST || pass->mode == MODE_MID) pass->lo_bits = upload_two_level<T>(size, pass->tw_lo, pass->tw_hi);
       if (pass->mode == MODE_LAST && !pass->k.split) {
         pass->k_pf = get_prefetch_kernel(Real<T>{}, L, IO_PLAIN);
         if (pass->k_pf.fn && pass->k_pf.COLS == pass->k.COLS) pass->pf_grid = resident_grid(pass->k_pf);
@@ -190,7 +153,7 @@ template <typename T> class Pow2Engine {
       pass->s = s; pass->size = size; pass->cn = size / r;  // cn = m of this pass
       if (size != r) {  // W_size^{e}, e < size (i*k < m*R)
         std::vector<cpx<T>> tw((size_t)size);
-        for (size_t e = 0; e < (size_t)size; ++e) { double re, im; unit_root(e, size, re, im); tw[e] = {(T)re, (T)im}; }
+        for (size_t e = 0; e < (size_t)size; ++e) tw[e] = root<T>(e, size);
         pass->tw_lo.upload(tw);
       }
       passes_.push_back(std::move(pass));
@@ -198,16 +161,6 @@ template <typename T> class Pow2Engine {
     }
   }
 
-  // two-level table of W_size^{e}: e = (e >> lo_bits) << lo_bits | (e & mask)
-  static void make_two_level(Pass& pass, uint64_t size) {
-    const int lb = (ilog2(size) + 1) / 2;
-    pass.lo_bits = (uint32_t)lb;
-    std::vector<cpx<T>> lo((size_t)1 << lb), hi((size_t)(size >> lb) + 1);  // +1: size need not be a power of two
-    for (size_t e = 0; e < lo.size(); ++e) { double re, im; unit_root(e, size, re, im); lo[e] = {(T)re, (T)im}; }
-    for (size_t h = 0; h < hi.size(); ++h) { double re, im; unit_root((uint64_t)h << lb, size, re, im); hi[h] = {(T)re, (T)im}; }
-    pass.tw_lo.upload(lo);
-    pass.tw_hi.upload(hi);
-  }
   static void set_smem_attribute(const KernelInfo& k) { raise_smem_limit((const void*)k.fn, k.smem); }
   // workgroups of a persistent kernel that are resident at once on this device, a multiple of 8 (one block sequence per XCD)
   static unsigned resident_grid(const KernelInfo& k) {
@@ -232,14 +185,7 @@ template <typename T> class Pow2Engine {
     }
     if (passes_[0]->mode != MODE_TWOLEVEL) return false;
     if (!get_blu_small_kernel(Real<T>{}, ilog2(n_), blu_small_)) return false;
-    std::vector<cpx<T>> tw(n_);
-    for (int k1 = 0; k1 < tl2_; ++k1)      // swapped roles: k1' < L2, i' < L1, layout [k1'][i']
-      for (int i = 0; i < tl1_; ++i) {
-        double re, im;
-        unit_root((uint64_t)i * (uint64_t)k1, n_, re, im);
-        tw[(size_t)k1 * tl1_ + i] = {(T)re, (T)im};
-      }
-    passes_[0]->tw_hi.upload(tw);
+    passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // swapped roles: k1' < L2, i' < L1, layout [k1'][i']
     set_smem_attribute(blu_small_);
     return true;
   }
@@ -257,10 +203,7 @@ template <typename T> class Pow2Engine {
     a.mul = wtab; a.blu_x = xtab; a.blu_n = n_user; a.blu_swap = inverse;
     a.n = n_; a.scale = scale; a.nxcd = nxcd & 0xff; a.total_cols = batch;
     const uint64_t grid = rows ? (batch + blu_small_.COLS - 1) / blu_small_.COLS : batch;
-    if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-    PROF_BEGIN(prof, 0);
-    FOURIER_LAUNCH(blu_small_.fn, grid, blu_small_.NT, blu_small_.smem, stream, a);
-    PROF_END(prof);
+    launch(prof, 0, blu_small_.fn, grid, blu_small_.NT, blu_small_.smem, stream, a);
   }
 
   // Convolution with a filter bank in one launch (conv_small_kernel; the convolution handle): available when this plan is a one-launch
@@ -269,16 +212,7 @@ template <typename T> class Pow2Engine {
     if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
     if (conv_small_.fn) return true;
     if (!get_conv_small_kernel(Real<T>{}, ilog2(n_), conv_small_)) return false;
-    if (!passes_[0]->tw_hi.p) {  // (enable_bluestein_small uploads the same table)
-      std::vector<cpx<T>> tw(n_);
-      for (int k1 = 0; k1 < tl2_; ++k1)
-        for (int i = 0; i < tl1_; ++i) {
-          double re, im;
-          unit_root((uint64_t)i * (uint64_t)k1, n_, re, im);
-          tw[(size_t)k1 * tl1_ + i] = {(T)re, (T)im};
-        }
-      passes_[0]->tw_hi.upload(tw);
-    }
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (enable_bluestein_small uploads the same table)
     set_smem_attribute(conv_small_);
     return true;
   }
@@ -294,8 +228,7 @@ template <typename T> class Pow2Engine {
     a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
     a.mul = bank; a.bank_filters = filters; a.bank_first = first_row;
     a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
-    if (batch > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-    FOURIER_LAUNCH(conv_small_.fn, batch, conv_small_.NT, conv_small_.smem, stream, a);
+    launch(nullptr, 0, conv_small_.fn, batch, conv_small_.NT, conv_small_.smem, stream, a);
   }
 
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
@@ -353,10 +286,7 @@ template <typename T> class Pow2Engine {
       f.in = in + b0 * n_; f.out = out + b0 * n_; f.batch = (uint32_t)nb;
       HIP_CHECK(hipMemsetAsync(fused_ctrl_.p, 0, fused_ctrl_words(nb) * sizeof(uint32_t), stream));
       const uint64_t items = (uint64_t)nb * (f.tiles_a + f.tiles_b);
-      const unsigned grid = (unsigned)std::min<uint64_t>(fused_grid_, items);
-      PROF_BEGIN(prof, slot);
-      FOURIER_LAUNCH(fused_.fn, grid, fused_.NT, fused_.smem, stream, f);
-      PROF_END(prof);
+      launch(prof, slot, fused_.fn, std::min<uint64_t>(fused_grid_, items), fused_.NT, fused_.smem, stream, f);
       // The kernel bounds its inter-workgroup waits (spin_limit) and raises ctrl[1] when one gives up; every workgroup
       // then returns early and part of the output is unwritten.  That must not read as success: the flag comes back
       // before the call returns (this plan option is therefore synchronous) and turns into FOURIER_HIP_RUNTIME_ERROR.
@@ -434,10 +364,7 @@ template <typename T> class Pow2Engine {
     const bool lane_per_transform = tiny_ || n_ == 16 || (n_ == 32 && sizeof(T) == 4);
     if (lane_per_transform && blu.io == IO_PLAIN) {
       TinyArgs a{in, out, (uint64_t)batch, (int)n_, inverse, inverse, scale};
-      PROF_BEGIN(prof, slot0);
-      const TinyKernel fn = get_tiny_kernel(Real<T>{}, n_);
-      FOURIER_LAUNCH(fn, (batch + 255) / 256, 256, 0, stream, a);
-      PROF_END(prof);
+      launch(prof, slot0, get_tiny_kernel(Real<T>{}, n_), (batch + 255) / 256, 256, 0, stream, a);
       apply_mul(out, batch, mul, inverse, scale, stream, prof, slot0);
       return;
     }
@@ -548,9 +475,8 @@ template <typename T> class Pow2Engine {
     if (inverse || scale != 1.0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "pointwise multiplier: forward unscaled only");
     BluArgs m{nullptr, out, mul, (uint64_t)n_, (uint64_t)n_, (uint64_t)batch, 0, 1.0};
     const size_t blocks = (batch * n_ + 255) / 256;
-    PROF_BEGIN(prof, slot);  // counted in the slot of the pass it follows (the last forward pass)
-    FOURIER_LAUNCH(get_blu_kernel(Real<T>{}, 2), std::min<size_t>(std::max<size_t>(blocks, 1), 256 * 32), 256, 0, stream, m);
-    PROF_END(prof);
+    // counted in the slot of the pass it follows (the last forward pass)
+    launch(prof, slot, get_blu_kernel(Real<T>{}, 2), std::min<size_t>(std::max<size_t>(blocks, 1), 256 * 32), 256, 0, stream, m);
   }
 
   // One pass of the schedule.  inverse / scale / mul take effect on the passes they belong to (leading swap on
@@ -571,11 +497,7 @@ template <typename T> class Pow2Engine {
         for (int e = 0; e < ps.odd_r; ++e) unit_root((uint64_t)e, (uint64_t)ps.odd_r, o.wr[e], o.wi[e]);
         constexpr int VEC = 16 / (2 * (int)sizeof(T));
         const uint64_t threads = (uint64_t)batch * (ps.s / VEC) * ps.cn;
-        const uint64_t grid = (threads + 255) / 256;
-        if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-        PROF_BEGIN(prof, slot);
-        FOURIER_LAUNCH(ps.odd_fn, grid, 256, 0, stream, o);
-        PROF_END(prof);
+        launch(prof, slot, ps.odd_fn, (threads + 255) / 256, 256, 0, stream, o);
         return;
       }
       PassArgs a;
@@ -586,9 +508,7 @@ template <typename T> class Pow2Engine {
       a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p; a.tw_half = ps.tw_half.p;
       a.n = n_; a.cn = ps.cn; a.s = ps.s; a.s_shift = (uint32_t)ilog2(ps.s);
       a.lo_bits = ps.lo_bits;
-      a.nxcd = nxcd & 0xff;
-      a.xcd_interleave = (nxcd >> 8) & 7;
-      a.walk_band = (nxcd >> 12) & 0xff; a.walk_group = (nxcd >> 20) & 0x3ff; a.walk_tf = nxcd >> 30;
+      set_tile_order(a, nxcd);
       const bool blu_here = ps.has_blu && ((blu.io == IO_BLU_IN && p == 0) || (blu.io == IO_BLU_OUT && p + 1 == np));
       if (blu_here) {
         a.blu_x = blu.xtab; a.blu_n = blu.n; a.blu_swap = blu.swap;
@@ -616,22 +536,18 @@ template <typename T> class Pow2Engine {
         a.tiles = ps.cn / kk.COLS;
         grid = (uint64_t)batch * a.tiles * (kk.split ? 2 : 1);
       }
-      if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
       // LAST pass in its persistent prefetching form (plan option "last_pass_prefetch"): the same tiles, walked by as many
       // workgroups as are resident at once
       const KernelInfo& pf = blu_here ? ps.k_pf_blu : ps.k_pf;
       if (prefetch_last(ps) && ps.mode == MODE_LAST && pf.fn && !a.swap_in && (!blu_here || blu.io == IO_BLU_OUT)) {
+        check_grid(grid);
         a.total_cols = grid;  // tiles of the whole launch
         const uint64_t resident = blu_here ? ps.pf_blu_grid : ps.pf_grid;
-        PROF_BEGIN(prof, slot);
-        FOURIER_LAUNCH(pf.fn, std::min<uint64_t>(grid, resident), pf.NT, pf.smem, stream, a);
-        PROF_END(prof);
+        launch(prof, slot, pf.fn, std::min<uint64_t>(grid, resident), pf.NT, pf.smem, stream, a);
         return;
       }
       const KernelInfo& run = (skeleton_ && !blu_here && ps.k_skel.fn) ? ps.k_skel : kk;
-      PROF_BEGIN(prof, slot);
-      FOURIER_LAUNCH(run.fn, grid, run.NT, run.smem, stream, a);
-      PROF_END(prof);
+      launch(prof, slot, run.fn, grid, run.NT, run.smem, stream, a);
     }
   }
   // "skeleton" (experiments library): every pass that has one runs as its load / store skeleton -- timing only, wrong results
@@ -652,13 +568,7 @@ template <typename T> class Pow2Engine {
     if (!can_conv()) return;
     conv_ = get_conv_kernel(Real<T>{}, passes_.back()->k.L);
     set_smem_attribute(conv_);
-    auto it = stage_.find(conv_.L);  // the last pass may run on half tiles with half-length stage tables
-    if (it == stage_.end()) {
-      auto st = std::unique_ptr<StageTables<T>>(new StageTables<T>());
-      make_stage_tables<T>(conv_.L, *st);
-      it = stage_.emplace(conv_.L, std::move(st)).first;
-    }
-    conv_st_ = it->second.get();
+    conv_st_ = stage_tables(conv_.L);  // the last pass may run on half tiles with half-length stage tables
   }
   // the same launch with a filter bank (ConvPlan): enable_conv plus the kernel that picks one table per transform
   void enable_conv_bank() {
@@ -687,9 +597,7 @@ template <typename T> class Pow2Engine {
     a.mul = wtab;
     a.n = n_; a.cn = last.cn; a.s = last.s; a.s_shift = (uint32_t)ilog2(last.s);
     a.tiles = last.cn / conv_.COLS;
-    a.nxcd = nxcd & 0xff;
-    a.xcd_interleave = (nxcd >> 8) & 7;
-    a.walk_band = (nxcd >> 12) & 0xff; a.walk_group = (nxcd >> 20) & 0x3ff; a.walk_tf = nxcd >> 30;
+    set_tile_order(a, nxcd);
     // this kernel (only) reads a per-transform table indexed like the data, the transformed chirp: let every XCD own an
     // eighth of the TILES of every transform, so that its 1/8 of the table (2 MiB of 16 at M = 2^21) stays in its L2
     // (with streaming stores: conv 4.5 vs 4.75 ms per 512 at C4; the plain passes lose 10-15 % under this order)
@@ -698,14 +606,20 @@ template <typename T> class Pow2Engine {
     a.scale = 1.0;
     a.bank_filters = filters; a.bank_first = first_row;
     const KernelInfo& ck = filters ? conv_bank_ : conv_;
-    const uint64_t grid = (uint64_t)batch * a.tiles;
-    if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-    PROF_BEGIN(prof, slot);
-    FOURIER_LAUNCH(ck.fn, grid, ck.NT, ck.smem, stream, a);
-    PROF_END(prof);
+    launch(prof, slot, ck.fn, (uint64_t)batch * a.tiles, ck.NT, ck.smem, stream, a);
   }
 
  private:
+  // the stage tables of an in-tile transform of length L, built on first use
+  StageTables<T>* stage_tables(int L) {
+    auto it = stage_.find(L);
+    if (it == stage_.end()) {
+      auto st = std::unique_ptr<StageTables<T>>(new StageTables<T>());
+      make_stage_tables<T>(L, *st);
+      it = stage_.emplace(L, std::move(st)).first;
+    }
+    return it->second.get();
+  }
   size_t n_;
   bool tiny_ = false;
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan

@@ -2,7 +2,7 @@
 // on column tiles (kernels_tiled.h): N = L1 x L2 (x L3), every factor a pass length with a kernel.  The reference runs these
 // lengths natively, one small radix per sweep of memory (autosort/mod.rs:104-116, 203-284).
 #pragma once
-#include "engine_common.h"
+#include "engine_host.h"
 #include "mixed_schedule.h"
 
 namespace fourier_hip {
@@ -154,39 +154,20 @@ template <typename T> class TiledMixedEngine {
       // tables of the in-tile transform: the reference's layout for a plan of length L (mod.rs:24-46), f64 trig then cast
       auto it = tables_.find(L);
       if (it == tables_.end()) {
-        std::vector<cpx<T>> tw;
-        size_t cur = L;
-        if (ps.k.r1) {  // register-resident kernel: the twiddle between its two stages, W_L^{j2 * k1} as [k1 < r1][j2 < r2]
-          for (size_t k1 = 0; k1 < ps.k.r1; ++k1)
-            for (size_t j2 = 0; j2 < ps.k.r2; ++j2) {
-              double re, im;
-              unit_root(j2 * k1, L, re, im);
-              tw.push_back({(T)re, (T)im});
-            }
-          cur = 1;
-        }
-        while (cur > 1) {
-          const size_t R = mix_next_radix(L, (uint32_t)cur, cur == L);
-          const size_t mm = cur / R;
-          for (size_t i = 0; i < mm; ++i) {
-            tw.push_back({(T)1, (T)0});
-            for (size_t j = 1; j < R; ++j) tw.push_back(ref_twiddle(i * j, cur));
-          }
-          cur /= R;
-        }
         auto buf = std::unique_ptr<DevBuf>(new DevBuf());
-        buf->upload(tw);
+        if (ps.k.r1) {  // register-resident kernel: the twiddle between its two stages, W_L^{j2 * k1} as [k1 < r1][j2 < r2]
+          buf->upload(product_table<T>(L, ps.k.r1, ps.k.r2));
+        } else {
+          std::vector<uint32_t> radices;
+          for (uint32_t cur = L; cur > 1; cur /= radices.back()) radices.push_back(mix_next_radix(L, cur, cur == L));
+          buf->upload(ref_schedule_table<T>(L, radices, tile_twiddle));
+        }
         it = tables_.emplace(L, std::move(buf)).first;
       }
       ps.tw = it->second.get();
       if (ps.m > 1) {  // inter-pass twiddle W_size^{i*k}, two-level
-        const int lb = (ilog2(size) + 1) / 2;
-        ps.lo_bits = (uint32_t)lb;
-        std::vector<cpx<T>> lo((size_t)1 << lb), hi((size_t)(size >> lb) + 1);
-        for (size_t e = 0; e < lo.size(); ++e) { double re, im; unit_root(e, size, re, im); lo[e] = {(T)re, (T)im}; }
-        for (size_t h = 0; h < hi.size(); ++h) { double re, im; unit_root((uint64_t)h << lb, size, re, im); hi[h] = {(T)re, (T)im}; }
         ps.tw_lo.reset(new DevBuf()); ps.tw_hi.reset(new DevBuf());
-        ps.tw_lo->upload(lo); ps.tw_hi->upload(hi);
+        ps.lo_bits = upload_two_level<T>(size, *ps.tw_lo, *ps.tw_hi);
       }
       passes_.push_back(std::move(ps));
       s *= L; size /= L;
@@ -223,28 +204,20 @@ template <typename T> class TiledMixedEngine {
       a.swap_in = (p == 0) && inverse; a.swap_out = (p + 1 == np) && inverse;
       a.scale = (p + 1 == np) ? scale : 1.0;
       a.xcd_chunk = ps.xcd_chunk;
-      const cpx<T> w3 = ref_twiddle(1, 3), w8 = ref_twiddle(1, 8);
+      const cpx<T> w3 = tile_twiddle(1, 3), w8 = tile_twiddle(1, 8);
       a.w3re = w3.re; a.w3im = w3.im; a.w8re = w8.re; a.w8im = w8.im;
       const uint64_t grid = (uint64_t)batch * a.tiles_per_row * (ps.s == 1 ? 1 : ps.m);
-      if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-      PROF_BEGIN(prof, (int)p);
-#ifndef FOURIER_EMU
-      if (ps.rtc.fn) {  // a tile length compiled at run time: a module function
-        void* params[] = {&a};
-        HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)ps.rtc.fn, (unsigned)grid, 1, 1, ps.k.threads, 1, 1, 0, stream, params, nullptr));
-      } else
-#endif
-      {
-        FOURIER_LAUNCH(ps.k.fn, grid, ps.k.threads, ps.k.smem, stream, a);
-      }
-      PROF_END(prof);
+      // (ps.rtc: a tile length compiled at run time, its LDS declared statically)
+      launch(prof, (int)p, ps.k.fn, grid, ps.k.threads, ps.rtc.fn ? 0 : ps.k.smem, stream, a, ps.rtc);
       src = dst;
     }
   }
 
  private:
-  // twiddle.rs:7-19: theta = (index*2) as f64 * PI / size as f64; (cos, -sin) cast to T
-  static cpx<T> ref_twiddle(size_t index, size_t size) {
+  // twiddle.rs:7-19: theta = (index*2) as f64 * PI / size as f64; (cos, -sin) cast to T.  Not ref_twiddle (engine_host.h): a compiler
+  // that merges this cos and sin into one sincos() call (g++: the emulator build) gives other last bits in f64 -- 267 entries of the
+  // tables of 79 tile lengths -- and the tile passes keep the bits they have always had
+  static cpx<T> tile_twiddle(size_t index, size_t size) {
     const double theta = (double)(index * 2) * M_PI / (double)size;
     return {(T)std::cos(theta), (T)(-std::sin(theta))};
   }
@@ -317,14 +290,9 @@ template <typename T> class BluTiledEngine {
     k_out_ = get_regtile_kernel(Real<T>{}, l1, 3);
     if (!k_in_.fn || !k_conv_.fn || !k_out_.fn) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "no register-tile Bluestein kernels of these lengths");
     for (const TiledKernel* k : {&k_in_, &k_conv_, &k_out_}) raise_smem_limit((const void*)k->fn, k->smem);
-    tw1_.upload(stage_table(k_in_));
-    tw2_.upload(stage_table(k_conv_));
-    const int lb = (ilog2(m_) + 1) / 2;  // W_M^{i * k}, two-level (first forward pass and first inverse pass)
-    lo_bits_ = (uint32_t)lb;
-    std::vector<cpx<T>> lo((size_t)1 << lb), hi((size_t)(m_ >> lb) + 1);
-    for (size_t e = 0; e < lo.size(); ++e) { double re, im; unit_root(e, m_, re, im); lo[e] = {(T)re, (T)im}; }
-    for (size_t h = 0; h < hi.size(); ++h) { double re, im; unit_root((uint64_t)h << lb, m_, re, im); hi[h] = {(T)re, (T)im}; }
-    tw_lo_.upload(lo); tw_hi_.upload(hi);
+    tw1_.upload(product_table<T>(k_in_.L, k_in_.r1, k_in_.r2));  // W_L^{j2 * k1} as [k1 < r1][j2 < r2]
+    tw2_.upload(product_table<T>(k_conv_.L, k_conv_.r1, k_conv_.r2));
+    lo_bits_ = upload_two_level<T>(m_, tw_lo_, tw_hi_);  // W_M^{i * k} (first forward pass and first inverse pass)
     const uint64_t e = sizeof(cpx<T>);
     chunk_in_ = ((n_ * e) % 128 != 0 || (l2_ * e) % 128 != 0) ? FOURIER_TILE_CHUNK : FOURIER_TILE_CHUNK_ALIGNED;
     chunk_conv_ = ((m_ * e) % 128 != 0 || (l1_ * e) % 128 != 0) ? FOURIER_TILE_CHUNK : FOURIER_TILE_CHUNK_ALIGNED;
@@ -344,41 +312,25 @@ template <typename T> class BluTiledEngine {
       a.n = m_; a.scale = 1.0;
       a.blu_x = xtab; a.blu_w = wtab; a.blu_n = n_; a.blu_swap = inverse ? 1 : 0;
     };
-    auto launch = [&](const TiledKernel& k, uint64_t tiles, int slot) {
-      const uint64_t grid = (uint64_t)batch * tiles;
-      if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-      PROF_BEGIN(prof, slot);
-      FOURIER_LAUNCH(k.fn, grid, k.threads, k.smem, stream, a);
-      PROF_END(prof);
-    };
+    auto pass = [&](const TiledKernel& k, int slot) { launch(prof, slot, k.fn, (uint64_t)batch * a.tiles_per_row, k.threads, k.smem, stream, a); };
     // chirp-in: first pass of the forward transform, length L1 at s = 1, m = L2 columns
     base();
     a.in = in; a.out = work; a.tw = tw1_.p; a.s = 1; a.m = l2_;
     a.tiles_per_row = (l2_ + k_in_.cols - 1) / k_in_.cols; a.xcd_chunk = chunk_in_;
-    launch(k_in_, a.tiles_per_row, 0);
+    pass(k_in_, 0);
     // conv: last forward pass (length L2 at s = L1), (.) w, first inverse pass (length L2, m = L1)
     base();
     a.in = work; a.out = scratch; a.tw = tw2_.p; a.s = l1_; a.m = 1;
     a.tiles_per_row = (l1_ + k_conv_.cols - 1) / k_conv_.cols; a.xcd_chunk = chunk_conv_;
-    launch(k_conv_, a.tiles_per_row, 1);
+    pass(k_conv_, 1);
     // chirp-out: last pass of the inverse transform, length L1 at s = L2
     base();
     a.in = scratch; a.out = out; a.tw = tw1_.p; a.s = l2_; a.m = 1; a.swap_out = 1; a.scale = scale;
     a.tiles_per_row = (l2_ + k_out_.cols - 1) / k_out_.cols; a.xcd_chunk = chunk_out_;
-    launch(k_out_, a.tiles_per_row, 2);
+    pass(k_out_, 2);
   }
 
  private:
-  static std::vector<cpx<T>> stage_table(const TiledKernel& k) {  // W_L^{j2 * k1} as [k1 < r1][j2 < r2]
-    std::vector<cpx<T>> tw;
-    for (size_t k1 = 0; k1 < k.r1; ++k1)
-      for (size_t j2 = 0; j2 < k.r2; ++j2) {
-        double re, im;
-        unit_root(j2 * k1, k.L, re, im);
-        tw.push_back({(T)re, (T)im});
-      }
-    return tw;
-  }
   size_t n_;
   uint64_t m_;
   uint32_t l1_, l2_, lo_bits_ = 0, chunk_in_ = 0, chunk_conv_ = 0, chunk_out_ = 0;
@@ -419,11 +371,7 @@ template <typename T> class BluRegEngine {
       throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "no one-launch register kernel of this length");
     raise_smem_limit((const void*)k_.fn, k_.smem);
     std::vector<cpx<T>> tw;
-    auto root = [&](uint64_t e, uint64_t size) {
-      double re, im;
-      unit_root(e % size, size, re, im);
-      tw.push_back({(T)re, (T)im});
-    };
+    auto root = [&](uint64_t e, uint64_t size) { tw.push_back(fourier_hip::root<T>(e, size)); };
     const uint64_t r1 = k_.r1, r2 = k_.r2, r3 = k_.r3;
     if (r3 == 0) {  // [j2][k1]: W_M^{j2 * k1}
       for (uint64_t j2 = 0; j2 < r2; ++j2)
@@ -462,11 +410,7 @@ template <typename T> class BluRegEngine {
     std::memset(&a, 0, sizeof(a));
     a.in = in; a.out = out; a.chirp = xtab; a.w = wtab; a.tw = tw_.p;
     a.n = n_; a.batch = batch; a.swap = inverse ? 1 : 0; a.scale = scale;
-    const uint64_t grid = ((uint64_t)batch + k_.tpw - 1) / k_.tpw;
-    if (grid > 0x7fffffffull) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "grid too large; lower chunk_bytes");
-    PROF_BEGIN(prof, 0);
-    FOURIER_LAUNCH(k_.fn, grid, k_.threads, k_.smem, stream, a);
-    PROF_END(prof);
+    launch(prof, 0, k_.fn, ((uint64_t)batch + k_.tpw - 1) / k_.tpw, k_.threads, k_.smem, stream, a);
   }
 
  private:

@@ -57,6 +57,10 @@ template <typename T> static double code_scale(int code, T n) {
 
 // rows per chunk of a call of `batch` rows of `per` bytes such that a chunk stays within `cap` bytes (never less than one row)
 static inline size_t chunk_rows(size_t batch, size_t cap, size_t per) { return std::max<size_t>(1, std::min<size_t>(batch, cap / per)); }
+// f(b0, nb) for every chunk of the `batch` rows of a call, in order: nb = `chunk` rows from row b0 on, fewer in the last one
+template <typename F> static inline void for_chunks(size_t batch, size_t chunk, F&& f) {
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) f(b0, std::min(chunk, batch - b0));
+}
 // a scratch bound: `dflt`, or what the development switch `name` says (experiments library and emulator build only, read at create)
 static inline size_t scratch_bound(const char* name, size_t dflt) {
   const char* e = dev_env(name);

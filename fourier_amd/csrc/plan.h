@@ -215,18 +215,18 @@ template <typename T> class Plan : public HandleBase {
   // kernel "slots" in launch order, as reported by profile(): names for bench.py / rocprof matching
   std::string slot_names() const {
     std::string d;
+    auto passes = [&](const char* tag, size_t count) {  // "tag0,tag1,..." appended to d
+      for (size_t p = 0; p < count; ++p) d += std::string(d.empty() ? "" : ",") + tag + std::to_string(p);
+    };
     if (regf_) return "registers_one_launch";
     if (mix_) return "mixed_radix";
-    if (tiled_) { for (size_t p = 0; p < tiled_->num_passes(); ++p) d += std::string(d.empty() ? "" : ",") + "pass" + std::to_string(p); return d; }
-    if (gen_) { for (size_t p = 0; p < gen_->num_passes(); ++p) d += std::string(d.empty() ? "" : ",") + "pass" + std::to_string(p); return d; }
-    auto passes = [&](const char* tag) {
-      for (size_t p = 0; p < (blu_ ? eng_->num_passes() : eng_->hbm_round_trips()); ++p) d += std::string(d.empty() ? "" : ",") + tag + std::to_string(p);
-    };
+    if (tiled_) { passes("pass", tiled_->num_passes()); return d; }
+    if (gen_) { passes("pass", gen_->num_passes()); return d; }
     if (blur_) return "bluestein_one_launch";
     if (blut_) return "chirp_in_pass,conv_pass,chirp_out_pass";
-    if (!blu_) { passes("pass"); return d; }
+    if (!blu_) { passes("pass", eng_->hbm_round_trips()); return d; }
     if (small_fused_) return "bluestein_one_launch";
-    d = "blu_pre"; passes("fwd_pass"); passes("inv_pass"); d += ",blu_post";  // blu_pre/post stay empty when fused
+    d = "blu_pre"; passes("fwd_pass", eng_->num_passes()); passes("inv_pass", eng_->num_passes()); d += ",blu_post";  // blu_pre/post stay empty when fused
     if (fused_ && conv_) {  // the last forward pass and the first inverse pass are one launch (inv_pass0 stays empty)
       const std::string from = "fwd_pass" + std::to_string(eng_->num_passes() - 1);
       d.replace(d.find(from), from.size(), "conv_pass");
@@ -396,63 +396,49 @@ template <typename T> class Plan : public HandleBase {
   size_t prepare(size_t batch, bool in_place) const {
     if (mix_ || regf_ || batch == 0) return batch;
     if (tiled_) {  // one scratch of a chunk for in-place calls and three-pass plans
-      size_t chunk = batch;
-      if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, n_ * ELEM);
-      while (chunk > 1 && (double)chunk * (double)n_ / 8.0 > 2.0e9) chunk = (chunk + 1) / 2;
-      if (!(tiled_->needs_scratch(in_place) || force_scratch_)) return chunk;
-      for (;;) {
-        try { scratch_.ensure(chunk * n_ * ELEM); return chunk; }
-        catch (const EngineError& e) {
-          if (e.status != ::fourier::c::FOURIER_HIP_OUT_OF_MEMORY || chunk <= 1) throw;
-          (void)hipGetLastError();
-          chunk = (chunk + 1) / 2;
-        }
-      }
+      size_t chunk = first_chunk(batch, n_, 8.0);
+      if (tiled_->needs_scratch(in_place) || force_scratch_) reserve(chunk, [&](size_t c) { scratch_.ensure(c * n_ * ELEM); });
+      return chunk;
     }
-    if (gen_) {  // two scratch halves of one chunk each; chunked so that a launch stays below 2^31 workgroups
-      size_t chunk = batch;
-      if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, n_ * ELEM);
-      while (chunk > 1 && (double)chunk * (double)n_ / 256.0 > 2.0e9) chunk = (chunk + 1) / 2;
-      for (;;) {
-        try { scratch_.ensure(2 * chunk * n_ * ELEM); return chunk; }
-        catch (const EngineError& e) {
-          if (e.status != ::fourier::c::FOURIER_HIP_OUT_OF_MEMORY || chunk <= 1) throw;
-          (void)hipGetLastError();
-          chunk = (chunk + 1) / 2;
-        }
-      }
+    if (gen_) {  // two scratch halves of one chunk each
+      size_t chunk = first_chunk(batch, n_, 256.0);
+      reserve(chunk, [&](size_t c) { scratch_.ensure(2 * c * n_ * ELEM); });
+      return chunk;
     }
-    const size_t per = (blu_ ? m_ : n_) * ELEM;
-    size_t chunk = batch;
-    if (chunk_bytes_) chunk = chunk_rows(batch, chunk_bytes_, per);
-    // keep every launch's grid below 2^31 blocks
-    while (chunk > 1 && (double)chunk * (double)(blu_ ? m_ : n_) / 16.0 > 2.0e9) chunk = (chunk + 1) / 2;
-    // The plan's scratch (and the Bluestein work array) hold one chunk.  If the device cannot give that much -- an
-    // in-place call on a batch that fills most of the HBM -- fall back to smaller chunks instead of failing: chunks
-    // run back to back on the stream and the results are the same.
-    auto reserve = [&](auto&& alloc) {
-      for (;;) {
-        try { alloc(chunk); return; }
-        catch (const EngineError& e) {
-          if (e.status != ::fourier::c::FOURIER_HIP_OUT_OF_MEMORY || chunk <= 1) throw;
-          (void)hipGetLastError();  // the allocation failure is handled here
-          chunk = (chunk + 1) / 2;
-        }
-      }
-    };
+    size_t chunk = first_chunk(batch, blu_ ? m_ : n_, 16.0);
     if (!blu_) {
       if (pipe_chunk_) { eng_->reserve_pipeline(std::min(pipe_chunk_, batch), pipe_slots_); return batch; }
       if (eng_->l2fused_enabled()) { eng_->reserve_l2fused(chunk); return chunk; }
       const bool need = eng_->needs_scratch(in_place) || (force_scratch_ && eng_->num_passes() >= 2);
-      if (need) reserve([&](size_t c) { scratch_.ensure(c * n_ * ELEM); });
+      if (need) reserve(chunk, [&](size_t c) { scratch_.ensure(c * n_ * ELEM); });
       return chunk;
     }
     if (small_fused_ || blur_) return batch;  // whole chirp-z in one launch: no work array
-    reserve([&](size_t c) {
+    reserve(chunk, [&](size_t c) {
       work_.ensure(c * m_ * ELEM);
       if (blut_ || eng_->needs_scratch(true) || fused_) scratch_.ensure(c * m_ * ELEM);
     });
     return chunk;
+  }
+  // the chunk a call starts from: `batch` transforms of `points` elements within option "chunk_bytes", halved until a launch of one
+  // workgroup per `per_group` elements keeps its grid below 2^31 workgroups
+  size_t first_chunk(size_t batch, size_t points, double per_group) const {
+    size_t chunk = chunk_bytes_ ? chunk_rows(batch, chunk_bytes_, points * ELEM) : batch;
+    while (chunk > 1 && (double)chunk * (double)points / per_group > 2.0e9) chunk = (chunk + 1) / 2;
+    return chunk;
+  }
+  // The plan's scratch (and the Bluestein work array) hold one chunk.  If the device cannot give that much -- an
+  // in-place call on a batch that fills most of the HBM -- fall back to smaller chunks instead of failing: chunks
+  // run back to back on the stream and the results are the same.
+  template <typename F> static void reserve(size_t& chunk, F&& alloc) {
+    for (;;) {
+      try { alloc(chunk); return; }
+      catch (const EngineError& e) {
+        if (e.status != ::fourier::c::FOURIER_HIP_OUT_OF_MEMORY || chunk <= 1) throw;
+        (void)hipGetLastError();  // the allocation failure is handled here
+        chunk = (chunk + 1) / 2;
+      }
+    }
   }
   void reserve_for(size_t batch, bool in_place) const {
     DeviceGuard g(device_);
@@ -483,18 +469,13 @@ template <typename T> class Plan : public HandleBase {
     }
     const size_t chunk = prepare(batch, in_place);
 
+    cpx<T>* const scratch = (cpx<T>*)scratch_.p;
     if (tiled_) {
-      for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = std::min(chunk, batch - b0);
-        tiled_->run(in + b0 * n_, out + b0 * n_, (cpx<T>*)scratch_.p, nb, inverse, scale, stream, prof);
-      }
+      for_chunks(batch, chunk, [&](size_t b0, size_t nb) { tiled_->run(in + b0 * n_, out + b0 * n_, scratch, nb, inverse, scale, stream, prof); });
       return;
     }
     if (gen_) {
-      for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = std::min(chunk, batch - b0);
-        gen_->run(in + b0 * n_, out + b0 * n_, (cpx<T>*)scratch_.p, nb, inverse, scale, stream, prof);
-      }
+      for_chunks(batch, chunk, [&](size_t b0, size_t nb) { gen_->run(in + b0 * n_, out + b0 * n_, scratch, nb, inverse, scale, stream, prof); });
       return;
     }
     if (!blu_) {
@@ -502,11 +483,9 @@ template <typename T> class Plan : public HandleBase {
         eng_->run_pipelined(in, out, batch, pipe_chunk_, pipe_slots_, inverse, scale, stream, nxcd_, nxcd_last_, pipe_one_stream_);
         return;
       }
-      for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = std::min(chunk, batch - b0);
-        eng_->run(in + b0 * n_, out + b0 * n_, (cpx<T>*)scratch_.p, nb, inverse, scale, nullptr, force_scratch_, stream, prof, 0, nxcd_,
-                  typename Pow2Engine<T>::BluIO(), nxcd_last_);
-      }
+      for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        eng_->run(in + b0 * n_, out + b0 * n_, scratch, nb, inverse, scale, nullptr, force_scratch_, stream, prof, 0, nxcd_, BluIO(), nxcd_last_);
+      });
       return;
     }
     // Bluestein (bluesteins.rs:215-259): work = x.in (zero padded) ; FFT_M ; .w ; IFFT_M ; out = work.x.scale
@@ -520,64 +499,33 @@ template <typename T> class Plan : public HandleBase {
     }
     cpx<T>* work = (cpx<T>*)work_.p;
     if (blut_) {  // smooth M: three sweeps on register tiles (kernels_regtile.h)
-      for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = std::min(chunk, batch - b0);
-        blut_->run(in + b0 * n_, out + b0 * n_, work, (cpx<T>*)scratch_.p, nb, xtab_.p, wtab_.p, inverse, scale, stream, prof);
-      }
+      for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        blut_->run(in + b0 * n_, out + b0 * n_, work, scratch, nb, xtab_.p, wtab_.p, inverse, scale, stream, prof);
+      });
       return;
     }
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
-      BluArgs pre{in + b0 * n_, work, xtab_.p, (uint64_t)n_, (uint64_t)m_, (uint64_t)nb, inverse, 1.0};
-      const int np = (int)eng_->num_passes();
+    const int np = (int)eng_->num_passes();
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+      const cpx<T>* x = in + b0 * n_;
+      cpx<T>* y = out + b0 * n_;
       if (fused_ && conv_) {
         // three sweeps instead of four: first forward pass (chirp-in fused), the conv kernel (last forward pass,
         // (.) w, first inverse pass), last inverse pass (chirp-out fused); intermediates ping-pong work/scratch
-        typename Pow2Engine<T>::BluIO bin, bout;
-        bin.io = IO_BLU_IN; bin.xtab = xtab_.p; bin.n = n_; bin.swap = inverse;
-        if (chirp_compute_) { bin.p_tab = chirp_p_.p; bin.u_tab = chirp_u_.p; bin.tn_lo = tn_lo_.p; bin.tn_hi = tn_hi_.p; bin.tn_bits = tn_bits_; }
-        bout.io = IO_BLU_OUT; bout.xtab = xtab_.p; bout.n = n_; bout.swap = inverse;
-        const Pow2Engine<T>& inv = eng_inv_ ? *eng_inv_ : *eng_;
-        cpx<T>* bufs[2] = {work, (cpx<T>*)scratch_.p};
-        const cpx<T>* src = in + b0 * n_;
-        int cur = 0;
-        for (int p = 0; p + 1 < np; ++p) {
-          eng_->launch_pass((size_t)p, src, bufs[cur], nb, false, 1.0, stream, prof, 1 + p, nxcd_, p == 0 ? bin : typename Pow2Engine<T>::BluIO());
-          src = bufs[cur]; cur ^= 1;
-        }
-        eng_->launch_conv(src, bufs[cur], nb, wtab_.p, stream, prof, np, nxcd_);
-        src = bufs[cur]; cur ^= 1;
-        for (int p = 1; p < np; ++p) {
-          const bool last = (p + 1 == np);
-          cpx<T>* dst = last ? out + b0 * n_ : bufs[cur];
-          inv.launch_pass((size_t)p, src, dst, nb, true, last ? scale : 1.0, stream, prof, 1 + np + p, nxcd_,
-                          last ? bout : typename Pow2Engine<T>::BluIO());
-          src = dst; cur ^= 1;
-        }
-        continue;
-      }
-      if (fused_) {
+        three_sweeps(x, y, nb, work, scratch, blu_in(inverse), blu_out(inverse), wtab_.p, 0, 0, nxcd_, nxcd_, scale, stream, prof);
+      } else if (fused_) {
         // chirp multiply + zero pad fused into the forward inner FFT's first pass, chirp * scale fused into
         // the inverse inner FFT's last pass: no separate sweeps over the M-point work array
-        typename Pow2Engine<T>::BluIO bin, bout;
-        bin.io = IO_BLU_IN; bin.xtab = xtab_.p; bin.n = n_; bin.swap = inverse;
-        if (chirp_compute_) { bin.p_tab = chirp_p_.p; bin.u_tab = chirp_u_.p; bin.tn_lo = tn_lo_.p; bin.tn_hi = tn_hi_.p; bin.tn_bits = tn_bits_; }
-        bout.io = IO_BLU_OUT; bout.xtab = xtab_.p; bout.n = n_; bout.swap = inverse;
-        eng_->run(in + b0 * n_, work, (cpx<T>*)scratch_.p, nb, false, 1.0, (const cpx<T>*)wtab_.p, false, stream, prof, 1,
-                  nxcd_, bin);
-        eng_->run(work, out + b0 * n_, (cpx<T>*)scratch_.p, nb, true, scale, nullptr, false, stream, prof, 1 + np, nxcd_, bout);
-        continue;
+        eng_->run(x, work, scratch, nb, false, 1.0, (const cpx<T>*)wtab_.p, false, stream, prof, 1, nxcd_, blu_in(inverse));
+        eng_->run(work, y, scratch, nb, true, scale, nullptr, false, stream, prof, 1 + np, nxcd_, blu_out(inverse));
+      } else {
+        BluArgs pre{x, work, xtab_.p, (uint64_t)n_, (uint64_t)m_, (uint64_t)nb, inverse, 1.0};
+        launch(prof, 0, get_blu_kernel(Real<T>{}, 0), elementwise_grid(nb * m_), 256, 0, stream, pre);
+        eng_->run(work, work, scratch, nb, false, 1.0, (const cpx<T>*)wtab_.p, false, stream, prof, 1, nxcd_);
+        eng_->run(work, work, scratch, nb, true, 1.0, nullptr, false, stream, prof, 1 + np, nxcd_);
+        BluArgs post{work, y, xtab_.p, (uint64_t)n_, (uint64_t)m_, (uint64_t)nb, inverse, scale};
+        launch(prof, 1 + 2 * np, get_blu_kernel(Real<T>{}, 1), elementwise_grid(nb * n_), 256, 0, stream, post);
       }
-      PROF_BEGIN(prof, 0);
-      FOURIER_LAUNCH(get_blu_kernel(Real<T>{}, 0), elementwise_grid(nb * m_), 256, 0, stream, pre);
-      PROF_END(prof);
-      eng_->run(work, work, (cpx<T>*)scratch_.p, nb, false, 1.0, (const cpx<T>*)wtab_.p, false, stream, prof, 1, nxcd_);
-      eng_->run(work, work, (cpx<T>*)scratch_.p, nb, true, 1.0, nullptr, false, stream, prof, 1 + np, nxcd_);
-      BluArgs post{work, out + b0 * n_, xtab_.p, (uint64_t)n_, (uint64_t)m_, (uint64_t)nb, inverse, scale};
-      PROF_BEGIN(prof, 1 + 2 * np);
-      FOURIER_LAUNCH(get_blu_kernel(Real<T>{}, 1), elementwise_grid(nb * n_), 256, 0, stream, post);
-      PROF_END(prof);
-    }
+    });
   }
 
   // ---- the hook of the convolution handle (ConvPlan, conv_plan.h); exec() is not affected.  enable_conv_bank sets up and returns the
@@ -616,25 +564,10 @@ template <typename T> class Plan : public HandleBase {
       eng_->run_conv_small((const cpx<T>*)d_in, (cpx<T>*)d_out, batch, bank, (uint32_t)filters, (uint32_t)(first % filters), stream, nxcd_);
       return true;
     }
-    const int np = (int)eng_->num_passes();
-    const Pow2Engine<T>& inv = eng_inv_ ? *eng_inv_ : *eng_;
-    cpx<T>* bufs[2] = {(cpx<T>*)work_a, (cpx<T>*)work_b};
-    const cpx<T>* src = (const cpx<T>*)d_in;
-    int cur = 0;
-    for (int p = 0; p + 1 < np; ++p) {
-      eng_->launch_pass((size_t)p, src, bufs[cur], batch, false, 1.0, stream, nullptr, 0, nxcd_);
-      src = bufs[cur]; cur ^= 1;
-    }
     // (the conv kernel in the tile order every Bluestein plan runs it in, 8 XCDs and launch_conv's slicing -- not this plan's nxcd_, which at
     // f32 2^20 is the band walk of the plain passes, an order the conv kernel has never been measured or tested in)
-    eng_->launch_conv(src, bufs[cur], batch, bank, stream, nullptr, 0, 8, (uint32_t)filters, (uint32_t)(first % filters));
-    src = bufs[cur]; cur ^= 1;
-    for (int p = 1; p < np; ++p) {
-      const bool last = (p + 1 == np);
-      cpx<T>* dst = last ? (cpx<T>*)d_out : bufs[cur];
-      inv.launch_pass((size_t)p, src, dst, batch, true, 1.0, stream, nullptr, 0, (last && nxcd_last_) ? nxcd_last_ : nxcd_);
-      src = dst; cur ^= 1;
-    }
+    three_sweeps((const cpx<T>*)d_in, (cpx<T>*)d_out, batch, (cpx<T>*)work_a, (cpx<T>*)work_b, BluIO(), BluIO(), bank, (uint32_t)filters,
+                 (uint32_t)(first % filters), 8, nxcd_last_ ? nxcd_last_ : nxcd_, 1.0, stream, nullptr);
     return true;
   }
 
@@ -721,6 +654,44 @@ template <typename T> class Plan : public HandleBase {
   static constexpr size_t NSLOTS = 4;  // chunks in flight: copy-in, H2D, kernels, D2H + copy-out each take about one chunk time
 
  private:
+  using BluIO = typename Pow2Engine<T>::BluIO;
+  // the chirp I/O of a fused Bluestein plan's first forward pass (x . chirp, zero padded) and last inverse pass (. chirp . scale)
+  BluIO blu_in(bool inverse) const {
+    BluIO b;
+    b.io = IO_BLU_IN; b.xtab = xtab_.p; b.n = n_; b.swap = inverse;
+    if (chirp_compute_) { b.p_tab = chirp_p_.p; b.u_tab = chirp_u_.p; b.tn_lo = tn_lo_.p; b.tn_hi = tn_hi_.p; b.tn_bits = tn_bits_; }
+    return b;
+  }
+  BluIO blu_out(bool inverse) const {
+    BluIO b;
+    b.io = IO_BLU_OUT; b.xtab = xtab_.p; b.n = n_; b.swap = inverse;
+    return b;
+  }
+  // A forward transform, a product with a table in spectrum order and an inverse transform in three sweeps of memory: forward passes
+  // 0 ... np-2 (the first reads `in` through `first`), launch_conv (last forward pass, (.) table, first inverse pass), inverse passes
+  // 1 ... np-1 (the last writes `out` through `last`, times `scale`, in the tile order nxcd_last); intermediates ping-pong buf_a / buf_b.
+  // filters != 0: `table` is a bank, row b multiplies by table (first_row + b) mod filters.  Timed in slots 1 + p, np, 1 + np + p.
+  void three_sweeps(const cpx<T>* in, cpx<T>* out, size_t nb, cpx<T>* buf_a, cpx<T>* buf_b, const BluIO& first, const BluIO& last,
+                    const void* table, uint32_t filters, uint32_t first_row, unsigned nxcd_conv, unsigned nxcd_last, double scale,
+                    hipStream_t stream, Profiler* prof) const {
+    const int np = (int)eng_->num_passes();
+    const Pow2Engine<T>& inv = eng_inv_ ? *eng_inv_ : *eng_;
+    cpx<T>* bufs[2] = {buf_a, buf_b};
+    const cpx<T>* src = in;
+    int cur = 0;
+    for (int p = 0; p + 1 < np; ++p) {
+      eng_->launch_pass((size_t)p, src, bufs[cur], nb, false, 1.0, stream, prof, 1 + p, nxcd_, p == 0 ? first : BluIO());
+      src = bufs[cur]; cur ^= 1;
+    }
+    eng_->launch_conv(src, bufs[cur], nb, table, stream, prof, np, nxcd_conv, filters, first_row);
+    src = bufs[cur]; cur ^= 1;
+    for (int p = 1; p < np; ++p) {
+      const bool end = (p + 1 == np);
+      cpx<T>* dst = end ? out : bufs[cur];
+      inv.launch_pass((size_t)p, src, dst, nb, true, end ? scale : 1.0, stream, prof, 1 + np + p, end ? nxcd_last : nxcd_, end ? last : BluIO());
+      src = dst; cur ^= 1;
+    }
+  }
   // option "bluestein_smooth_m" (and "bluestein_fusion" = 0 on the register route): the Bluestein route chosen again under another rule
   void rebuild_bluestein(int mode) {
     HIP_CHECK(hipDeviceSynchronize());
@@ -798,23 +769,12 @@ template <typename T> class Plan : public HandleBase {
       std::vector<cpx<T>> pt(rows), ut(cn);
       for (uint64_t r = 0; r < rows; ++r) {
         const unsigned __int128 k = (unsigned __int128)r * cn;
-        double re, im;
-        unit_root((uint64_t)((k * k) % two_n), two_n, re, im);
-        pt[r] = {(T)re, (T)im};
+        pt[r] = root<T>((uint64_t)((k * k) % two_n), two_n);
       }
-      for (uint64_t b = 0; b < cn; ++b) {
-        double re, im;
-        unit_root((uint64_t)(((unsigned __int128)b * b) % two_n), two_n, re, im);
-        ut[b] = {(T)re, (T)im};
-      }
+      for (uint64_t b = 0; b < cn; ++b) ut[b] = root<T>((uint64_t)(((unsigned __int128)b * b) % two_n), two_n);
       chirp_p_.upload(pt);
       chirp_u_.upload(ut);
-      tn_bits_ = (uint32_t)((ilog2(n_) + 1) / 2);
-      std::vector<cpx<T>> lo((size_t)1 << tn_bits_), hi((size_t)(n_ >> tn_bits_) + 1);
-      for (size_t e = 0; e < lo.size(); ++e) { double re, im; unit_root(e, n_, re, im); lo[e] = {(T)re, (T)im}; }
-      for (size_t h = 0; h < hi.size(); ++h) { double re, im; unit_root((uint64_t)h << tn_bits_, n_, re, im); hi[h] = {(T)re, (T)im}; }
-      tn_lo_.upload(lo);
-      tn_hi_.upload(hi);
+      tn_bits_ = upload_two_level<T>(n_, tn_lo_, tn_hi_);  // W_n^e
       // Default: only where it pays.  Measured (profiles/r03_s7_chirp_compute_ab.jsonl): C4 (N = 999983, first pass of length
       // 2048 on 8-column tiles) 2.76-2.85 vs 2.92-3.08 ms per 512, f64 2.61 vs 2.88; N = 40000 / 65537 (the 0.3-0.5 MB table
       // is L2-resident anyway) and N = 2200000 (first pass of length 256: 32-column tiles, eight times the per-tile table

@@ -69,8 +69,7 @@ template <typename T> class RealPlan : public HandleBase {
     const T* in = (const T*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
       if (even_) {
         inner_->exec(in + b0 * n_, work, nb, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
         sweep(REAL_POST, work, out + b0 * (h_ + 1), nb, scale, stream);
@@ -79,7 +78,7 @@ template <typename T> class RealPlan : public HandleBase {
         inner_->exec(work, work, nb, code, stream);
         odd_sweep(REAL_NARROW, work, out + b0 * (h_ + 1), nb, stream);
       }
-    }
+    });
   }
 
   void inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
@@ -97,8 +96,7 @@ template <typename T> class RealPlan : public HandleBase {
     const cpx<T>* in = (const cpx<T>*)d_in;
     T* out = (T*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
       if (even_) {
         sweep(REAL_PRE, in + b0 * (h_ + 1), work, nb, fac, stream);
         inner_->exec(work, out + b0 * n_, nb, ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT, stream);
@@ -107,7 +105,7 @@ template <typename T> class RealPlan : public HandleBase {
         inner_->exec(work, work, nb, code, stream);
         odd_sweep(REAL_PART, work, out + b0 * n_, nb, stream);
       }
-    }
+    });
   }
 
  private:

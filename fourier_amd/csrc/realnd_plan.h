@@ -101,8 +101,7 @@ template <typename T> class RealNdPlan : public HandleBase {
     cpx<T>* out = (cpx<T>*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
     const size_t xi = rows_ * (h_ + 1);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
       if (packed_) {
         row_->exec(in + b0 * rows_ * w_, work, nb * rows_, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
         axes(work, work, nb, h_, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
@@ -111,7 +110,7 @@ template <typename T> class RealNdPlan : public HandleBase {
         rows1d_->run_forward(in + b0 * rows_ * w_, out + b0 * xi, nb * rows_, code, stream);
         axes(out + b0 * xi, out + b0 * xi, nb, h_ + 1, code, stream);
       }
-    }
+    });
   }
 
   void inverse(const void* d_in, void* d_out, size_t batch, int code, hipStream_t stream) const {
@@ -125,8 +124,7 @@ template <typename T> class RealNdPlan : public HandleBase {
     T* out = (T*)d_out;
     cpx<T>* work = (cpx<T>*)scratch_.p;
     const size_t xi = rows_ * (h_ + 1);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-      const size_t nb = std::min(chunk, batch - b0);
+    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
       if (packed_) {
         // the code's scale over P = W x R: the unscaled inverses of Z return P/2 times what the sweep wrote, and the sweep's S +- iT
         // carry a factor 2 (RealPlan::run_inverse with N = P)
@@ -137,7 +135,7 @@ template <typename T> class RealNdPlan : public HandleBase {
         axes(in + b0 * xi, work, nb, h_ + 1, code, stream);
         rows1d_->run_inverse(work, out + b0 * rows_ * w_, nb * rows_, code, stream);
       }
-    }
+    });
   }
 
  private:
