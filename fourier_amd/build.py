@@ -100,6 +100,15 @@ def deps_of(obj):
     return files or None
 
 
+def compile_jobs():
+    """Compilations side by side: MAX_JOBS or CMAKE_BUILD_PARALLEL_LEVEL where set (a shared machine reports more CPUs than a job may use), else every CPU."""
+    for var in ("MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        v = os.environ.get(var, "")
+        if v.isdigit() and int(v) > 0:
+            return int(v)
+    return max(1, os.cpu_count() or 1)
+
+
 def compile_objects(objdir=OBJDIR, extra=(), force=False, groups=None, verbose=False):
     """Compiles every translation unit whose object is older than one of the files it was built from (its source and the
     headers it includes, from the compiler's own dependency list; every header when that list is missing) -- or all with
@@ -127,7 +136,7 @@ def compile_objects(objdir=OBJDIR, extra=(), force=False, groups=None, verbose=F
         return job[0], p.returncode, p.stderr, time.time() - t0
 
     if jobs:
-        with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, os.cpu_count() or 1)) as ex:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=compile_jobs()) as ex:
             for name, rc, err, dt in ex.map(run, jobs):
                 if verbose or rc:
                     sys.stderr.write(f"[build] {name}: {dt:.1f} s rc={rc}\n")

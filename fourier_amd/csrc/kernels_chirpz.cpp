@@ -5,7 +5,7 @@
 // of a first menu of 23 that beat the power-of-two one-launch kernels -- 1728 ... 2048, 3375 ... 4096 against 2048 / 4096 and every M of 4500 ... 8000
 // (stages of 20 points, one workgroup per compute unit) against 8192 are level or slower, profiles/r06_s46_chirpz_reg3_ab.jsonl).  Compiled once per precision and shard: -DFOURIER_TU_REAL=float / double
 // -DFOURIER_TILED_SHARD=i (fourier_amd/build.py, packaging/CMakeLists.txt).
-#include "engine_common.h"
+#include "regstage_host.h"
 #include "kernels_chirpz.h"
 
 namespace fourier_hip {
@@ -16,19 +16,11 @@ template <typename T, uint32_t R1, uint32_t R2> static ChirpzKernel make_chirpz(
   if constexpr (R1 > 32 && sizeof(T) == 8) {
     return ChirpzKernel();  // (f64: a stage of more than 32 points spills, profiles/r06_s42_1000_point_tiles_f64.jsonl)
   } else {
-    using C = ChirpzRegCfg<T, R1, R2>;
-    ChirpzKernel k;
-    k.fn = &chirpz_reg_kernel<T, R1, R2>;
-    k.m = C::M; k.r1 = R1; k.r2 = R2; k.tpw = C::TPW; k.smem = C::SMEM;
-    return k;
+    return regstage_kernel_record<ChirpzRegCfg<T, R1, R2>, R1, R2, 0>(&chirpz_reg_kernel<T, R1, R2>);
   }
 }
 template <typename T, uint32_t R1, uint32_t R2, uint32_t R3> static ChirpzKernel make_chirpz3() {
-  using C = Chirpz3Cfg<T, R1, R2, R3>;
-  ChirpzKernel k;
-  k.fn = &chirpz_reg3_kernel<T, R1, R2, R3>;
-  k.m = C::M; k.r1 = R1; k.r2 = R2; k.r3 = R3; k.tpw = C::NV; k.threads = C::NT; k.smem = C::SMEM;
-  return k;
+  return regstage_kernel_record<Chirpz3Cfg<T, R1, R2, R3>, R1, R2, R3>(&chirpz_reg3_kernel<T, R1, R2, R3>);
 }
 #define FOURIER_CHIRPZ(A, B) case (A) * (B): return make_chirpz<T, A, B>();
 #define FOURIER_CHIRPZ3(A, B, C) case (A) * (B) * (C): return make_chirpz3<T, A, B, C>();

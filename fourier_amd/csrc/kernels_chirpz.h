@@ -19,47 +19,15 @@
 // a v_pk_add / v_pk_mul / v_pk_fma_f32): the scalar f32 kernels spent 78 - 86 % of their SIMD cycles issuing VALU work at 0.29 - 0.34 of the HBM
 // peak (profiles/r06_s44_sq_chirpz_reg.json); the two transforms share every table load, every address and every 16-byte LDS access.
 #pragma once
-#include "kernels_regtile.h"
+#include "kernels_regstage.h"  // Pk2, LaneVal, the launch-bound rule, LDS put / get / exchange, chirpz_table_product
 
 namespace fourier_hip {
 
-// two f32 values, one per transform of the lane: arithmetic on both at once
-typedef float v2f_t __attribute__((vector_size(8)));
-struct Pk2 {
-  v2f_t v;
-  Pk2() = default;
-  __device__ __forceinline__ explicit Pk2(double s) : v{(float)s, (float)s} {}
-  __device__ __forceinline__ Pk2(v2f_t w) : v(w) {}
-};
-__device__ __forceinline__ Pk2 operator+(Pk2 a, Pk2 b) { return Pk2(a.v + b.v); }
-__device__ __forceinline__ Pk2 operator-(Pk2 a, Pk2 b) { return Pk2(a.v - b.v); }
-__device__ __forceinline__ Pk2 operator*(Pk2 a, Pk2 b) { return Pk2(a.v * b.v); }
-__device__ __forceinline__ Pk2 operator-(Pk2 a) { return Pk2(-a.v); }
-__device__ __forceinline__ Pk2 operator*(Pk2 a, float s) { return Pk2(a.v * v2f_t{s, s}); }
-// lane value type P over memory type T: T itself (one transform per lane) or Pk2 over float (two)
-template <typename P, typename T> struct LaneVal {
-  static constexpr uint32_t NV = 1;
-  static __device__ __forceinline__ P make(const T* s) { return s[0]; }
-  static __device__ __forceinline__ T get(P p, uint32_t) { return p; }
-};
-template <> struct LaneVal<Pk2, float> {
-  static constexpr uint32_t NV = 2;
-  static __device__ __forceinline__ Pk2 make(const float* s) { return Pk2(v2f_t{s[0], s[1]}); }
-  static __device__ __forceinline__ float get(Pk2 p, uint32_t v) { return p.v[v]; }
-};
-// a lane value times a table entry (one per lane, shared by the lane's transforms)
-template <typename P, typename T> __device__ __forceinline__ cpx<P> cmul_tab(cpx<P> a, cpx<T> w) {
-  return {a.re * w.re - a.im * w.im, a.re * w.im + a.im * w.re};
-}
-template <bool B, typename X, typename Y> struct ChirpzSelect { typedef X type; };
-template <typename X, typename Y> struct ChirpzSelect<false, X, Y> { typedef Y type; };
-
-template <typename T, uint32_t R1, uint32_t R2> struct ChirpzRegCfg {
+template <typename T, uint32_t R1, uint32_t R2> struct ChirpzRegCfg : RegStageLane<T> {
   static_assert(R1 >= R2 && R1 <= 64, "chirpz_reg_kernel: split");
   // f32: two transforms per lane on packed arithmetic -- 1.2 ... 1.45 x one transform per lane on scalar arithmetic at every M (profiles/r06_s45_chirpz_reg_ab.jsonl)
-  static constexpr bool VEC2 = sizeof(T) == 4;
-  using P = typename ChirpzSelect<VEC2, Pk2, T>::type;
-  static constexpr uint32_t NV = VEC2 ? 2u : 1u;
+  using typename RegStageLane<T>::P;
+  using RegStageLane<T>::NV;
   static constexpr uint32_t M = R1 * R2, GPW = 64 / R1, TPW = GPW * NV;  // lane groups and transforms per wave
   // exchange planes: [k1 < R1][j2 < R2] then [k1'' < R2][k1 < R1], the inner pitch odd (a reader's lanes walk the planes)
   static constexpr uint32_t P1 = R2 | 1u, P2 = R1 | 1u;
@@ -67,10 +35,8 @@ template <typename T, uint32_t R1, uint32_t R2> struct ChirpzRegCfg {
   static constexpr size_t SMEM = (size_t)GPW * XE * sizeof(cpx<P>);
   static constexpr uint32_t HALF = M / 2 + 1;  // 2N <= M + 1: user positions stop below this
   static constexpr uint32_t NROW = (HALF + R2 - 1) / R2;  // rows j1 (positions q + R2*j1) that can hold user data
-  // waves per SIMD the register allocation aims at: what the LDS lets a compute unit hold (160 KiB, four SIMDs), at most CAP
-  static constexpr uint32_t LDS_WAVES = (uint32_t)((160u * 1024u) / SMEM) / 4u;
   static constexpr uint32_t CAP = R1 <= 16 ? 4u : 2u;  // (no bound, or four everywhere: within 2 %, r06_s45)
-  static constexpr uint32_t MINW = LDS_WAVES < 1u ? 1u : (LDS_WAVES < CAP ? LDS_WAVES : CAP);
+  static constexpr uint32_t MINW = regstage_min_waves(SMEM, 1u, CAP);  // a workgroup is one wave
 };
 
 template <typename T, uint32_t R1, uint32_t R2>
@@ -79,7 +45,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
   using P = typename C::P;
   using LV = LaneVal<P, T>;
   constexpr uint32_t GPW = C::GPW, TPW = C::TPW, NV = C::NV, P1 = C::P1, P2 = C::P2, XE = C::XE, NROW = C::NROW;
-  constexpr uint32_t EB = (uint32_t)sizeof(cpx<T>), XB = (uint32_t)sizeof(cpx<P>), OOB = 0xfffffff0u;
+  constexpr uint32_t EB = (uint32_t)sizeof(cpx<T>), OOB = 0xfffffff0u;
   // the chirp values of stage A stay in registers for the output: f32 (two registers each; loaded again: -2 ... 8 %) and the short f64 stages
   // (+3 ... 8 % up to 14 x 12; 14 x 14 and longer lose up to 20 % to the 4 registers each) -- r06_s45
   constexpr bool KEEP = sizeof(T) == 4 || R1 * R2 <= 168;
@@ -128,12 +94,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
       }
     }
     dft_any<P, (int)R1>(x);
-#pragma unroll
-    for (uint32_t k1 = 0; k1 < R1; ++k1) {
-      cpx<P>* p = xb + k1 * P1 + q;
-      LDS_NOTE(p, XB, true, 320);
-      *p = x[k1];
-    }
+    regstage_put<R1>(xb, x, [&](uint32_t k1) { return k1 * P1 + q; }, 320);
   }
   // ---- stage B, (.) w, swap, stage A' of the inverse transform.  Three table products (the lane's R2 twiddles, its R2 entries of w, the
   // twiddles again), their loads in batches of TB, each batch issued one batch ahead of its use -- the first one before the barrier, the
@@ -153,12 +114,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
   __syncthreads();
   cpx<P> y[R2];
   if (active) {
-#pragma unroll
-    for (uint32_t j2 = 0; j2 < R2; ++j2) {
-      const cpx<P>* p = xb + q * P1 + j2;
-      LDS_NOTE(p, XB, false, 321);
-      y[j2] = *p;
-    }
+    regstage_get<R2>(xb, y, [&](uint32_t j2) { return q * P1 + j2; }, 321);
 #pragma unroll
     for (uint32_t g = 0; g < 3 * NBATCH; ++g) {
       if (g + 1 < 3 * NBATCH) load_batch(g + 1);
@@ -179,12 +135,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
   }
   __syncthreads();  // every lane has read its stage-B inputs
   if (active) {
-#pragma unroll
-    for (uint32_t k = 0; k < R2; ++k) {
-      cpx<P>* p = xb + k * P2 + q;
-      LDS_NOTE(p, XB, true, 322);
-      *p = y[k];
-    }
+    regstage_put<R2>(xb, y, [&](uint32_t k) { return k * P2 + q; }, 322);
   }
   __syncthreads();
 
@@ -195,12 +146,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
 #pragma unroll
       for (uint32_t j1 = 0; j1 < NROW; ++j1) ch[j1] = buf_load_elem<T>(rc, (q + R2 * j1) * EB);
     }
-#pragma unroll
-    for (uint32_t k1 = 0; k1 < R1; ++k1) {
-      const cpx<P>* p = xb + q * P2 + k1;
-      LDS_NOTE(p, XB, false, 323);
-      z[k1] = *p;
-    }
+    regstage_get<R1>(xb, z, [&](uint32_t k1) { return q * P2 + k1; }, 323);
     dft_any<P, (int)R1>(z);
     const T scale = (T)a.scale;
 #pragma unroll
@@ -222,16 +168,10 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) chirpz_re
 // Y[k1 + R1*k2 + R1R2*k3].  The inverse takes the split the other way round, as above: a = k1 + R1*k2, DFT_R3 over k3 -> c3 on the same lanes;
 // W_M^{a*c3}; DFT_R2 over k2 -> c2; W_{R1R2}^{k1*c2}; DFT_R1 over k1 -> c1: output c3 + R3*c2 + R2R3*c1 -- the positions stage A loaded.
 // Lanes: A / A' m (< R2R3), B k1*R3 + j3, C / C' a = k1 + R1*k2, B' c3*R1 + k1.  Four LDS exchanges [row][lane of the reader]: a reader's lanes are
-// contiguous, a writer's lanes either run contiguously with the rows a multiple of 16 units + the run length apart, or walk an odd row pitch.
-constexpr uint32_t chirpz3_pitch_runs(uint32_t lanes, uint32_t run) {  // >= lanes, = run (mod 16)
-  uint32_t p = lanes;
-  while (p % 16u != run % 16u) ++p;
-  return p;
-}
-template <typename T, uint32_t R1, uint32_t R2, uint32_t R3, bool PAIR = true> struct Chirpz3Cfg {
-  static constexpr bool VEC2 = sizeof(T) == 4 && PAIR;  // (PAIR = false: kernels_regfft.h, one f32 transform per workgroup)
-  using P = typename ChirpzSelect<VEC2, Pk2, T>::type;
-  static constexpr uint32_t NV = VEC2 ? 2u : 1u;
+// contiguous, a writer's lanes either run contiguously with the rows a multiple of 16 units + the run length apart (chirpz3_pitch_runs), or walk
+// an odd row pitch.
+template <typename T, uint32_t R1, uint32_t R2, uint32_t R3, bool PAIR = true> struct Chirpz3Cfg : RegStageLane<T, PAIR> {  // (PAIR = false: kernels_regfft.h, one f32 transform per workgroup)
+  using typename RegStageLane<T, PAIR>::P;
   static constexpr uint32_t M = R1 * R2 * R3, LA = R2 * R3, LB = R1 * R3, LC = R1 * R2;  // lanes of the stages
   static constexpr uint32_t LMAX = LA > LB ? (LA > LC ? LA : LC) : (LB > LC ? LB : LC);
   static constexpr uint32_t NT = (LMAX + 63u) / 64u * 64u;
@@ -243,34 +183,8 @@ template <typename T, uint32_t R1, uint32_t R2, uint32_t R3, bool PAIR = true> s
   static constexpr uint32_t XE = X12 > X34 ? X12 : X34;
   static constexpr size_t SMEM = (size_t)XE * sizeof(cpx<P>);
   static constexpr uint32_t HALF = M / 2 + 1, NROW = (HALF + LA - 1) / LA;  // rows j1 (positions m + R2R3*j1) that can hold user data
-  static constexpr uint32_t LDS_WG = (uint32_t)((160u * 1024u) / SMEM);
-  static constexpr uint32_t WAVES = LDS_WG * (NT / 64u) / 4u;  // per SIMD, as far as the LDS goes
-  static constexpr uint32_t MINW = WAVES < 1u ? 1u : (WAVES > 3u ? 3u : WAVES);
+  static constexpr uint32_t MINW = regstage_min_waves(SMEM, NT / 64u, 3u);
 };
-// y[r] *= tab[r * stride] for first <= r < R (swap: re <-> im afterwards), the loads in batches of TB, each issued one batch ahead of its use
-template <typename P, typename T, uint32_t R, uint32_t TB> __device__ __forceinline__ void chirpz_table_product(cpx<P>* y, const cpx<T>* tab, uint32_t stride, bool swap) {
-  constexpr uint32_t NB = (R + TB - 1) / TB;
-  cpx<T> t[2][TB];
-#pragma unroll
-  for (uint32_t i = 0; i < TB; ++i)
-    if (i < R) t[0][i] = tab[i * stride];
-#pragma unroll
-  for (uint32_t b = 0; b < NB; ++b) {
-    if (b + 1 < NB) {
-#pragma unroll
-      for (uint32_t i = 0; i < TB; ++i)
-        if ((b + 1) * TB + i < R) t[(b + 1) & 1u][i] = tab[((b + 1) * TB + i) * stride];
-    }
-    FOURIER_SCHED_FENCE();
-#pragma unroll
-    for (uint32_t i = 0; i < TB; ++i)
-      if (b * TB + i < R) {
-        const cpx<P> z = cmul_tab(y[b * TB + i], t[b & 1u][i]);
-        y[b * TB + i] = swap ? cpx<P>{z.im, z.re} : z;
-      }
-    FOURIER_SCHED_FENCE();
-  }
-}
 
 template <typename T, uint32_t R1, uint32_t R2, uint32_t R3>
 __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T, R1, R2, R3>::MINW)) chirpz_reg3_kernel(ChirpzArgs a) {
@@ -293,6 +207,10 @@ __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T
   const cpx<T>* t4 = t3 + (size_t)R3 * LC;    // [c2 < R2][k1 < R1]: W_{R1R2}^{k1 * c2}
   const cpx<T>* wt = (const cpx<T>*)a.w;
 
+  // (The four readers, sites 331 / 333 / 335 / 337, and the writer 332 go through regstage_get / regstage_put; the writers 330, 334 and 336 stay
+  // written out.  Compared on the device assembly: 330 or 334 alone -- the writers with a three-term index -- make hipcc fuse the other product
+  // of the table multiplies, a change of rounding; 332 or 336 with the four readers is neutral, both together are not.  That is how the
+  // compiler's operand order falls, not a property of the helpers: compare the assembly again before moving a site.)
   // ---- stage A: lane m = t
   if (t < LA) {
     cpx<P> x[R1];
@@ -331,12 +249,7 @@ __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T
   // ---- stage B: lane k1*R3 + j3
   cpx<P> y[R2];
   if (t < LB) {
-#pragma unroll
-    for (uint32_t j2 = 0; j2 < R2; ++j2) {
-      const cpx<P>* p = xb + j2 * S1 + t;
-      LDS_NOTE(p, XB, false, 331);
-      y[j2] = *p;
-    }
+    regstage_get<R2>(xb, y, [&](uint32_t j2) { return j2 * S1 + t; }, 331);
     chirpz_table_product<P, T, R2, TB>(y, t1 + t, LB, false);
     dft_any<P, (int)R2>(y);
     FOURIER_SCHED_FENCE();
@@ -345,23 +258,13 @@ __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T
   __syncthreads();  // exchange 1 is read
   if (t < LB) {
     const uint32_t k1 = t / R3, j3 = t - k1 * R3;
-#pragma unroll
-    for (uint32_t k2 = 0; k2 < R2; ++k2) {
-      cpx<P>* p = xb + j3 * S2 + k1 + R1 * k2;
-      LDS_NOTE(p, XB, true, 332);
-      *p = y[k2];
-    }
+    regstage_put<R2>(xb, y, [&](uint32_t k2) { return j3 * S2 + k1 + R1 * k2; }, 332);
   }
   __syncthreads();
   // ---- stage C, (.) w, swap, stage C': lane a = k1 + R1*k2
   cpx<P> z[R3];
   if (t < LC) {
-#pragma unroll
-    for (uint32_t j3 = 0; j3 < R3; ++j3) {
-      const cpx<P>* p = xb + j3 * S2 + t;
-      LDS_NOTE(p, XB, false, 333);
-      z[j3] = *p;
-    }
+    regstage_get<R3>(xb, z, [&](uint32_t j3) { return j3 * S2 + t; }, 333);
     dft_any<P, (int)R3>(z);  // z[k3] = Y[a + R1R2 * k3]
     FOURIER_SCHED_FENCE();
     chirpz_table_product<P, T, R3, TB>(z, wt + t, LC, true);  // (.) w, swap for the inverse transform (bluesteins.rs:236-239)
@@ -382,12 +285,7 @@ __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T
   __syncthreads();
   // ---- stage B': lane c3*R1 + k1
   if (t < LB) {
-#pragma unroll
-    for (uint32_t k2 = 0; k2 < R2; ++k2) {
-      const cpx<P>* p = xb + k2 * S3 + t;
-      LDS_NOTE(p, XB, false, 335);
-      y[k2] = *p;
-    }
+    regstage_get<R2>(xb, y, [&](uint32_t k2) { return k2 * S3 + t; }, 335);
     dft_any<P, (int)R2>(y);  // y[c2]
     FOURIER_SCHED_FENCE();
     chirpz_table_product<P, T, R2, TB>(y, t4 + t % R1, R1, false);
@@ -409,12 +307,7 @@ __global__ void __launch_bounds__((Chirpz3Cfg<T, R1, R2, R3>::NT), (Chirpz3Cfg<T
     cpx<T> ch[NROW];
 #pragma unroll
     for (uint32_t j1 = 0; j1 < NROW; ++j1) ch[j1] = buf_load_elem<T>(rc, (t + LA * j1) * EB);
-#pragma unroll
-    for (uint32_t k1 = 0; k1 < R1; ++k1) {
-      const cpx<P>* p = xb + k1 * S4 + t;
-      LDS_NOTE(p, XB, false, 337);
-      v1[k1] = *p;
-    }
+    regstage_get<R1>(xb, v1, [&](uint32_t k1) { return k1 * S4 + t; }, 337);
     dft_any<P, (int)R1>(v1);
     const T scale = (T)a.scale;
 #pragma unroll

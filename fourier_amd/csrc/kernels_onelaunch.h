@@ -258,6 +258,27 @@ __global__ void __launch_bounds__((L / 16) * CG, FOURIER_MIN_WAVES((L / 16) * CG
   }
 }
 
+// XCD-contiguous order of the transforms: with nxcd > 1 the workgroups an XCD receives (every nxcd-th index) take one contiguous range of transforms
+__device__ __forceinline__ uint64_t onelaunch_block(const PassArgs& a) {
+  uint64_t blk = blockIdx.x;
+  if (a.nxcd > 1) {
+    const uint64_t nwg = gridDim.x, nx = a.nxcd, xcd = blk % nx, q = nwg / nx, r = nwg % nx;
+    blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blk / nx;
+  }
+  return blk;
+}
+// x[v][r] (register r: X[k1 + L1*k2], k2 = th2 + Q2*r) times the table behind rw, then re <-> im: the inverse transform's leading swap
+template <typename T, int L1, int Q2, int VEC> __device__ __forceinline__ void onelaunch_times_table_swap(cpx<T> (&x)[VEC][16], BufRsrc rw, uint32_t woff) {
+  units_batched<T, 8>([&](int r) { return buf_load_unit<T>(rw, woff, (uint32_t)((Q2 * r) * L1 * sizeof(cpx<T>))); },
+                      [&](int r, const Unit16<T>& u) {
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                          const cpx<T> y = cmul(x[v][r], cpx<T>{u.a[2 * v], u.a[2 * v + 1]});
+                          x[v][r] = {y.im, y.re};
+                        }
+                      });
+}
+
 #define FOURIER_TWOLEVEL_NT(T, L1, L2) ((L1 / 16) * (L2 / (16 / (2 * (int)sizeof(T)))))
 
 template <typename T, int L1, int L2>
@@ -267,11 +288,7 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_MIN_WA
   constexpr int CG1 = L2 / VEC, CG2 = L1 / VEC, Q1 = L1 / 16, Q2 = L2 / 16, N = L1 * L2;
   FOURIER_DYN_SMEM(smem);
   const int tid = (int)threadIdx.x;
-  uint64_t blk = blockIdx.x;
-  if (a.nxcd > 1) {
-    const uint64_t nwg = gridDim.x, nx = a.nxcd, xcd = blk % nx, q = nwg / nx, r = nwg % nx;
-    blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blk / nx;
-  }
+  const uint64_t blk = onelaunch_block(a);
   // one descriptor per transform, one 32-bit lane offset, the row offsets are compile-time scalars
   cpx<T>* const obase = (cpx<T>*)a.out + blk * N;
   const BufRsrc ri = make_rsrc((const cpx<T>*)a.in + blk * N), ro = make_rsrc(obase);
@@ -330,11 +347,7 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
   constexpr int CG1 = L2 / VEC, CG2 = L1 / VEC, Q1 = L1 / 16, Q2 = L2 / 16;
   FOURIER_DYN_SMEM(smem);
   const int tid = (int)threadIdx.x;
-  uint64_t blk = blockIdx.x;
-  if (a.nxcd > 1) {
-    const uint64_t nwg = gridDim.x, nx = a.nxcd, xcd = blk % nx, q = nwg / nx, r = nwg % nx;
-    blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blk / nx;
-  }
+  const uint64_t blk = onelaunch_block(a);
   // bounds-checked descriptors over this transform's user arrays and the chirp: everything at or beyond blu_n loads
   // as zero (the padding, bluesteins.rs:229-234) and is not stored (bluesteins.rs:240-258); no branches, and the
   // user rows of an odd-length f32 batch are only 8-byte aligned, which buffer_load/store_dwordx4 tolerate
@@ -372,14 +385,7 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
     FOURIER_LAUNDER(tb);
     const BufRsrc rw = make_rsrc(a.mul);
     const uint32_t woff = (uint32_t)(((tb / CG2) * L1 + (tb % CG2) * VEC) * sizeof(cpx<T>));
-    units_batched<T, 8>([&](int r) { return buf_load_unit<T>(rw, woff, (uint32_t)((Q2 * r) * L1 * sizeof(cpx<T>))); },
-                        [&](int r, const Unit16<T>& u) {
-#pragma unroll
-                          for (int v = 0; v < VEC; ++v) {
-                            const cpx<T> y = cmul(x[v][r], cpx<T>{u.a[2 * v], u.a[2 * v + 1]});
-                            x[v][r] = {y.im, y.re};
-                          }
-                        });
+    onelaunch_times_table_swap<T, L1, Q2>(x, rw, woff);
   }
   __syncthreads();
   {
@@ -421,11 +427,7 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
   constexpr int CG1 = L2 / VEC, CG2 = L1 / VEC, Q1 = L1 / 16, Q2 = L2 / 16, N = L1 * L2;
   FOURIER_DYN_SMEM(smem);
   const int tid = (int)threadIdx.x;
-  uint64_t blk = blockIdx.x;
-  if (a.nxcd > 1) {
-    const uint64_t nwg = gridDim.x, nx = a.nxcd, xcd = blk % nx, q = nwg / nx, r = nwg % nx;
-    blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blk / nx;
-  }
+  const uint64_t blk = onelaunch_block(a);
   constexpr uint32_t NBYTES = (uint32_t)(N * sizeof(cpx<T>));
   const BufRsrc ri = make_rsrc((const cpx<T>*)a.in + blk * N, NBYTES), ro = make_rsrc((cpx<T>*)a.out + blk * N, NBYTES);
   constexpr uint32_t ROWB = (uint32_t)(Q1 * L2 * sizeof(cpx<T>));  // register r holds index (th + Q1*r)*L2 + cg*VEC + v
@@ -447,14 +449,7 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
     const cpx<T>* wt = (const cpx<T>*)a.mul + (uint64_t)((a.bank_first + (uint32_t)blk) % a.bank_filters) * N;
     const BufRsrc rw = make_rsrc(wt, NBYTES);
     const uint32_t woff = (uint32_t)(((tb / CG2) * L1 + (tb % CG2) * VEC) * sizeof(cpx<T>));
-    units_batched<T, 8>([&](int r) { return buf_load_unit<T>(rw, woff, (uint32_t)((Q2 * r) * L1 * sizeof(cpx<T>))); },
-                        [&](int r, const Unit16<T>& u) {
-#pragma unroll
-                          for (int v = 0; v < VEC; ++v) {
-                            const cpx<T> y = cmul(x[v][r], cpx<T>{u.a[2 * v], u.a[2 * v + 1]});
-                            x[v][r] = {y.im, y.re};
-                          }
-                        });
+    onelaunch_times_table_swap<T, L1, Q2>(x, rw, woff);
   }
   __syncthreads();
   {

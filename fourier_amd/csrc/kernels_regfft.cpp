@@ -3,7 +3,7 @@
 // precision where the A/B against the route it had says so).  Compiled FOURIER_REGFFT_SHARDS times per precision
 // (-DFOURIER_TU_REAL=float / double -DFOURIER_REGFFT_SHARD=i): the rows are dealt round-robin over the shards (fourier_amd/build.py,
 // packaging/CMakeLists.txt).
-#include "engine_common.h"
+#include "regstage_host.h"
 #include "kernels_regfft.h"
 
 namespace fourier_hip {
@@ -11,17 +11,14 @@ namespace fourier_hip {
 typedef FOURIER_TU_REAL TUReal;
 
 template <typename T, uint32_t R1, uint32_t R2, uint32_t R3, bool SPLIT, bool FACT, bool PAIR = true> static ChirpzKernel make_regfft() {
-  ChirpzKernel k;
   if constexpr (R3 == 0) {
-    using C = ChirpzRegCfg<T, R1, R2>;
-    k.fn = &regfft_kernel<T, R1, R2>;
-    k.m = C::M; k.r1 = R1; k.r2 = R2; k.tpw = C::TPW; k.smem = C::SMEM;
+    return regstage_kernel_record<ChirpzRegCfg<T, R1, R2>, R1, R2, 0>(&regfft_kernel<T, R1, R2>);
   } else if constexpr (Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>::SMEM <= (size_t)160 * 1024 && Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>::NT <= 1024) {
-    using C = Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>;  // (a transform -- in f32 a pair -- with its padding within a compute unit's LDS, a stage within 1024 lanes)
-    k.fn = &regfft3_kernel<T, R1, R2, R3, SPLIT, FACT, PAIR>;
-    k.m = C::M; k.r1 = R1; k.r2 = R2; k.r3 = R3; k.tpw = C::NV; k.threads = C::NT; k.smem = C::SMEM; k.split = SPLIT; k.fact = FACT;
+    // (a transform -- in f32 a pair -- with its padding within a compute unit's LDS, a stage within 1024 lanes)
+    return regstage_kernel_record<Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>, R1, R2, R3>(&regfft3_kernel<T, R1, R2, R3, SPLIT, FACT, PAIR>, SPLIT, FACT);
+  } else {
+    return ChirpzKernel();
   }
-  return k;
 }
 
 enum { REGFFT_COUNTER_BASE = __COUNTER__ };

@@ -5,7 +5,8 @@
 // Here such lengths had the LDS mixed-radix kernels (kernels_mixed.h): a per-length kernel for the common ones, the runtime-parameterised
 // kernel for the rest (factors 7 / 11 / 13: 0.25 ... 0.35 of the HBM peak, one LDS round trip per SMALL radix, four to six per transform).
 // regfft_kernel / regfft3_kernel are ahead-of-time kernels per length (regfft_shapes.h, kernels_regfft.cpp) that keep the lane layout, the
-// packed f32 arithmetic (two transforms per lane) and the exchange layouts of the chirp-z kernels' forward half.  Tolerance-only route like
+// packed f32 arithmetic (two transforms per lane) and the exchange layouts of the chirp-z kernels' forward half; the lane value types, the LDS
+// put / get / exchange and the table product are those of kernels_regstage.h.  Tolerance-only route like
 // every length beyond 2^a 3^b (include/fourier.h); 2^a 3^b keep the reference's own schedule (bit-identical to the CPU restatement).
 #pragma once
 #include "kernels_chirpz.h"
@@ -20,7 +21,7 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) regfft_ke
   using P = typename C::P;
   using LV = LaneVal<P, T>;
   constexpr uint32_t GPW = C::GPW, TPW = C::TPW, NV = C::NV, P1 = C::P1, N = R1 * R2;
-  constexpr uint32_t EB = (uint32_t)sizeof(cpx<T>), XB = (uint32_t)sizeof(cpx<P>);
+  constexpr uint32_t EB = (uint32_t)sizeof(cpx<T>);
   FOURIER_DYN_SMEM(smem);
   const uint32_t lane = threadIdx.x, c = lane / R1, q = lane - c * R1;
   const bool active = c < GPW;
@@ -44,20 +45,15 @@ __global__ void __launch_bounds__(64, (ChirpzRegCfg<T, R1, R2>::MINW)) regfft_ke
       x[j1] = a.swap ? cpx<P>{LV::make(im), LV::make(re)} : cpx<P>{LV::make(re), LV::make(im)};
     }
     dft_any<P, (int)R1>(x);
-#pragma unroll
-    for (uint32_t k1 = 0; k1 < R1; ++k1) {
-      cpx<P>* p = xb + k1 * P1 + q;
-      LDS_NOTE(p, XB, true, 340);
-      *p = x[k1];
-    }
+    regstage_put<R1>(xb, x, [&](uint32_t k1) { return k1 * P1 + q; }, 340);
   }
   __syncthreads();
   if (active) {
     cpx<P> y[R2];
 #pragma unroll
-    for (uint32_t j2 = 0; j2 < R2; ++j2) {
+    for (uint32_t j2 = 0; j2 < R2; ++j2) {  // (written out: through regstage_get hipcc commutes one add of the 7-point butterfly where R2 = 7 -- 77, 91, 98, 147, f64 also 175; other shapes are neutral)
       const cpx<P>* p = xb + q * P1 + j2;
-      LDS_NOTE(p, XB, false, 341);
+      LDS_NOTE(p, (uint32_t)sizeof(cpx<P>), false, 341);
       y[j2] = *p;
     }
     chirpz_table_product<P, T, R2, 8u>(y, (const cpx<T>*)a.tw + q, R1, false);
@@ -85,64 +81,9 @@ template <typename T, uint32_t R1, uint32_t R2, uint32_t R3, bool SPLIT, bool PA
   using P = typename B::P;
   static constexpr uint32_t X12 = R2 * B::S1 > R3 * B::S2 ? R2 * B::S1 : R3 * B::S2;  // the forward exchanges only
   static constexpr size_t SMEM = (size_t)X12 * (SPLIT ? sizeof(P) : sizeof(cpx<P>));
-  static constexpr uint32_t LDS_WG = (uint32_t)((160u * 1024u) / SMEM);
-  static constexpr uint32_t WAVES = LDS_WG * (B::NT / 64u) / 4u;  // per SIMD, as far as the LDS goes
   // (unpaired f32: no bound -- the kernels take 70 ... 100 registers; any bound here is turned into one on whole workgroups and spills)
-  static constexpr uint32_t MINW = !PAIR || WAVES < 1u ? 1u : (WAVES > 3u ? 3u : WAVES);
+  static constexpr uint32_t MINW = !PAIR ? 1u : regstage_min_waves(SMEM, B::NT / 64u, 3u);
 };
-// one exchange: the writer lanes (t < LW) put their R values at widx(r), the reader lanes (t < LR) take theirs from ridx(r)
-template <bool SPLIT, typename P, uint32_t RW, uint32_t RR, typename WI, typename RI>
-__device__ __forceinline__ void regfft_exchange(void* smem, bool writer, bool reader, const cpx<P>* w, cpx<P>* r, WI widx, RI ridx, int note) {
-  if constexpr (!SPLIT) {
-    cpx<P>* xb = (cpx<P>*)smem;
-    if (writer) {
-#pragma unroll
-      for (uint32_t i = 0; i < RW; ++i) {
-        cpx<P>* p = xb + widx(i);
-        LDS_NOTE(p, (uint32_t)sizeof(cpx<P>), true, note);
-        *p = w[i];
-      }
-    }
-    __syncthreads();
-    if (reader) {
-#pragma unroll
-      for (uint32_t i = 0; i < RR; ++i) {
-        const cpx<P>* p = xb + ridx(i);
-        LDS_NOTE(p, (uint32_t)sizeof(cpx<P>), false, note + 1);
-        r[i] = *p;
-      }
-    }
-  } else {
-    P* xs = (P*)smem;
-    if (writer) {
-#pragma unroll
-      for (uint32_t i = 0; i < RW; ++i) {
-        P* p = xs + widx(i);
-        LDS_NOTE(p, (uint32_t)sizeof(P), true, note);
-        *p = w[i].re;
-      }
-    }
-    __syncthreads();
-    if (reader) {
-#pragma unroll
-      for (uint32_t i = 0; i < RR; ++i) {
-        const P* p = xs + ridx(i);
-        LDS_NOTE(p, (uint32_t)sizeof(P), false, note + 1);
-        r[i].re = *p;
-      }
-    }
-    __syncthreads();
-    if (writer) {
-#pragma unroll
-      for (uint32_t i = 0; i < RW; ++i) xs[widx(i)] = w[i].im;
-    }
-    __syncthreads();
-    if (reader) {
-#pragma unroll
-      for (uint32_t i = 0; i < RR; ++i) r[i].im = xs[ridx(i)];
-    }
-  }
-}
 
 // FACT: the twiddle between stages A and B, W_N^{(j3 + R3 j2) k1}, as W_{R1R2}^{j2 k1} (R1 R2 entries, the lanes of one k1 share an address) before
 // DFT_R2 and W_N^{j3 k1} (one entry per lane) after it: tables of R1R2 + R1R3 + R2R3 entries that stay in the L1 instead of N + R2R3 entries
@@ -181,7 +122,7 @@ __global__ void __launch_bounds__((Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>::NT), 
   }
   {  // exchange 1: rows j2, the reader's lane k1*R3 + j3
     const uint32_t j2 = t / R3, j3 = t - j2 * R3;
-    regfft_exchange<SPLIT, P, R1, R2>(smem, t < LA, t < LB, x, y, [&](uint32_t k1) { return j2 * S1 + k1 * R3 + j3; },
+    regstage_exchange<SPLIT, R1, R2>(smem, t < LA, t < LB, x, y, [&](uint32_t k1) { return j2 * S1 + k1 * R3 + j3; },
                                       [&](uint32_t r) { return r * S1 + t; }, 350);
   }
   if (t < LB) {
@@ -203,7 +144,7 @@ __global__ void __launch_bounds__((Regfft3Cfg<T, R1, R2, R3, SPLIT, PAIR>::NT), 
   __syncthreads();  // exchange 1 is read
   {  // exchange 2: rows j3, the reader's lane k1 + R1*k2
     const uint32_t k1 = t / R3, j3 = t - k1 * R3;
-    regfft_exchange<SPLIT, P, R2, R3>(smem, t < LB, t < LC, y, z, [&](uint32_t k2) { return j3 * S2 + k1 + R1 * k2; },
+    regstage_exchange<SPLIT, R2, R3>(smem, t < LB, t < LC, y, z, [&](uint32_t k2) { return j3 * S2 + k1 + R1 * k2; },
                                       [&](uint32_t r) { return r * S2 + t; }, 352);
   }
   if (t < LC) {
