@@ -16,6 +16,7 @@
 #include "axis_plan.h"
 #include "realnd_plan.h"
 #include "conv_plan.h"
+#include "r2r_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -203,6 +204,24 @@ FOURIER_DEFINE_REALND_ABI(double, double)
 
 FOURIER_DEFINE_CONV_ABI(float, float)
 FOURIER_DEFINE_CONV_ABI(double, double)
+
+// real-to-real transforms, DCT / DST of types II and III (fourier_hip_r2r_*)
+#define FOURIER_DEFINE_R2R_ABI(T, SUFFIX)                                                                        \
+  FOURIER_DEFINE_HANDLE_ABI(r2r, fourier_r2r_##SUFFIX, R2RPlan<T>, SUFFIX)                                       \
+  extern "C" fc::fourier_r2r_##SUFFIX* fourier_hip_r2r_create_##SUFFIX(size_t size, int device) {                \
+    return (fc::fourier_r2r_##SUFFIX*)create_handle<R2RPlan<T>>(size, device);                                   \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_r2r_size_##SUFFIX(const fc::fourier_r2r_##SUFFIX* h) {                           \
+    return h ? ((const R2RPlan<T>*)h)->size() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" int fourier_hip_r2r_transform_batch_##SUFFIX(const fc::fourier_r2r_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                          size_t batch, int kind, int norm, void* stream) {      \
+    const R2RPlan<T>* p = (const R2RPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->transform(d_in, d_out, batch, kind, norm, (hipStream_t)stream); });        \
+  }
+
+FOURIER_DEFINE_R2R_ABI(float, float)
+FOURIER_DEFINE_R2R_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -169,6 +169,7 @@ typedef void (*TinyKernel)(TinyArgs);
 typedef void (*GenKernel)(GenArgs);
 typedef void (*BluKernel)(BluArgs);
 typedef void (*RealKernel)(RealArgs);
+typedef void (*R2RKernel)(R2RArgs);
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -248,6 +249,8 @@ template <typename T> struct Real {};
   BluKernel get_blu_kernel(Real<T>, int which); /* 0 = pre, 1 = post, 2 = mul */                                       \
   /* kernels_real.cpp: the sweeps of the real-input transforms, which = REAL_POST ... REAL_PART (kernel_args.h) */        \
   RealKernel get_real_kernel(Real<T>, int which);                                                                      \
+  /* kernels_r2r.cpp: the sweeps of the DCT / DST handle, which = R2R_PACK ... R2R_ODD_PART (kernel_args.h) */             \
+  R2RKernel get_r2r_kernel(Real<T>, int which);                                                                        \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_PAD (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \

@@ -166,6 +166,28 @@ struct RealArgs {
   uint32_t seg_m, seg_l, row_m, row_l, c_m, c_l, b_m, b_l;  // N-D: multiply-high dividers by segs, nd_rows, nd[2], nd[1]
 };
 
+// ---- real-to-real transforms, DCT / DST of types II and III (kernels_r2r.h; R2RPlan, r2r_plan.h)
+// Even N = 2h: r2r_pack_kernel / r2r_unpack_kernel run one lane per four consecutive reals of a row (`lanes` = (h + 1) / 2; the
+// middle lane of an odd h has two), r2r_post_kernel / r2r_pre_kernel one lane per mirrored pair (j, h - j), j <= h / 2 (`lanes` =
+// h / 2 + 1), all over a flat index of rows x lanes; byte offsets are 32-bit as the real sweeps' (rows of N reals and rows of h
+// complex values have the same size, so one launch covers the same rows of both sides).  The odd-N sweeps (plain grid-stride loops
+// between user rows and the complex N-point work array) read in, out, ct, n, rows, sine, scale and edge only.
+enum { R2R_PACK = 0, R2R_POST = 1, R2R_PRE = 2, R2R_UNPACK = 3, R2R_ODD_WIDEN = 4, R2R_ODD_POST = 5, R2R_ODD_PRE = 6, R2R_ODD_PART = 7 };
+struct R2RArgs {
+  const void* in; void* out;
+  const void* tw;             // W_N^j, j <= h / 2 (f64 on the host, cast)
+  const void* ct;             // c_j = exp(-i pi j / 2N), j <= h (odd N: j < N)
+  uint32_t h;                 // N / 2: complex points of the inner transform
+  uint32_t lanes;             // lanes per row
+  uint32_t total;             // rows * lanes
+  uint32_t div_m, div_l;      // idx / lanes = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  int sine;                   // DST: the odd-indexed reals of the time side change sign, the index of the transform side is reversed
+  double scale;               // the norm's factor (post: times 2 Re / -2 Im; pre: on V)
+  double edge;                // factor on the transform side's element 0 (cosine index): 1, or the orthogonalised form's 1/sqrt 2, sqrt 2
+  uint64_t n, rows;           // odd N: real length, rows in this launch
+};
+
 // ---- convolution with a filter bank (kernels_conv.h; ConvPlan, conv_plan.h)
 // conv_mul_kernel: Z[b][k] *= H[(first + b) mod filters][k] over a flat index of rows x len, one lane per element.
 // real_conv_mid_kernel: one lane per mirrored pair (j, h - j) of a row of the inner plan's output, as the real sweeps (`len` = h / 2 + 1

@@ -459,6 +459,116 @@ def fftconv(x, taps, correlate=False, out=None):
     return p.apply(x, out)
 
 
+R2R_KINDS = {("dct", 2): 0, ("dct", 3): 1, ("dst", 2): 2, ("dst", 3): 3}  # FOURIER_R2R_DCT2 ... FOURIER_R2R_DST3
+R2R_NORMS = {None: 0, "backward": 0, "ortho": 1, "forward": 2}             # FOURIER_R2R_NORM_*
+
+
+class R2R(_Handle):
+    """Batched DCT / DST of types II and III (include/fourier.h, fourier_hip_r2r_*) on device memory: rows of N reals in, rows of N
+    reals out, scipy.fft's definitions and norms.  One handle serves every kind and norm."""
+
+    _prefix = "fourier_hip_r2r_"
+    _destroy = "fourier_hip_r2r_destroy"
+
+    def __init__(self, size, real, device=-1):
+        self._create(real, f"real-to-real plan of size {size}", int(size), int(device))
+        self._n = int(size)
+
+    def size(self):
+        return self._n
+
+    def transform_batch_ptr(self, d_in, d_out, batch, kind, norm=0, stream=0):
+        """`batch` rows of N reals at d_in -> `batch` rows at d_out (d_out may be d_in), enqueued on `stream`; kind and norm are the
+        header's FOURIER_R2R_* values (R2R_KINDS, R2R_NORMS)."""
+        self._call("transform_batch", d_in, d_out, int(batch), int(kind), int(norm), stream)
+
+    def transform(self, x, kind, norm=0, out=None):
+        """Contiguous (..., N) float32 / float64 CUDA tensor -> a new tensor of the same shape, or `out` (which may be `x`), on the
+        current stream."""
+        import torch
+
+        _require_cuda(x, _torch_dtypes(self.real)[0])
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out is not x:
+            _require_out(out, x.shape, x.dtype, x.device)
+            _require_no_partial_overlap(x, out)
+        batch = x.numel() // self._n
+        if batch:
+            self.transform_batch_ptr(x.data_ptr(), out.data_ptr(), batch, kind, norm, _stream(x))
+        return out
+
+
+def create_r2r_f32(size, device=-1):
+    return R2R(size, "f32", device)
+
+
+def create_r2r_f64(size, device=-1):
+    return R2R(size, "f64", device)
+
+
+def _r2r(family, inverse, x, type, norm, dim, out):
+    import torch
+
+    if type not in (2, 3):
+        raise ValueError(f"{family} type {type!r} is not supported: types 2 and 3 are (types 1 and 4 are unsupported)")
+    if norm not in R2R_NORMS:
+        raise ValueError(f"norm must be None, 'backward', 'ortho' or 'forward', got {norm!r}")
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    d = _normalise_dims(x.dim(), (dim,))[0]
+    if x.shape[d] == 0:
+        raise ValueError(f"the transformed dimension must have length >= 1, got {tuple(x.shape)}")
+    code = R2R_NORMS[norm]
+    if inverse:  # scipy's idct / idst: the other type, backward and forward exchanged
+        type, code = 5 - type, {0: 2, 1: 1, 2: 0}[code]
+    kind = R2R_KINDS[(family, type)]
+    if out is not None and out is not x:
+        if not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == tuple(x.shape) and out.device == x.device):
+            raise TypeError(f"out must be a CUDA {_names((x.dtype,))} tensor of shape {tuple(x.shape)} on the input's device")
+    plan = _cached_plan(R2R, int(x.shape[d]), _precision(x.dtype)[0], int(_device_index(x)))
+    last = d == x.dim() - 1
+    if last and x.is_contiguous() and (out is None or out.is_contiguous()):
+        return plan.transform(x, kind, code, out)
+    # any other dim (or layout): a torch copy that makes the axis last and contiguous, the transform in place there, a copy back
+    work = x.movedim(d, -1).contiguous()
+    if work.data_ptr() == x.data_ptr():
+        work = work.clone()
+    plan.transform(work, kind, code, work)
+    res = work.movedim(-1, d)
+    if out is None:
+        return res.contiguous()
+    out.copy_(res)
+    return out
+
+
+def dct(x, type=2, norm=None, dim=-1, out=None):
+    """scipy.fft.dct of a float32 / float64 CUDA tensor along `dim`, types 2 and 3 (types 1 and 4 raise ValueError), norm None /
+    "backward" / "ortho" / "forward" (scipy's orthogonalised "ortho"), on the current stream; returns a new tensor or `out`, which
+    may be `x`.  Only the last dimension of a contiguous tensor is native (one cached R2R handle per (N, dtype, device)); any other
+    `dim` is moved last with a torch copy, transformed there and moved back."""
+    return _r2r("dct", False, x, type, norm, dim, out)
+
+
+def idct(x, type=2, norm=None, dim=-1, out=None):
+    """scipy.fft.idct: the inverse of dct(type, norm) -- the other type with "backward" and "forward" exchanged.  See dct."""
+    return _r2r("dct", True, x, type, norm, dim, out)
+
+
+def dst(x, type=2, norm=None, dim=-1, out=None):
+    """scipy.fft.dst, types 2 and 3.  See dct."""
+    return _r2r("dst", False, x, type, norm, dim, out)
+
+
+def idst(x, type=2, norm=None, dim=-1, out=None):
+    """scipy.fft.idst: the inverse of dst(type, norm).  See dct."""
+    return _r2r("dst", True, x, type, norm, dim, out)
+
+
 class RealFftN(_RealHandle):
     """Batched real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*) over items of `shape` (1 ... 4 dimensions, the
     last one real) on device memory, numpy's rfftn / irfftn layout: an item of reals has `shape`, an item of the half spectrum has

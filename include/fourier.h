@@ -502,6 +502,60 @@ const char *fourier_hip_conv_describe_double(const FOURIER_STRUCT fourier_conv_d
 int fourier_hip_conv_last_status_float(const FOURIER_STRUCT fourier_conv_float *);
 int fourier_hip_conv_last_status_double(const FOURIER_STRUCT fourier_conv_double *);
 
+/* ---------------- real-to-real transforms: DCT and DST of types II and III (extension; the reference has none) ----------
+ * Batched discrete cosine / sine transforms of length N >= 1 on DEVICE memory, scipy.fft's dct / dst definitions (FFTW's REDFT10,
+ * REDFT01, RODFT10, RODFT01): `batch` rows of N reals T in, row b at element offset b*N, `batch` rows of N reals out.
+ *   FOURIER_R2R_DCT2  X[k] = 2 sum_n x[n] cos(pi k (2n+1) / 2N)
+ *   FOURIER_R2R_DCT3  x[n] = X[0] + 2 sum_{k>=1} X[k] cos(pi k (2n+1) / 2N)         (DCT3(DCT2(x)) = 2N x)
+ *   FOURIER_R2R_DST2  X[k] = 2 sum_n x[n] sin(pi (k+1) (2n+1) / 2N)
+ *   FOURIER_R2R_DST3  x[n] = (-1)^n X[N-1] + 2 sum_{k<N-1} X[k] sin(pi (k+1) (2n+1) / 2N)   (DST3(DST2(x)) = 2N x)
+ * times the norm's factor: FOURIER_R2R_NORM_BACKWARD 1, FOURIER_R2R_NORM_FORWARD 1/2N, FOURIER_R2R_NORM_ORTHO 1/sqrt(2N) in scipy's
+ * orthogonalised form (DCT2's X[0] and DST2's X[N-1] times 1/sqrt 2, DCT3's input X[0] and DST3's input X[N-1] times sqrt 2), whose
+ * matrices are orthogonal.  The inverse of a type-II transform is the type-III one with BACKWARD and FORWARD exchanged (scipy's idct /
+ * idst), and the other way round.  One handle serves every kind and norm.
+ * d_in == d_out is in place and allowed; any other overlap, a NULL pointer, a pointer not aligned to 2*sizeof(T), a kind or norm
+ * outside the enums give FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.  Stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*.  Even N runs an inner N/2-point complex plan between two linear sweeps (pack and post, or pre and
+ * unpack), each one read and one write of the rows; odd N runs the N-point complex plan on a widened copy (a correctness path).  The
+ * plan owns a scratch of at most 1 GiB (never less than one row) and walks larger batches in chunks of it; the first call with a
+ * batch larger than any before allocates it unless fourier_hip_r2r_reserve_* was called for at least that batch.
+ * fourier_hip_r2r_describe_* returns "r2r half-length: <inner plan's describe>" (even N) or "r2r full-length: <inner plan's
+ * describe>" (odd N).  Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_r2r_last_status_*. */
+enum {
+  FOURIER_R2R_DCT2 = 0,
+  FOURIER_R2R_DCT3 = 1,
+  FOURIER_R2R_DST2 = 2,
+  FOURIER_R2R_DST3 = 3,
+};
+enum {
+  FOURIER_R2R_NORM_BACKWARD = 0,
+  FOURIER_R2R_NORM_ORTHO = 1,
+  FOURIER_R2R_NORM_FORWARD = 2,
+};
+struct fourier_r2r_float;
+struct fourier_r2r_double;
+
+/* NULL on failure (size 0 included). */
+struct fourier_r2r_float *fourier_hip_r2r_create_float(FOURIER_SIZE_TYPE size, int device);
+struct fourier_r2r_double *fourier_hip_r2r_create_double(FOURIER_SIZE_TYPE size, int device);
+/* NULL is a no-op. */
+void fourier_hip_r2r_destroy_float(FOURIER_STRUCT fourier_r2r_float *);
+void fourier_hip_r2r_destroy_double(FOURIER_STRUCT fourier_r2r_double *);
+/* N; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_r2r_size_float(const FOURIER_STRUCT fourier_r2r_float *);
+FOURIER_SIZE_TYPE fourier_hip_r2r_size_double(const FOURIER_STRUCT fourier_r2r_double *);
+int fourier_hip_r2r_transform_batch_float(const FOURIER_STRUCT fourier_r2r_float *, const void *d_in, void *d_out,
+                                          FOURIER_SIZE_TYPE batch, int kind, int norm, void *stream);
+int fourier_hip_r2r_transform_batch_double(const FOURIER_STRUCT fourier_r2r_double *, const void *d_in, void *d_out,
+                                           FOURIER_SIZE_TYPE batch, int kind, int norm, void *stream);
+/* Pre-size the scratch and the inner plan's buffers: afterwards calls of at most `batch` rows never allocate. */
+int fourier_hip_r2r_reserve_float(const FOURIER_STRUCT fourier_r2r_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_r2r_reserve_double(const FOURIER_STRUCT fourier_r2r_double *, FOURIER_SIZE_TYPE batch);
+const char *fourier_hip_r2r_describe_float(const FOURIER_STRUCT fourier_r2r_float *);
+const char *fourier_hip_r2r_describe_double(const FOURIER_STRUCT fourier_r2r_double *);
+int fourier_hip_r2r_last_status_float(const FOURIER_STRUCT fourier_r2r_float *);
+int fourier_hip_r2r_last_status_double(const FOURIER_STRUCT fourier_r2r_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -602,6 +656,53 @@ template <typename T> struct real_fft;
 FOURIER_DEFINE_CXX_REAL_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_REAL_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_REAL_WRAPPER
+
+/* DCT / DST of types II and III on device memory (extension): fourier::r2r<float> / <double> */
+enum class r2r_kind {
+  dct2 = ::fourier::c::FOURIER_R2R_DCT2,
+  dct3 = ::fourier::c::FOURIER_R2R_DCT3,
+  dst2 = ::fourier::c::FOURIER_R2R_DST2,
+  dst3 = ::fourier::c::FOURIER_R2R_DST3,
+};
+enum class r2r_norm {
+  backward = ::fourier::c::FOURIER_R2R_NORM_BACKWARD,
+  ortho = ::fourier::c::FOURIER_R2R_NORM_ORTHO,
+  forward = ::fourier::c::FOURIER_R2R_NORM_FORWARD,
+};
+template <typename T> struct r2r;
+
+#define FOURIER_DEFINE_CXX_R2R_WRAPPER(T, SUFFIX)                                                  \
+  template <> struct r2r<T> {                                                                      \
+    explicit r2r(std::size_t size, int device = -1)                                                \
+        : impl(::fourier::c::fourier_hip_r2r_create_##SUFFIX(size, device),                        \
+               ::fourier::c::fourier_hip_r2r_destroy_##SUFFIX) {}                                  \
+    r2r() = delete;                                                                                \
+    r2r(const r2r &) = delete;                                                                     \
+    r2r(r2r &&) = default;                                                                         \
+    r2r &operator=(const r2r &) = delete;                                                          \
+    r2r &operator=(r2r &&) = default;                                                              \
+    ~r2r() = default;                                                                              \
+    std::size_t size() const { return ::fourier::c::fourier_hip_r2r_size_##SUFFIX(impl.get()); }   \
+    /* N reals per row -> N reals per row; d_out may be d_in */                                    \
+    int transform_batch_device(const void *d_in, void *d_out, std::size_t batch, r2r_kind kind,    \
+                               r2r_norm norm = r2r_norm::backward, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_r2r_transform_batch_##SUFFIX(                               \
+          impl.get(), d_in, d_out, batch, static_cast<int>(kind), static_cast<int>(norm), stream); \
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_r2r_reserve_##SUFFIX(impl.get(), batch);                    \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_r2r_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_r2r_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_r2r_##SUFFIX,                                          \
+                      void (*)(::fourier::c::fourier_r2r_##SUFFIX *)> impl;                        \
+  };
+FOURIER_DEFINE_CXX_R2R_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_R2R_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_R2R_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
