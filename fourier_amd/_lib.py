@@ -36,6 +36,10 @@ _CONV = ("fourier_hip_conv_", {  # convolution with a prepared filter bank
     "create": (vp, [sz, ci, ci]), "destroy": (None, [vp]), "size": (sz, [vp]), "filters": (sz, [vp]),
     "set_filters": (ci, [vp, vp, sz, sz, ci, vp]), "apply": (ci, [vp, vp, vp, sz, vp]), "reserve": (ci, [vp, sz]),
     "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_LCONV = ("fourier_hip_lconv_", {  # linear convolution (full / same / valid) with a prepared filter bank
+    "create": (vp, [sz, sz, ci, ci, ci]), "destroy": (None, [vp]), "length": (sz, [vp]), "taps": (sz, [vp]), "out_length": (sz, [vp]),
+    "filters": (sz, [vp]), "set_filters": (ci, [vp, vp, sz, ci, vp]), "apply": (ci, [vp, vp, vp, sz, vp]), "reserve": (ci, [vp, sz]),
+    "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _R2R = ("fourier_hip_r2r_", {  # DCT / DST of types II and III
     "create": (vp, [sz, ci]), "destroy": (None, [vp]), "size": (sz, [vp]),
     "transform_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),  # handle, d_in, d_out, batch, kind, norm, stream
@@ -56,7 +60,8 @@ REAL_SYMBOLS = list(_signatures(_REAL))
 AXIS_SYMBOLS = list(_signatures(_AXIS))
 REALND_SYMBOLS = list(_signatures(_REALND))
 CONV_SYMBOLS = list(_signatures(_CONV))
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS
+LCONV_SYMBOLS = list(_signatures(_LCONV))
+ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -66,7 +71,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _R2R):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -47,6 +47,7 @@ template <typename T> class ConvPlan : public HandleBase {
 
   size_t size() const { return n_; }
   size_t filters() const { return filters_; }
+  int device() const { return device_; }
 
   int set_option(const std::string& key, long long v) {
     if (key == "fusion" && (v == 0 || v == 1)) { set_fusion(v == 1); return ::fourier::c::FOURIER_HIP_OK; }
@@ -103,7 +104,8 @@ template <typename T> class ConvPlan : public HandleBase {
     filters_ = filters;
   }
 
-  void apply(const void* d_in, void* d_out, size_t batch, hipStream_t stream) const {
+  // first: the index the call's first row counts its filter from (the linear-convolution handle walks its own chunks)
+  void apply(const void* d_in, void* d_out, size_t batch, hipStream_t stream, size_t first = 0) const {
     const size_t row = n_ * (real_ ? sizeof(T) : ELEM);
     check_buffers(d_in, d_out, batch * row, batch * row, ELEM, true);
     if (filters_ == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "no filters set");
@@ -115,9 +117,10 @@ template <typename T> class ConvPlan : public HandleBase {
     cpx<T>* work = (cpx<T>*)scratch_.p;
     const cpx<T>* bank = (const cpx<T>*)bank_.p;
     const int FWD = ::fourier::c::FOURIER_TRANSFORM_FFT, INV = ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT;
-    for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
-      const void* src = in + b0 * row;
-      void* dst = out + b0 * row;
+    for_chunks(batch, chunk, [&](size_t c0, size_t nb) {
+      const void* src = in + c0 * row;
+      void* dst = out + c0 * row;
+      const size_t b0 = first + c0;
       switch (route_) {
         case ONE_LAUNCH:
           plan_->exec_conv(src, dst, nb, bank, filters_, b0, nullptr, nullptr, stream);

@@ -16,6 +16,7 @@
 #include "axis_plan.h"
 #include "realnd_plan.h"
 #include "conv_plan.h"
+#include "lconv_plan.h"
 #include "r2r_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -204,6 +205,42 @@ FOURIER_DEFINE_REALND_ABI(double, double)
 
 FOURIER_DEFINE_CONV_ABI(float, float)
 FOURIER_DEFINE_CONV_ABI(double, double)
+
+// linear convolution with a prepared filter bank (fourier_hip_lconv_*)
+#define FOURIER_DEFINE_LCONV_ABI(T, SUFFIX)                                                                      \
+  FOURIER_DEFINE_HANDLE_ABI(lconv, fourier_lconv_##SUFFIX, LinearConvPlan<T>, SUFFIX)                            \
+  extern "C" fc::fourier_lconv_##SUFFIX* fourier_hip_lconv_create_##SUFFIX(size_t length, size_t taps, int mode, int real_data, \
+                                                                           int device) {                         \
+    return (fc::fourier_lconv_##SUFFIX*)create_handle<LinearConvPlan<T>>(length, taps, mode, real_data != 0, device); \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_lconv_length_##SUFFIX(const fc::fourier_lconv_##SUFFIX* h) {                     \
+    return h ? ((const LinearConvPlan<T>*)h)->length() : 0;                                                      \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_lconv_taps_##SUFFIX(const fc::fourier_lconv_##SUFFIX* h) {                       \
+    return h ? ((const LinearConvPlan<T>*)h)->taps() : 0;                                                        \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_lconv_out_length_##SUFFIX(const fc::fourier_lconv_##SUFFIX* h) {                 \
+    return h ? ((const LinearConvPlan<T>*)h)->out_length() : 0;                                                  \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_lconv_filters_##SUFFIX(const fc::fourier_lconv_##SUFFIX* h) {                    \
+    return h ? ((const LinearConvPlan<T>*)h)->filters() : 0;                                                     \
+  }                                                                                                              \
+  extern "C" int fourier_hip_lconv_set_filters_##SUFFIX(fc::fourier_lconv_##SUFFIX* h, const void* d_taps, size_t filters, \
+                                                        int correlate, void* stream) {                           \
+    LinearConvPlan<T>* p = (LinearConvPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->set_filters(d_taps, filters, correlate != 0, (hipStream_t)stream); });     \
+  }                                                                                                              \
+  extern "C" int fourier_hip_lconv_apply_##SUFFIX(const fc::fourier_lconv_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                  size_t batch, void* stream) {                                  \
+    const LinearConvPlan<T>* p = (const LinearConvPlan<T>*)h;                                                    \
+    return guarded_handle(p, [&] { p->apply(d_in, d_out, batch, (hipStream_t)stream); });                        \
+  }                                                                                                              \
+  extern "C" int fourier_hip_lconv_set_option_##SUFFIX(fc::fourier_lconv_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<LinearConvPlan<T>>(h, key, v);                                                      \
+  }
+
+FOURIER_DEFINE_LCONV_ABI(float, float)
+FOURIER_DEFINE_LCONV_ABI(double, double)
 
 // real-to-real transforms, DCT / DST of types II and III (fourier_hip_r2r_*)
 #define FOURIER_DEFINE_R2R_ABI(T, SUFFIX)                                                                        \

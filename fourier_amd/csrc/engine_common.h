@@ -242,6 +242,8 @@ template <typename T> struct Real {};
   bool get_blu_small_kernel(Real<T>, int k, KernelInfo& info);                                                         \
   /* ... and the circular convolution with a filter bank in one launch for the two-level plans of 2^11 ... 2^15 */       \
   bool get_conv_small_kernel(Real<T>, int k, KernelInfo& info);                                                        \
+  /* ... and the overlap-save blocks of a linear convolution on the same shapes (lconv_small_kernel), complex or real rows */ \
+  bool get_lconv_small_kernel(Real<T>, int k, bool real_data, KernelInfo& info);                                       \
   /* kernels_misc.cpp */                                                                                               \
   TinyKernel get_tiny_kernel(Real<T>, size_t n);                                                                       \
   OddKernel get_odd_kernel(Real<T>, int r);                                                                            \
@@ -251,7 +253,7 @@ template <typename T> struct Real {};
   RealKernel get_real_kernel(Real<T>, int which);                                                                      \
   /* kernels_r2r.cpp: the sweeps of the DCT / DST handle, which = R2R_PACK ... R2R_ODD_PART (kernel_args.h) */             \
   R2RKernel get_r2r_kernel(Real<T>, int which);                                                                        \
-  /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_PAD (kernel_args.h) */             \
+  /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \

@@ -15,6 +15,10 @@ template <typename T> static void make_stage_tables(int L, StageTables<T>& st) {
   if (Q > 1 && R3 > 1) st.tw2.upload(product_table<T>(Q, R3, 16));  // W_Q^{i * k} as [i < R3][k < 16]
 }
 
+// the overlap-save geometry of a linear-convolution handle (lconv_plan.h), as lconv_small_kernel reads it (PassArgs lc_*): row lengths
+// in and out, step S, the mode's offset, blocks and workgroups per row, the multiply-high divider by wpr
+struct LconvGeom { uint32_t lx = 0, lout = 0, step = 0, off = 0, nb = 0, wpr = 0, div_m = 0, div_l = 0; };
+
 // ---------------------------------------------------------------------------------------------
 // batched power-of-two FFT: schedule of big-radix Stockham passes
 template <typename T> class Pow2Engine {
@@ -229,6 +233,36 @@ template <typename T> class Pow2Engine {
     a.mul = bank; a.bank_filters = filters; a.bank_first = first_row;
     a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
     launch(nullptr, 0, conv_small_.fn, batch, conv_small_.NT, conv_small_.smem, stream, a);
+  }
+
+  // The overlap-save blocks of a linear convolution in one launch (lconv_small_kernel; the linear-convolution handle): conv_small_kernel's
+  // shapes and tables; one kernel for complex rows, one for real rows (two blocks of a row as real and imaginary part).
+  bool enable_lconv_small(bool real_data) {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    KernelInfo& k = lconv_small_[real_data ? 1 : 0];
+    if (k.fn) return true;
+    if (!get_lconv_small_kernel(Real<T>{}, ilog2(n_), real_data, k)) return false;
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    set_smem_attribute(k);
+    return true;
+  }
+  // in: `rows` rows of g.lx values, out: rows of g.lout values, no overlap; bank: `filters` tables of n entries, row b of the launch
+  // multiplies by table (first_row + b) mod filters; rows * g.wpr workgroups, below 2^31 (the caller bounds `rows`)
+  void run_lconv_small(const void* in, void* out, size_t rows, const void* bank, uint32_t filters, uint32_t first_row, bool real_data,
+                       const LconvGeom& g, hipStream_t stream, unsigned nxcd) const {
+    if (rows == 0) return;
+    const Pass& ps = *passes_[0];
+    const KernelInfo& k = lconv_small_[real_data ? 1 : 0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.mul = bank; a.bank_filters = filters; a.bank_first = first_row;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = (uint64_t)rows * g.wpr;
+    a.lc_lx = g.lx; a.lc_lout = g.lout; a.lc_step = g.step; a.lc_off = g.off; a.lc_nb = g.nb; a.lc_wpr = g.wpr;
+    a.lc_m = g.div_m; a.lc_l = g.div_l;
+    launch(nullptr, 0, k.fn, (uint64_t)rows * g.wpr, k.NT, k.smem, stream, a);
   }
 
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
@@ -623,7 +657,7 @@ template <typename T> class Pow2Engine {
   size_t n_;
   bool tiny_ = false;
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
-  KernelInfo blu_small_, conv_, conv_bank_, conv_small_;
+  KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   StageTables<T>* conv_st_ = nullptr;
   FusedInfo fused_;
   bool fused_on_ = false;

@@ -59,6 +59,14 @@ struct PassArgs {
   // mul + ((bank_first + b) mod bank_filters) * n; the Bluestein instantiations read neither field
   uint32_t bank_filters;
   uint32_t bank_first;  // (the first row of the launch) mod bank_filters
+  // lconv_small_kernel (LinearConvPlan, lconv_plan.h): overlap-save blocks of rows of lc_lx values in, lc_lout values out.  Block j of a
+  // row holds input positions j * lc_step - (N - lc_step) + i, i < N, and stores its elements i >= N - lc_step to output position
+  // j * lc_step + i - (N - lc_step) - lc_off.  Workgroup w of the launch: row w / lc_wpr, block (complex data) or pair of blocks
+  // (real data) w % lc_wpr.
+  uint32_t lc_lx, lc_lout, lc_step, lc_off;
+  uint32_t lc_nb;           // blocks per row
+  uint32_t lc_wpr;          // workgroups per row: lc_nb, real data (lc_nb + 1) / 2
+  uint32_t lc_m, lc_l;      // w / lc_wpr = (umulhi(w, lc_m) + w) >> lc_l
 };
 
 
@@ -195,7 +203,13 @@ struct R2RArgs {
 // 32-bit (at most REAL_LAUNCH_BYTES per launch), the bank is addressed with 64-bit indices.
 // conv_finish_kernel: bank[i] = scale * bank[i] (conjugated where conj != 0), i < count.  conv_pad_kernel: `rows` rows of `taps`
 // words T -> rows of `n` words, zero-extended (a complex value is two words).
-enum { CONV_MUL = 0, CONV_REAL_MID = 1, CONV_FINISH = 2, CONV_PAD = 3 };
+// The linear-convolution handle (LinearConvPlan, lconv_plan.h) adds two more.  lconv_copy_kernel, the pad and the crop sweep of its
+// padded route: output row r, word k < n, is input word skip + k of input row r (rows of `taps` words) where that lies inside the
+// row, else zero; one workgroup per LCONV_SEG words of an output row, `len` segments per row, over a flat index of rows x len.
+// lconv_taps_kernel (set_filters): `rows` filters of `taps` values of the handle's kind -> rows of `n` values, zero-extended, in
+// reverse order and conjugated where conj != 0 (a correlation), real values widened to complex ones where widen != 0.
+enum { CONV_MUL = 0, CONV_REAL_MID = 1, CONV_FINISH = 2, CONV_PAD = 3, CONV_LCOPY = 4, CONV_LTAPS = 5 };
+constexpr uint32_t LCONV_SEG = 2048;
 struct ConvArgs {
   const void* in; void* out;  // the sweeps run in place: in == out
   const void* tw;             // real mid sweep: W_N^j, j <= h / 2
@@ -211,6 +225,8 @@ struct ConvArgs {
   uint64_t count;             // finish: complex values
   int conj;
   double scale;
+  uint64_t skip;              // lconv copy: words of an input row in front of the first one copied
+  int widen, real;            // lconv taps: real taps -> complex rows; the values are reals (else complex)
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -14,6 +14,8 @@ ConvKernel get_conv_sweep_kernel(Real<TUReal>, int which) {
     case CONV_REAL_MID: return &real_conv_mid_kernel<T>;
     case CONV_FINISH: return &conv_finish_kernel<T>;
     case CONV_PAD: return &conv_pad_kernel<T>;
+    case CONV_LCOPY: return &lconv_copy_kernel<T>;
+    case CONV_LTAPS: return &lconv_taps_kernel<T>;
     default: return nullptr;
   }
 }

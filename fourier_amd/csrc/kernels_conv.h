@@ -1,4 +1,4 @@
-// kernels_conv.h -- device code of the convolution handle's sweeps (ConvPlan, conv_plan.h).
+// kernels_conv.h -- device code of the convolution handles' sweeps (ConvPlan, conv_plan.h; LinearConvPlan, lconv_plan.h).
 //
 // conv_mul_kernel: the pointwise product of a batch of spectra with a filter bank, Z[b][k] *= H[(first + b) mod F][k], in place.
 // real_conv_mid_kernel: the middle of a real-data convolution of even length N = 2h, between the inner h-point plan's forward
@@ -84,6 +84,42 @@ __global__ void __launch_bounds__(256) conv_pad_kernel(ConvArgs a) {
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
     const uint64_t r = i / a.n, k = i - r * a.n;
     y[i] = k < a.taps ? x[r * a.taps + k] : (T)0;
+  }
+}
+
+// ---- the linear-convolution handle (LinearConvPlan, lconv_plan.h)
+// The pad and the crop sweep of its padded route: word k of output row r = word skip + k of input row r, zero beyond the input row.
+// One workgroup per LCONV_SEG words of an output row (flat index rows x segments, split by multiply-high, XCD-contiguous like the
+// other sweeps); a lane walks its segment with stride 256, so a wave moves whole lines.  Rows are addressed with 64-bit indices: their
+// lengths are not multiples of anything and a launch is bounded by its grid only.
+template <typename T>
+__global__ void __launch_bounds__(REAL_THREADS) lconv_copy_kernel(ConvArgs a) {
+  const uint32_t blk = real_xcd_block(blockIdx.x, gridDim.x);
+  const uint32_t row = real_div(blk, a.div_m, a.div_l), seg = blk - row * a.len;
+  const T* x = (const T*)a.in + (uint64_t)row * a.taps;
+  T* y = (T*)a.out + (uint64_t)row * a.n;
+  const uint64_t k0 = (uint64_t)seg * LCONV_SEG + threadIdx.x;
+#pragma unroll
+  for (uint32_t u = 0; u < LCONV_SEG / REAL_THREADS; ++u) {
+    const uint64_t k = k0 + u * REAL_THREADS;
+    if (k < a.n) y[k] = a.skip + k < a.taps ? x[a.skip + k] : (T)0;
+  }
+}
+// set_filters: filters of a.taps values -> rows of a.n values, zero-extended; a correlation (conj != 0) takes conj(h[K-1-k]) for h[k]
+template <typename T>
+__global__ void __launch_bounds__(256) lconv_taps_kernel(ConvArgs a) {
+  const uint64_t total = a.rows * a.n;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
+    const uint64_t r = i / a.n, k = i - r * a.n;
+    cpx<T> v = {(T)0, (T)0};
+    if (k < a.taps) {
+      const uint64_t src = r * a.taps + (a.conj ? a.taps - 1 - k : k);
+      if (a.real) v.re = ((const T*)a.in)[src];
+      else v = ((const cpx<T>*)a.in)[src];
+      if (a.conj) v.im = -v.im;
+    }
+    if (a.real && !a.widen) ((T*)a.out)[i] = v.re;
+    else ((cpx<T>*)a.out)[i] = v;
   }
 }
 

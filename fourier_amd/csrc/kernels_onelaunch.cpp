@@ -98,4 +98,24 @@ bool get_conv_small_kernel(Real<TUReal>, int k, KernelInfo& info) {
   }
 }
 
+// lconv_small_kernel: the overlap-save blocks of the linear-convolution handle on the same shapes, complex rows or real rows
+template <typename T, int L1, int L2> static KernelInfo make_lconv_small_info(bool real_data) {
+  KernelInfo k = make_twolevel_info<T, L1, L2>();
+  k.fn = real_data ? &lconv_small_kernel<T, L1, L2, true> : &lconv_small_kernel<T, L1, L2, false>;
+  return k;
+}
+bool get_lconv_small_kernel(Real<TUReal>, int k, bool real_data, KernelInfo& info) {
+  typedef TUReal T;
+  switch (k) {
+    case 11: info = make_lconv_small_info<T, 64, 32>(real_data); return true;
+    case 12: info = make_lconv_small_info<T, 64, 64>(real_data); return true;
+    case 13: info = make_lconv_small_info<T, 128, 64>(real_data); return true;
+    case 14: info = make_lconv_small_info<T, 128, 128>(real_data); return true;
+    case 15:
+      if constexpr (sizeof(T) == 4) { info = make_lconv_small_info<T, 256, 128>(real_data); return true; }
+      return false;
+    default: return false;
+  }
+}
+
 }  // namespace fourier_hip

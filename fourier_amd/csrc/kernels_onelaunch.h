@@ -472,4 +472,170 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
   }
 }
 
+// ---- linear convolution by overlap-save in ONE launch (the linear-convolution handle, lconv_plan.h) ----
+// conv_small_kernel on overlapping blocks of a row: workgroup w of the launch owns block j = w % wpr of row w / wpr (real data: the
+// pair of blocks 2j, 2j + 1).  Element i of block j is input position j*S - D + i of the row, D = N - S, zero outside [0, Lx); after
+// load -> FFT -> (.) H -> inverse its elements i >= D (the others are circularly contaminated) go to output position j*S + i - D - off
+// where that lies in [0, Lout).  Row lengths are run-time values: one descriptor per row and side with the row's byte count (at most
+// 2^31), and every access computes its predicate and takes LCONV_REJECT as its offset where it is rejected -- at or above every
+// descriptor's byte count, and far enough below 2^32 that an instruction's immediate offset cannot carry it back into range (a negative
+// position is never left to 32-bit wrap-around).  S is a whole number of 128-byte lines of complex data, so a block begins on a line of
+// its row and D is even: a 16-byte unit of two f32 values lies inside or outside the row at the lower end and is kept or dropped as
+// one; at the upper end the hardware's dword-wise range check cuts it.  Rows of odd length are 8-byte aligned in f32, which the
+// 16-byte buffer accesses tolerate (bluestein_small_kernel).  The cropped store has any parity (off): where the first kept output of
+// the block lies in front of the row (wave-uniform: the first block of a row), the unit is stored element by element.
+// REAL: the rows are reals (4-byte aligned in f32): block 2j is loaded as the real parts and block 2j + 1 as the imaginary parts (zeros
+// where the row has no such block), one value per access; the taps are real, so the real parts of the result are block 2j's outputs
+// and the imaginary parts block 2j + 1's.  Where Lx, Lout and off are even and both base pointers are 8-byte aligned (wave-uniform), an
+// f32 lane's two adjacent reals are 8-byte aligned in their rows and inside or outside them together: they move as one 8-byte access.
+constexpr uint32_t LCONV_REJECT = 0x80000000u;
+// one real (4 / 8 bytes) through a descriptor, bounds-checked like the units
+template <typename T, int AUX = BUF_PLAIN> __device__ __forceinline__ T buf_load_real(BufRsrc r, uint32_t voff) {
+  T y;
+#ifdef FOURIER_EMU
+  y = (T)0;
+  if ((uint64_t)voff + sizeof(T) <= r.num_records) memcpy(&y, r.base + voff, sizeof(T));
+#else
+  if constexpr (sizeof(T) == 4) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, AUX);
+    __builtin_memcpy(&y, &v, 4);
+  } else {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, 0, AUX);
+    __builtin_memcpy(&y, &v, 8);
+  }
+#endif
+  return y;
+}
+template <typename T, int AUX = BUF_PLAIN> __device__ __forceinline__ void buf_store_real(BufRsrc r, uint32_t voff, T y) {
+#ifdef FOURIER_EMU
+  if ((uint64_t)voff + sizeof(T) <= r.num_records) memcpy(r.base + voff, &y, sizeof(T));
+#else
+  if constexpr (sizeof(T) == 4) {
+    decltype(__builtin_amdgcn_raw_buffer_load_b32(r, 0, 0, 0)) v;
+    __builtin_memcpy(&v, &y, 4);
+    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, 0, AUX);
+  } else {
+    decltype(__builtin_amdgcn_raw_buffer_load_b64(r, 0, 0, 0)) v;
+    __builtin_memcpy(&v, &y, 8);
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)voff, 0, AUX);
+  }
+#endif
+}
+// two adjacent f32 reals (8 bytes) through a descriptor
+template <typename T, int AUX = BUF_PLAIN> __device__ __forceinline__ cpx<T> buf_load_pair(BufRsrc r, uint32_t voff) {
+  static_assert(sizeof(T) == 4, "pairs of f32 values");
+  cpx<T> y;
+  const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, 0, AUX);
+  __builtin_memcpy(&y, &v, 8);
+  return y;
+}
+template <typename T, int L1, int L2, bool REAL>
+__global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SMALL_MIN_WAVES(FOURIER_TWOLEVEL_NT(T, L1, L2)))
+    lconv_small_kernel(PassArgs a) {
+  constexpr int VEC = 16 / (2 * (int)sizeof(T));
+  constexpr int CG1 = L2 / VEC, CG2 = L1 / VEC, Q1 = L1 / 16, Q2 = L2 / 16, N = L1 * L2;
+  FOURIER_DYN_SMEM(smem);
+  const int tid = (int)threadIdx.x;
+  const uint32_t blk = (uint32_t)onelaunch_block(a);
+  const uint32_t hi = (uint32_t)(((uint64_t)blk * a.lc_m) >> 32);
+  const uint32_t row = (uint32_t)(((uint64_t)hi + blk) >> a.lc_l), w = blk - row * a.lc_wpr;
+  constexpr uint32_t VS = (uint32_t)(REAL ? sizeof(T) : sizeof(cpx<T>));  // bytes of one value of a row
+  constexpr uint32_t NBYTES = (uint32_t)(N * sizeof(cpx<T>));
+  const uint32_t S = a.lc_step, D = (uint32_t)N - S, lx = a.lc_lx, lout = a.lc_lout;
+  const uint32_t j0 = REAL ? 2 * w : w;
+  // the second block of a real pair where the row has one: its lengths are zero otherwise, and every access to it is rejected
+  const uint32_t lx2 = j0 + 1 < a.lc_nb ? lx : 0, lout2 = j0 + 1 < a.lc_nb ? lout : 0;
+  const uint32_t p0 = j0 * S - D;               // row position of element 0 of the block, modulo 2^32: compared, never used as an offset
+  const uint32_t q0 = j0 * S - D - a.lc_off;    // output position of element 0
+  const BufRsrc ri = make_rsrc((const char*)a.in + (uint64_t)row * lx * VS, lx * VS);
+  const BufRsrc ro = make_rsrc((char*)a.out + (uint64_t)row * lout * VS, lout * VS);
+  // f32 real rows whose lanes may move their two reals as one 8-byte access (see above)
+  const bool pairs = REAL && VEC == 2 && ((lx | lout | a.lc_off) & 1u) == 0 && (((uint64_t)a.in | (uint64_t)a.out) & 7u) == 0;
+  cpx<T> x[VEC][16];
+  {
+    const int th = tid / CG1, cg = tid % CG1;
+    const uint32_t pe = p0 + (uint32_t)(th * L2 + cg * VEC);  // register r holds element (th + Q1*r)*L2 + cg*VEC + v
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t p = pe + (uint32_t)(r * Q1 * L2);
+      if constexpr (REAL && VEC == 2) {
+        if (pairs) {
+          const uint32_t pb = p + S;
+          const cpx<T> re = buf_load_pair<T, BUF_NT>(ri, p < lx ? p * VS : LCONV_REJECT);
+          const cpx<T> im = buf_load_pair<T, BUF_NT>(ri, pb < lx2 ? pb * VS : LCONV_REJECT);
+          x[0][r] = {re.re, im.re};
+          x[1][r] = {re.im, im.im};
+          continue;
+        }
+      }
+      if constexpr (REAL) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          const uint32_t pa = p + (uint32_t)v, pb = pa + S;
+          x[v][r].re = buf_load_real<T, BUF_NT>(ri, pa < lx ? pa * VS : LCONV_REJECT);
+          x[v][r].im = buf_load_real<T, BUF_NT>(ri, pb < lx2 ? pb * VS : LCONV_REJECT);
+        }
+      } else {
+        const Unit16<T> u = buf_load_unit<T, BUF_NT>(ri, p < lx ? p * VS : LCONV_REJECT);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) x[v][r] = {u.a[2 * v], u.a[2 * v + 1]};
+      }
+    }
+  }
+  twolevel_core<T, L1, L2>(x, tid, smem, (const cpx<T>*)a.tw1, (const cpx<T>*)a.tw2, (const cpx<T>*)a.tw_lo, 0);
+  {  // (.) H of the row's filter, then the inverse's leading swap (conv_small_kernel)
+    int tb = tid;
+    FOURIER_LAUNDER(tb);
+    const cpx<T>* wt = (const cpx<T>*)a.mul + (uint64_t)((a.bank_first + row) % a.bank_filters) * N;
+    const BufRsrc rw = make_rsrc(wt, NBYTES);
+    const uint32_t woff = (uint32_t)(((tb / CG2) * L1 + (tb % CG2) * VEC) * sizeof(cpx<T>));
+    onelaunch_times_table_swap<T, L1, Q2>(x, rw, woff);
+  }
+  __syncthreads();
+  {
+    int t2 = tid;
+    FOURIER_LAUNDER(t2);
+    twolevel_core<T, L2, L1>(x, t2, smem, (const cpx<T>*)a.tw2, (const cpx<T>*)a.tw1, (const cpx<T>*)a.tw_hi, 32);
+  }
+  // back in the input's layout; the trailing swap: the result is (x.im, x.re)
+  {
+    int tb = tid;
+    FOURIER_LAUNDER(tb);
+    const uint32_t ie = (uint32_t)((tb / CG1) * L2 + (tb % CG1) * VEC);
+    const bool low = (int32_t)(q0 + D) < 0;  // the first kept output of this block lies in front of the row
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t i = ie + (uint32_t)(r * Q1 * L2), q = q0 + i;
+      const bool keep = i >= D;
+      if constexpr (REAL && VEC == 2) {
+        if (pairs) {
+          const uint32_t qb = q + S;
+          buf_store_elem<T, BUF_NT>(ro, keep && q < lout ? q * VS : LCONV_REJECT, cpx<T>{x[0][r].im, x[1][r].im});
+          buf_store_elem<T, BUF_NT>(ro, keep && qb < lout2 ? qb * VS : LCONV_REJECT, cpx<T>{x[0][r].re, x[1][r].re});
+          continue;
+        }
+      }
+      if constexpr (REAL) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          const uint32_t qa = q + (uint32_t)v, qb = qa + S;
+          buf_store_real<T, BUF_NT>(ro, keep && qa < lout ? qa * VS : LCONV_REJECT, x[v][r].im);
+          buf_store_real<T, BUF_NT>(ro, keep && qb < lout2 ? qb * VS : LCONV_REJECT, x[v][r].re);
+        }
+      } else if (VEC == 1 || !low) {
+        Unit16<T> u;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) { u.a[2 * v] = x[v][r].im; u.a[2 * v + 1] = x[v][r].re; }
+        buf_store_unit<T, BUF_NT>(ro, keep && q < lout ? q * VS : LCONV_REJECT, u);
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          const uint32_t qv = q + (uint32_t)v;
+          buf_store_elem<T, BUF_NT>(ro, keep && qv < lout ? qv * VS : LCONV_REJECT, cpx<T>{x[v][r].im, x[v][r].re});
+        }
+      }
+    }
+  }
+}
+
 FOURIER_KERNELS_END  // namespace fourier_hip

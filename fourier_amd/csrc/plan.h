@@ -571,6 +571,20 @@ template <typename T> class Plan : public HandleBase {
     return true;
   }
 
+  // ---- the hook of the linear-convolution handle (LinearConvPlan, lconv_plan.h); exec() is not affected.  A one-launch two-level plan
+  // (2^11 ... 2^15, f64 ... 2^14) runs the overlap-save blocks of `rows` rows in one launch of lconv_small_kernel; the bank is laid out as
+  // exec_conv's, row b of the call uses table (first + b) mod filters.  The caller keeps rows * g.wpr below 2^31.
+  bool enable_lconv(bool real_data) {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_lconv_small(real_data);
+  }
+  void exec_lconv(const void* d_in, void* d_out, size_t rows, const void* bank, size_t filters, size_t first, bool real_data,
+                  const LconvGeom& geo, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_lconv_small(d_in, d_out, rows, bank, (uint32_t)filters, (uint32_t)(first % filters), real_data, geo, stream, nxcd_);
+  }
+
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).
   void synchronize(hipStream_t stream) const {
     DeviceGuard g(device_);

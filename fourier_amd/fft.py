@@ -459,6 +459,106 @@ def fftconv(x, taps, correlate=False, out=None):
     return p.apply(x, out)
 
 
+LCONV_MODES = {"full": 0, "same": 1, "valid": 2}  # FOURIER_LCONV_FULL ... FOURIER_LCONV_VALID
+
+
+class LinearConv(_Handle):
+    """Batched linear convolution / correlation with a prepared filter bank (include/fourier.h, fourier_hip_lconv_*) on device memory:
+    rows of `length` values in, rows of out_length() values out ("full", "same", "valid" as numpy.convolve), row b with filter b mod F;
+    complex rows with complex taps (real_data=False) or real rows with real taps (real_data=True).  The filters are given in the time
+    domain (set_filters) and transformed once."""
+
+    _prefix = "fourier_hip_lconv_"
+    _destroy = "fourier_hip_lconv_destroy"
+
+    def __init__(self, length, taps, real="f32", mode="full", real_data=False, device=-1):
+        if mode not in LCONV_MODES:
+            raise ValueError(f"mode must be one of {sorted(LCONV_MODES)}, got {mode!r}")
+        self.real_data = bool(real_data)
+        self.mode = mode
+        self._create(real, f"linear convolution plan of length {length}, {taps} taps, mode {mode}", int(length), int(taps),
+                     LCONV_MODES[mode], int(self.real_data), int(device))
+        self._lx, self._k = int(length), int(taps)
+        self._lout = int(self._fn("out_length")(self._h))
+
+    def length(self):
+        return self._lx
+
+    def taps(self):
+        return self._k
+
+    def out_length(self):
+        return self._lout
+
+    def filters(self):
+        return int(self._fn("filters")(self._h))
+
+    def set_option(self, key, value):
+        """"block": 11 ... 15 forces the overlap-save block 2^value, 0 = the rule; "overlap_save": 0 = the padded route, 1 (default).
+        A change of route or block drops the bank: set the filters again."""
+        self._call("set_option", key.encode(), int(value))
+
+    def set_filters_ptr(self, d_taps, filters=1, correlate=False, stream=0):
+        """`filters` rows of taps() values of the handle's kind at d_taps -> the bank, enqueued on `stream`."""
+        self._call("set_filters", d_taps, int(filters), int(bool(correlate)), stream)
+
+    def apply_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of length() values at d_in -> `batch` rows of out_length() values at d_out (no overlap), enqueued on `stream`."""
+        self._call("apply", d_in, d_out, int(batch), stream)
+
+    def _dtype(self):
+        return _torch_dtypes(self.real)[0 if self.real_data else 1]
+
+    def set_filters(self, taps, correlate=False):
+        """Contiguous CUDA tensor of shape (K,) or (F, K), of the handle's dtype; on the current stream."""
+        _require_cuda(taps, self._dtype())
+        if taps.dim() not in (1, 2) or taps.numel() == 0 or taps.shape[-1] != self._k:
+            raise ValueError(f"taps must have shape ({self._k},) or (F, {self._k}), got {tuple(taps.shape)}")
+        self.set_filters_ptr(taps.data_ptr(), taps.numel() // self._k, correlate, _stream(taps))
+
+    def apply(self, x, out=None):
+        """Contiguous (..., length) CUDA tensor of the handle's dtype -> a new (..., out_length) tensor, or `out` (which may not
+        overlap `x`), on the current stream.  Row b of the flattened leading dimensions uses filter b mod F."""
+        import torch
+
+        _require_cuda(x, self._dtype())
+        if x.dim() == 0 or x.shape[-1] != self._lx:
+            raise ValueError(f"last dimension must be {self._lx}, got {tuple(x.shape)}")
+        shape = tuple(x.shape[:-1]) + (self._lout,)
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        else:
+            _require_out(out, shape, x.dtype, x.device)
+        batch = x.numel() // self._lx
+        if batch:
+            self.apply_ptr(x.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+
+def create_lconv_f32(length, taps, mode="full", real_data=False, device=-1):
+    return LinearConv(length, taps, "f32", mode, real_data, device)
+
+
+def create_lconv_f64(length, taps, mode="full", real_data=False, device=-1):
+    return LinearConv(length, taps, "f64", mode, real_data, device)
+
+
+def fftconvolve(x, taps, mode="full", correlate=False, out=None):
+    """Linear convolution (or correlation) of the rows of a contiguous (..., Lx) CUDA tensor with `taps` of shape (K,) or (F, K) and
+    the same dtype, numpy.convolve's "full" / "same" / "valid" (numpy.correlate's with correlate=True): complex64 / complex128 rows, or
+    float32 / float64 rows (real data).  Handles are cached per (Lx, K, dtype, mode, device) and the filters are set on EVERY call; keep
+    a LinearConv to apply the same filters repeatedly."""
+    _require_cuda(x, *_torch_dtypes("f32"), *_torch_dtypes("f64"))
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    if not _is_torch(taps) or taps.dim() not in (1, 2) or taps.numel() == 0:
+        raise TypeError("taps must be a tensor of shape (K,) or (F, K)")
+    real, real_data = _precision(x.dtype)
+    p = _cached_plan(LinearConv, int(x.shape[-1]), int(taps.shape[-1]), real, mode, real_data, int(_device_index(x)))
+    p.set_filters(taps, correlate)
+    return p.apply(x, out)
+
+
 R2R_KINDS = {("dct", 2): 0, ("dct", 3): 1, ("dst", 2): 2, ("dst", 3): 3}  # FOURIER_R2R_DCT2 ... FOURIER_R2R_DST3
 R2R_NORMS = {None: 0, "backward": 0, "ortho": 1, "forward": 2}             # FOURIER_R2R_NORM_*
 

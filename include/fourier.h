@@ -438,8 +438,7 @@ const char *fourier_hip_describe_axis_double(const FOURIER_STRUCT fourier_fft_do
  *   convolution (circular, length N)   y[b] = ifft(fft(x[b]) * fft(h[b mod F], N))
  *   correlation (correlate != 0)       y[b] = ifft(fft(x[b]) * conj(fft(h[b mod F], N))),  y[b][n] = sum_m x[b][(n+m) mod N] conj(h[m])
  * scaled as numpy's ifft / irfft (the 1/N lives in the stored spectra).  Real data: real taps, real rows in and out; the half
- * spectrum never leaves the library.  A linear ("full", "same", causal) convolution is the caller's zero padding to a length
- * N >= len(x) + taps - 1.
+ * spectrum never leaves the library.  A linear ("full", "same", "valid") convolution is fourier_hip_lconv_* below.
  * d_in == d_out is in place and allowed; any other overlap, a NULL pointer, a pointer not aligned to 2*sizeof(T) (also for real
  * rows; taps: one value of their kind), taps == 0, taps > N, filters == 0, or apply before any filters were set give
  * FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.  Both calls are stream-ordered on `stream` like
@@ -501,6 +500,88 @@ const char *fourier_hip_conv_describe_float(const FOURIER_STRUCT fourier_conv_fl
 const char *fourier_hip_conv_describe_double(const FOURIER_STRUCT fourier_conv_double *);
 int fourier_hip_conv_last_status_float(const FOURIER_STRUCT fourier_conv_float *);
 int fourier_hip_conv_last_status_double(const FOURIER_STRUCT fourier_conv_double *);
+
+/* ---------------- linear convolution with a prepared filter bank by overlap-save (extension; the reference has none) ----------
+ * A handle is made for a row length Lx >= 1, a tap count K >= 1, a mode, a kind of data (real_data == 0: rows of interleaved complex
+ * T with complex taps, else rows of reals T with real taps) and a device.  It holds a bank of F >= 1 filters of K taps, given in the
+ * time domain as `filters` contiguous rows of K values of the handle's kind and transformed once by fourier_hip_lconv_set_filters_*.
+ * fourier_hip_lconv_apply_* maps `batch` contiguous rows of Lx values at d_in to `batch` contiguous rows of Lout values at d_out on
+ * DEVICE memory, row b with filter b mod F (b counted over the whole call):
+ *   full[b] = x[b] * h[b mod F]          the linear convolution of Lx + K - 1 values, numpy.convolve(x, h)
+ *   y[b]    = full[b][off : off + Lout]  FOURIER_LCONV_FULL   off = 0,          Lout = Lx + K - 1
+ *                                        FOURIER_LCONV_SAME   off = (K - 1) / 2, Lout = Lx          (integer division)
+ *                                        FOURIER_LCONV_VALID  off = K - 1,      Lout = Lx - K + 1  (needs K <= Lx)
+ * the lengths of scipy.signal.fftconvolve for K <= Lx.  With correlate != 0 set_filters stores conj(h[K-1-i]) in place of h[i], and
+ * the rows are numpy.correlate(x, h, mode); apply does not know about it.
+ * d_in and d_out may not overlap at all (d_in == d_out included: the blocks of a row overlap and the row strides differ); an overlap,
+ * a NULL pointer, a pointer not aligned to one value of the handle's kind, filters == 0 or apply before any filters were set give
+ * FOURIER_HIP_INVALID_ARGUMENT; create returns NULL for Lx == 0, K == 0, an unknown mode, FOURIER_LCONV_VALID with K > Lx, and for rows
+ * of more than 2^31 bytes on either side.  batch == 0 is a successful no-op.  Calls are stream-ordered on `stream` like
+ * fourier_hip_conv_*.
+ * Routes, chosen at create and named by fourier_hip_lconv_describe_*:
+ *   "lconv overlap-save: block N step S blocks nb[ real pairs], <block plan>"   ONE launch per apply, no scratch.  Every row is cut
+ *     into nb = ceil((Lx + K - 1) / S) overlapping blocks of N = 2^11 ... 2^15 (f64: ... 2^14) values, S = floor((N - (K - 1)) / A) * A
+ *     with A = 128 / (2 sizeof(T)) values (one 128-byte line of complex data).  One workgroup loads block j from position j*S - (N - S)
+ *     of its row (zeros outside the row), transforms it on register-resident data, multiplies by the filter's N-point spectrum,
+ *     transforms back, drops the first N - S values and stores the others at j*S - off where that lies in the output row.  Real rows:
+ *     one workgroup takes blocks 2j and 2j + 1 as the real and the imaginary part of one complex block (the taps are real); float
+ *     rows of even Lx, Lout and off at 8-byte aligned pointers move two reals per access, all others one.  The
+ *     bank is F x N complex values in both kinds.  Bytes per row, algorithmic: (Lx + Lout) values; the N - S values neighbouring
+ *     blocks share are read twice, the second time from the L2.
+ *   "lconv padded: M=..., <circular handle>"   filters too long for a block, or option "overlap_save" = 0: the rows zero-padded into
+ *     the handle's scratch, the circular handle (fourier_hip_conv_*) of M = the smallest power of two >= Lx + K - 1 in place there,
+ *     a crop sweep to the output: the circular handle's bytes per row of M values plus (Lx + M) and (M + Lout) values for the two
+ *     sweeps.  The batch is walked in chunks of a scratch of at most 1 GiB (never less than one row); fourier_hip_lconv_reserve_*
+ *     for `batch` rows makes later apply calls of at most `batch` rows allocation-free (the overlap-save route has nothing to size).
+ * Block rule: float handles first take the smallest N = 2^11 ... 2^13 with N >= 8 (K - 1) where the row has more than one such block
+ * (N < Lx + K - 1; measured faster than the next rule's block there); then, and double handles at once, the smallest N = 2^11 ...
+ * with N >= 4 (K - 1); where there is none, the largest N if N >= 2 (K - 1); else the padded route.  Options (fourier_hip_lconv_set_option_*): "block" = 11 ... 15 forces N = 2^value (FOURIER_HIP_INVALID_ARGUMENT where the
+ * precision has no such block or N < K - 1 + A), 0 = the rule; "overlap_save" = 0 selects the padded route, 1 (default) the rule.
+ * An option that changes the route or the block drops the bank: set the filters again.  Handles are Send, not Sync; the status of the
+ * last call that did work (set_filters, apply, reserve) is fourier_hip_lconv_last_status_*. */
+enum fourier_lconv_mode {
+  FOURIER_LCONV_FULL = 0,
+  FOURIER_LCONV_SAME = 1,
+  FOURIER_LCONV_VALID = 2,
+};
+struct fourier_lconv_float;
+struct fourier_lconv_double;
+
+/* NULL on failure. */
+struct fourier_lconv_float *fourier_hip_lconv_create_float(FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE taps, int mode, int real_data,
+                                                           int device);
+struct fourier_lconv_double *fourier_hip_lconv_create_double(FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE taps, int mode, int real_data,
+                                                             int device);
+/* NULL is a no-op. */
+void fourier_hip_lconv_destroy_float(FOURIER_STRUCT fourier_lconv_float *);
+void fourier_hip_lconv_destroy_double(FOURIER_STRUCT fourier_lconv_double *);
+/* Lx, K, Lout, F (0 before set_filters); 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_lconv_length_float(const FOURIER_STRUCT fourier_lconv_float *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_length_double(const FOURIER_STRUCT fourier_lconv_double *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_taps_float(const FOURIER_STRUCT fourier_lconv_float *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_taps_double(const FOURIER_STRUCT fourier_lconv_double *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_out_length_float(const FOURIER_STRUCT fourier_lconv_float *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_out_length_double(const FOURIER_STRUCT fourier_lconv_double *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_filters_float(const FOURIER_STRUCT fourier_lconv_float *);
+FOURIER_SIZE_TYPE fourier_hip_lconv_filters_double(const FOURIER_STRUCT fourier_lconv_double *);
+/* `filters` rows of K values of the handle's kind at d_taps -> the bank. */
+int fourier_hip_lconv_set_filters_float(FOURIER_STRUCT fourier_lconv_float *, const void *d_taps, FOURIER_SIZE_TYPE filters,
+                                        int correlate, void *stream);
+int fourier_hip_lconv_set_filters_double(FOURIER_STRUCT fourier_lconv_double *, const void *d_taps, FOURIER_SIZE_TYPE filters,
+                                        int correlate, void *stream);
+int fourier_hip_lconv_apply_float(const FOURIER_STRUCT fourier_lconv_float *, const void *d_in, void *d_out,
+                                  FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_lconv_apply_double(const FOURIER_STRUCT fourier_lconv_double *, const void *d_in, void *d_out,
+                                  FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_lconv_reserve_float(const FOURIER_STRUCT fourier_lconv_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_lconv_reserve_double(const FOURIER_STRUCT fourier_lconv_double *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_lconv_set_option_float(FOURIER_STRUCT fourier_lconv_float *, const char *key, long long value);
+int fourier_hip_lconv_set_option_double(FOURIER_STRUCT fourier_lconv_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_lconv_describe_float(const FOURIER_STRUCT fourier_lconv_float *);
+const char *fourier_hip_lconv_describe_double(const FOURIER_STRUCT fourier_lconv_double *);
+int fourier_hip_lconv_last_status_float(const FOURIER_STRUCT fourier_lconv_float *);
+int fourier_hip_lconv_last_status_double(const FOURIER_STRUCT fourier_lconv_double *);
 
 /* ---------------- real-to-real transforms: DCT and DST of types II and III (extension; the reference has none) ----------
  * Batched discrete cosine / sine transforms of length N >= 1 on DEVICE memory, scipy.fft's dct / dst definitions (FFTW's REDFT10,
@@ -747,6 +828,53 @@ template <typename T> struct conv;
 FOURIER_DEFINE_CXX_CONV_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CONV_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CONV_WRAPPER
+
+/* linear convolution with a prepared filter bank on device memory (extension): fourier::lconv<float> / <double> */
+template <typename T> struct lconv;
+
+#define FOURIER_DEFINE_CXX_LCONV_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct lconv<T> {                                                                     \
+    lconv(std::size_t length, std::size_t taps, int mode = ::fourier::c::FOURIER_LCONV_FULL,        \
+          bool real_data = false, int device = -1)                                                  \
+        : impl(::fourier::c::fourier_hip_lconv_create_##SUFFIX(length, taps, mode, real_data ? 1 : 0, device), \
+               ::fourier::c::fourier_hip_lconv_destroy_##SUFFIX) {}                                 \
+    lconv() = delete;                                                                               \
+    lconv(const lconv &) = delete;                                                                  \
+    lconv(lconv &&) = default;                                                                      \
+    lconv &operator=(const lconv &) = delete;                                                       \
+    lconv &operator=(lconv &&) = default;                                                           \
+    ~lconv() = default;                                                                             \
+    std::size_t length() const { return ::fourier::c::fourier_hip_lconv_length_##SUFFIX(impl.get()); } \
+    std::size_t taps() const { return ::fourier::c::fourier_hip_lconv_taps_##SUFFIX(impl.get()); }  \
+    std::size_t out_length() const { return ::fourier::c::fourier_hip_lconv_out_length_##SUFFIX(impl.get()); } \
+    std::size_t filters() const { return ::fourier::c::fourier_hip_lconv_filters_##SUFFIX(impl.get()); } \
+    /* `filters` rows of taps() values of the handle's kind -> the bank */                          \
+    int set_filters_device(const void *d_taps, std::size_t filters = 1, bool correlate = false,     \
+                           void *stream = nullptr) {                                                \
+      return ::fourier::c::fourier_hip_lconv_set_filters_##SUFFIX(impl.get(), d_taps, filters,      \
+                                                                  correlate ? 1 : 0, stream);       \
+    }                                                                                               \
+    /* `batch` rows of length() values -> `batch` rows of out_length() values, row b with filter b mod F */ \
+    int apply_device(const void *d_in, void *d_out, std::size_t batch, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_lconv_apply_##SUFFIX(impl.get(), d_in, d_out, batch, stream); \
+    }                                                                                               \
+    int reserve(std::size_t batch) const {                                                          \
+      return ::fourier::c::fourier_hip_lconv_reserve_##SUFFIX(impl.get(), batch);                   \
+    }                                                                                               \
+    int set_option(const char *key, long long value) {                                              \
+      return ::fourier::c::fourier_hip_lconv_set_option_##SUFFIX(impl.get(), key, value);           \
+    }                                                                                               \
+    const char *describe() const { return ::fourier::c::fourier_hip_lconv_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_lconv_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                              \
+                                                                                                    \
+  private:                                                                                          \
+    ::std::unique_ptr<::fourier::c::fourier_lconv_##SUFFIX,                                         \
+                      void (*)(::fourier::c::fourier_lconv_##SUFFIX *)> impl;                       \
+  };
+FOURIER_DEFINE_CXX_LCONV_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_LCONV_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_LCONV_WRAPPER
 
 /* real-input N-D transforms on device memory (extension): fourier::real_fft_nd<float> / <double> */
 template <typename T> struct real_fft_nd;
