@@ -18,6 +18,7 @@
 #include "conv_plan.h"
 #include "lconv_plan.h"
 #include "r2r_plan.h"
+#include "stft_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -259,6 +260,55 @@ FOURIER_DEFINE_LCONV_ABI(double, double)
 
 FOURIER_DEFINE_R2R_ABI(float, float)
 FOURIER_DEFINE_R2R_ABI(double, double)
+
+// short-time Fourier transform and its inverse (fourier_hip_stft_*)
+#define FOURIER_DEFINE_STFT_ABI(T, SUFFIX)                                                                       \
+  extern "C" fc::fourier_stft_##SUFFIX* fourier_hip_stft_create_##SUFFIX(size_t n_fft, size_t hop, size_t win_length, int pad_mode, \
+                                                                         int device) {                           \
+    return (fc::fourier_stft_##SUFFIX*)create_handle<StftPlan<T>>(n_fft, hop, win_length, pad_mode, device);     \
+  }                                                                                                              \
+  extern "C" void fourier_hip_stft_destroy_##SUFFIX(fc::fourier_stft_##SUFFIX* h) { destroy_handle<StftPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_stft_describe_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) { return describe_handle<StftPlan<T>>(h); } \
+  extern "C" int fourier_hip_stft_last_status_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) { return last_status_of<StftPlan<T>>(h); } \
+  extern "C" int fourier_hip_stft_set_option_##SUFFIX(fc::fourier_stft_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<StftPlan<T>>(h, key, v);                                                            \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_stft_n_fft_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) {                        \
+    return h ? ((const StftPlan<T>*)h)->n_fft() : 0;                                                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_stft_hop_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) {                          \
+    return h ? ((const StftPlan<T>*)h)->hop() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_stft_win_length_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) {                   \
+    return h ? ((const StftPlan<T>*)h)->win_length() : 0;                                                        \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_stft_bins_##SUFFIX(const fc::fourier_stft_##SUFFIX* h) {                         \
+    return h ? ((const StftPlan<T>*)h)->bins() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_stft_frames_##SUFFIX(const fc::fourier_stft_##SUFFIX* h, size_t length) {        \
+    return h ? ((const StftPlan<T>*)h)->frames(length) : 0;                                                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_stft_set_window_##SUFFIX(fc::fourier_stft_##SUFFIX* h, const void* d_window, void* stream) { \
+    StftPlan<T>* p = (StftPlan<T>*)h;                                                                            \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_stft_reserve_##SUFFIX(const fc::fourier_stft_##SUFFIX* h, size_t length, size_t batch) { \
+    const StftPlan<T>* p = (const StftPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_stft_forward_##SUFFIX(const fc::fourier_stft_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                   size_t batch, int normalized, void* stream) {                 \
+    const StftPlan<T>* p = (const StftPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, length, batch, normalized != 0, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_stft_inverse_##SUFFIX(const fc::fourier_stft_##SUFFIX* h, const void* d_in, void* d_out, size_t frames, \
+                                                   size_t length, size_t batch, int normalized, void* stream) {  \
+    const StftPlan<T>* p = (const StftPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, frames, length, batch, normalized != 0, (hipStream_t)stream); }); \
+  }
+
+FOURIER_DEFINE_STFT_ABI(float, float)
+FOURIER_DEFINE_STFT_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -170,6 +170,9 @@ typedef void (*GenKernel)(GenArgs);
 typedef void (*BluKernel)(BluArgs);
 typedef void (*RealKernel)(RealArgs);
 typedef void (*R2RKernel)(R2RArgs);
+typedef void (*StftKernel)(StftArgs);
+// the fused frame route of the STFT handle on a whole-row kernel's tile shape (kernels_stft.h); fn == nullptr: none for that length
+struct StftRowsKernel { StftKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -253,6 +256,10 @@ template <typename T> struct Real {};
   RealKernel get_real_kernel(Real<T>, int which);                                                                      \
   /* kernels_r2r.cpp: the sweeps of the DCT / DST handle, which = R2R_PACK ... R2R_ODD_PART (kernel_args.h) */             \
   R2RKernel get_r2r_kernel(Real<T>, int which);                                                                        \
+  /* kernels_stft.cpp: the frame gather and the overlap-add of the STFT handle, which = STFT_FRAME / STFT_OLA; its fused */ \
+  /* frame route for n_fft = 2 L on the whole-row kernel of length L                                                   */ \
+  StftKernel get_stft_kernel(Real<T>, int which);                                                                      \
+  StftRowsKernel get_stft_rows_kernel(Real<T>, int L);                                                                 \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \

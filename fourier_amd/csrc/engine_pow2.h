@@ -265,6 +265,25 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, (uint64_t)rows * g.wpr, k.NT, k.smem, stream, a);
   }
 
+  // The fused frame route of the STFT handle (stft_rows_kernel; stft_plan.h): available when this plan, of h = n_fft / 2 points, is ONE
+  // whole-row pass and kernels_stft.cpp holds the kernel on that pass's tile shape; it runs on this plan's stage tables.
+  bool enable_stft_rows() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
+    if (stft_rows_.fn) return true;
+    const StftRowsKernel k = get_stft_rows_kernel(Real<T>{}, passes_[0]->k.L);
+    if (!k.fn || k.L != passes_[0]->k.L) return false;
+    raise_smem_limit((const void*)k.fn, k.smem);
+    stft_rows_ = k;
+    return true;
+  }
+  // a: everything but the stage tables; a.total frames, below 2^31 workgroups (the caller bounds a launch)
+  void run_stft_rows(StftArgs a, hipStream_t stream) const {
+    if (a.total == 0) return;
+    const Pass& ps = *passes_[0];
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st->tw2.p;
+    launch(nullptr, 0, stft_rows_.fn, (a.total + stft_rows_.COLS - 1) / stft_rows_.COLS, stft_rows_.NT, stft_rows_.smem, stream, a);
+  }
+
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
   void init_l2fused(int k) {
     FusedInfo fi;
@@ -659,6 +678,7 @@ template <typename T> class Pow2Engine {
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   StageTables<T>* conv_st_ = nullptr;
+  StftRowsKernel stft_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -196,6 +196,34 @@ struct R2RArgs {
   uint64_t n, rows;           // odd N: real length, rows in this launch
 };
 
+// ---- short-time Fourier transform (kernels_stft.h; StftPlan, stft_plan.h)
+// A launch covers `total` items counted from a row base: `in` (forward) or `out` (inverse) points at the first sample of signal row 0
+// of the launch.  Forward (stft_frame_kernel, stft_rows_kernel): item i is frame x = first + i of the flat frame index row * frames + f,
+// row = x / frames by multiply-high (first < frames, x < 2^32); its sample n is xpad[f * hop - pad + n], the padding by index arithmetic
+// (mode = FOURIER_STFT_PAD_*), times win[n]; the frame kernel writes rows of n_fft reals at out + i * n_fft, the fused kernel the h + 1
+// bins at out + i * (h + 1).  Inverse (istft_ola_kernel): one lane per output sample of `rows` rows, sample t = t0 + i of `span` samples
+// per row; frames f_lo ... f_lo + nfr - 1 of every row lie in `in` as rows of n_fft reals (row r at (r * nfr + f - f_lo) * n_fft), and
+//   y[t] = scale * env[t] * sum_f win[t + pad - f hop] * frame_f[t + pad - f hop]   over the frames that cover t.
+enum { STFT_FRAME = 0, STFT_OLA = 1 };
+enum { STFT_PAD_NONE = 0, STFT_PAD_REFLECT = 1, STFT_PAD_ZERO = 2 };  // FOURIER_STFT_PAD_* (include/fourier.h)
+struct StftArgs {
+  const void* in; void* out;
+  const void* win;            // the window, zero-extended to n_fft reals
+  const void* env;            // inverse: 1 / sum_f win^2, `length` reals
+  const void* tw;             // fused: W_N^j, j <= N / 4 (real_untangle_twiddles)
+  const void* tw1; const void* tw2;  // fused: the row core's stage tables
+  uint64_t length;            // reals per signal row
+  uint64_t total;             // forward: frames of this launch; inverse: rows * span
+  uint32_t frames;            // frames per signal row
+  uint32_t first;             // forward: frame index (within row 0 of the launch) of item 0
+  uint32_t fr_m, fr_l;        // x / frames = (umulhi(x, fr_m) + x) >> fr_l
+  uint32_t n_fft, hop, pad, mode;
+  int pairs;                  // fused: every interior frame starts on an even element of a 2 * sizeof(T)-aligned row
+  uint64_t t0, span, rows;    // inverse: first sample of the range, samples per row in it, rows
+  uint64_t f_lo, nfr;         // inverse: first frame in the scratch, frames per row there
+  double scale;
+};
+
 // ---- convolution with a filter bank (kernels_conv.h; ConvPlan, conv_plan.h)
 // conv_mul_kernel: Z[b][k] *= H[(first + b) mod filters][k] over a flat index of rows x len, one lane per element.
 // real_conv_mid_kernel: one lane per mirrored pair (j, h - j) of a row of the inner plan's output, as the real sweeps (`len` = h / 2 + 1

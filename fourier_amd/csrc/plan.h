@@ -585,6 +585,18 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_lconv_small(d_in, d_out, rows, bank, (uint32_t)filters, (uint32_t)(first % filters), real_data, geo, stream, nxcd_);
   }
 
+  // ---- the hook of the STFT handle (StftPlan, stft_plan.h); exec() is not affected.  A plan of h points that is one whole-row pass runs
+  // the frames of n_fft = 2h samples in one launch of stft_rows_kernel (gather, window, transform, untangle).
+  bool enable_stft() {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_stft_rows();
+  }
+  void exec_stft(const StftArgs& a, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_stft_rows(a, stream);
+  }
+
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).
   void synchronize(hipStream_t stream) const {
     DeviceGuard g(device_);

@@ -669,6 +669,195 @@ def idst(x, type=2, norm=None, dim=-1, out=None):
     return _r2r("dst", True, x, type, norm, dim, out)
 
 
+STFT_PAD_MODES = {"none": 0, "reflect": 1, "constant": 2}  # FOURIER_STFT_PAD_NONE / _REFLECT / _ZERO; "none" is center=False
+
+
+def _stft_pad_mode(center, pad_mode):
+    if not center:
+        return "none"
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    return pad_mode
+
+
+class Stft(_Handle):
+    """Batched short-time Fourier transform and its inverse (include/fourier.h, fourier_hip_stft_*) on device memory, torch.stft /
+    torch.istft with onesided=True: rows of `length` reals <-> frames x bins complex per row, FRAME-MAJOR (frame f of row b at complex
+    offset (b * frames + f) * bins).  n_fft, hop, win_length and the padding are fixed at create; the window is set afterwards
+    (set_window; default all ones)."""
+
+    _prefix = "fourier_hip_stft_"
+    _destroy = "fourier_hip_stft_destroy"
+
+    def __init__(self, n_fft, real="f32", hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+        n_fft = int(n_fft)
+        hop = n_fft // 4 if hop_length is None else int(hop_length)
+        wl = n_fft if win_length is None else int(win_length)
+        self.pad_mode = _stft_pad_mode(center, pad_mode)
+        if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+            raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+        self._create(real, f"STFT plan of n_fft {n_fft}, hop {hop}, win_length {wl}, padding {self.pad_mode}", n_fft, hop, wl,
+                     STFT_PAD_MODES[self.pad_mode], int(device))
+        self._n, self._hop, self._wl = n_fft, hop, wl
+        self._pad = 0 if self.pad_mode == "none" else n_fft // 2
+
+    def n_fft(self):
+        return self._n
+
+    def hop(self):
+        return self._hop
+
+    def win_length(self):
+        return self._wl
+
+    def bins(self):
+        return self._n // 2 + 1
+
+    def frames(self, length):
+        """Frames of a row of `length` reals; 0 where the length is invalid."""
+        return int(self._fn("frames")(self._h, int(length)))
+
+    def default_length(self, frames):
+        """The longest row `frames` frames give back: hop * (frames - 1) + n_fft - 2 * padding."""
+        return self._hop * (int(frames) - 1) + self._n - 2 * self._pad
+
+    def set_option(self, key, value):
+        """"fusion": 0 = the composed forward route, 1 = the fused one-launch route wherever it exists."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def reserve(self, length, batch):
+        """Later forward calls of at most `batch` rows of `length` reals, and inverse calls to that length from frames(length) frames,
+        never allocate."""
+        self._call("reserve", int(length), int(batch))
+
+    def set_window_ptr(self, d_window, stream=0):
+        """win_length() reals of the handle's precision at d_window (0 / None: all ones).  Waits for `stream`."""
+        self._call("set_window", d_window or None, stream)
+
+    def forward_ptr(self, d_in, d_out, length, batch, normalized=False, stream=0):
+        """`batch` rows of `length` reals at d_in -> batch x frames(length) x bins() complex at d_out, enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(length), int(batch), int(bool(normalized)), stream)
+
+    def inverse_ptr(self, d_in, d_out, frames, length, batch, normalized=False, stream=0):
+        """batch x frames x bins() complex at d_in -> `batch` rows of `length` reals at d_out, enqueued on `stream`."""
+        self._call("inverse", d_in, d_out, int(frames), int(length), int(batch), int(bool(normalized)), stream)
+
+    def set_window(self, window):
+        """A contiguous CUDA tensor of win_length() reals of the handle's precision, or None for all ones; on the current stream."""
+        if window is None:
+            return self.set_window_ptr(None)
+        _require_cuda(window, _torch_dtypes(self.real)[0])
+        if tuple(window.shape) != (self._wl,):
+            raise ValueError(f"window must have shape ({self._wl},), got {tuple(window.shape)}")
+        self.set_window_ptr(window.data_ptr(), _stream(window))
+
+    def forward(self, x, normalized=False, out=None):
+        """Contiguous (..., length) real CUDA tensor -> a new (..., frames, bins) complex tensor (frame-major), or `out`, on the current
+        stream."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(x, rdt)
+        if x.dim() == 0:
+            raise ValueError("expected at least one dimension")
+        length = int(x.shape[-1])
+        fr = self.frames(length)
+        if fr == 0:
+            raise ValueError(f"a row of {length} samples is too short for n_fft {self._n} with padding {self.pad_mode}")
+        shape = tuple(x.shape[:-1]) + (fr, self.bins())
+        if out is None:
+            out = torch.empty(shape, dtype=cdt, device=x.device)
+        else:
+            _require_out(out, shape, cdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), length, batch, normalized, _stream(x))
+        return out
+
+    def inverse(self, X, length=None, normalized=False, out=None):
+        """Contiguous (..., frames, bins) complex CUDA tensor (frame-major) -> a new (..., length) real tensor, or `out`, on the current
+        stream; length defaults to default_length(frames)."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(X, cdt)
+        if X.dim() < 2 or X.shape[-1] != self.bins() or X.shape[-2] == 0:
+            raise ValueError(f"expected (..., frames >= 1, {self.bins()}), got {tuple(X.shape)}")
+        fr = int(X.shape[-2])
+        full = self.default_length(fr)
+        length = full if length is None else int(length)
+        if not 1 <= length <= full:
+            raise ValueError(f"length must be in 1 ... {full} for {fr} frames, got {length}")
+        shape = tuple(X.shape[:-2]) + (length,)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=X.device)
+        else:
+            _require_out(out, shape, rdt, X.device)
+        batch = X.numel() // (fr * self.bins())
+        self.inverse_ptr(X.data_ptr(), out.data_ptr(), fr, length, batch, normalized, _stream(X))
+        return out
+
+
+def create_stft_f32(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return Stft(n_fft, "f32", hop_length, win_length, center, pad_mode, device)
+
+
+def create_stft_f64(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return Stft(n_fft, "f64", hop_length, win_length, center, pad_mode, device)
+
+
+def _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, real):
+    """The cached handle of these parameters with `window` set (on every call, like fftconv's filters)."""
+    n_fft = int(n_fft)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    mode = _stft_pad_mode(center, pad_mode)
+    if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+        raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+    if window is not None:
+        if not (_is_torch(window) and window.is_cuda and window.dtype == _torch_dtypes(real)[0] and window.device == x.device):
+            raise TypeError(f"window must be a CUDA {_names((_torch_dtypes(real)[0],))} tensor on the input's device")
+        if tuple(window.shape) != (wl,):
+            raise ValueError(f"window must have shape ({wl},), got {tuple(window.shape)}")
+        window = window.contiguous()
+    p = _cached_plan(Stft, n_fft, real, hop, wl, mode != "none", "reflect" if mode == "none" else mode, int(_device_index(x)))
+    p.set_window(window)
+    return p
+
+
+def stft(x, n_fft, hop_length=None, win_length=None, window=None, center=True, pad_mode="reflect", normalized=False):
+    """torch.stft(..., onesided=True, return_complex=True) of a float32 / float64 CUDA tensor of shape (..., length) on the current
+    stream, torch's defaults (hop_length n_fft // 4, win_length n_fft, window of ones); pad_mode "reflect" or "constant".  Returns shape
+    (..., bins, frames) like torch -- the TRANSPOSED VIEW of the frame-major buffer the library writes (bins contiguous per frame), not
+    a contiguous tensor; istft takes it back without a copy.  Leading dimensions fold into the batch.  Handles are cached per
+    (n_fft, hop, win_length, padding, dtype, device) and the window is set on EVERY call; keep an Stft to reuse one."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    p = _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, _precision(x.dtype)[0])
+    return p.forward(x.contiguous(), normalized).transpose(-1, -2)
+
+
+def istft(X, n_fft, hop_length=None, win_length=None, window=None, center=True, normalized=False, length=None):
+    """torch.istft(..., onesided=True) of a complex64 / complex128 CUDA tensor of shape (..., bins, frames) on the current stream ->
+    (..., length) reals, length defaulting to hop * (frames - 1) + n_fft - 2 * padding.  A tensor that is the transposed view stft
+    returns is used as it is; any other layout is copied into frame-major order first.  A window whose overlap-add envelope falls
+    below 1e-11 on a kept sample raises FourierError (torch's NOLA check)."""
+    import torch
+
+    if not (_is_torch(X) and X.is_cuda and X.dtype in (torch.complex64, torch.complex128)):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor")
+    if X.dim() < 2:
+        raise ValueError("expected shape (..., bins, frames)")
+    if X.shape[-2] != int(n_fft) // 2 + 1 or X.shape[-1] == 0:
+        raise ValueError(f"expected (..., {int(n_fft) // 2 + 1}, frames >= 1), got {tuple(X.shape)}")
+    p = _stft_plan(X, n_fft, hop_length, win_length, window, center, "reflect", _precision(X.dtype)[0])
+    return p.inverse(X.transpose(-1, -2).contiguous(), length, normalized)
+
+
 class RealFftN(_RealHandle):
     """Batched real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*) over items of `shape` (1 ... 4 dimensions, the
     last one real) on device memory, numpy's rfftn / irfftn layout: an item of reals has `shape`, an item of the half spectrum has

@@ -637,6 +637,85 @@ const char *fourier_hip_r2r_describe_double(const FOURIER_STRUCT fourier_r2r_dou
 int fourier_hip_r2r_last_status_float(const FOURIER_STRUCT fourier_r2r_float *);
 int fourier_hip_r2r_last_status_double(const FOURIER_STRUCT fourier_r2r_double *);
 
+/* ---------------- short-time Fourier transform and its inverse (extension; the reference has none) ----------
+ * torch.stft / torch.istft with onesided = True, return_complex = True, on DEVICE memory.  A handle is made for n_fft >= 1, hop >= 1,
+ * win_length in 1 ... n_fft and a pad mode: FOURIER_STFT_PAD_NONE (torch's center = False), FOURIER_STFT_PAD_REFLECT or
+ * FOURIER_STFT_PAD_ZERO (center = True with p = n_fft / 2 samples, integer division, of padding on each side; p' = p below, 0 without
+ * padding).  The padding is index arithmetic at the load (reflect: t < 0 -> -t, t >= length -> 2 (length - 1) - t); no padded copy exists.
+ * Window: fourier_hip_stft_set_window_* takes win_length reals T on the device, centred in the frame ((n_fft - win_length) / 2 zeros
+ * in front); NULL restores the default of all ones (torch's window = None).  A set-up call: it waits for `stream`.
+ * Frames of a row of `length` reals (fourier_hip_stft_frames_*; 0 where the length is invalid): PAD_NONE 1 + (length - n_fft) / hop
+ * for length >= n_fft; otherwise 1 + (length + 2 p - n_fft) / hop as torch, which is 1 + length / hop for even n_fft, where PAD_REFLECT
+ * needs length > p.  bins = n_fft / 2 + 1.
+ * Forward: `batch` contiguous rows of `length` reals in; batch x frames x bins interleaved complex out, FRAME-MAJOR: frame f of row b at
+ * complex offset (b * frames + f) * bins (torch's (bins, frames) is the transposed view of a row's block),
+ *   X[b, f, k] = sum_n w[n] xpad[b, f hop + n] exp(-2 pi i k n / n_fft),   times n_fft^-1/2 where normalized != 0.
+ * Inverse: batch x frames x bins in, `batch` rows of `length` reals out, 1 <= length <= hop (frames - 1) + n_fft - 2 p',
+ *   y[t] = (sum_f w[t + p' - f hop] frame_f[t + p' - f hop]) / (sum_f w[t + p' - f hop]^2),   frame_f = irfft(X[b, f], n_fft),
+ * times n_fft^1/2 where normalized != 0.  Where the envelope sum_f w^2 falls below 1e-11 on a kept sample (torch's NOLA check) the call
+ * returns FOURIER_HIP_INVALID_ARGUMENT.  The envelope is computed on the host in f64 on first use of a (frames, length) and cached.
+ * The overlap-add is a gather, one lane per output sample: no atomics, deterministic.
+ * A NULL handle or pointer, reals not aligned to sizeof(T) or complex values not aligned to 2 * sizeof(T), any overlap of d_in and d_out
+ * or an invalid length give FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  Stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*.  Routes (fourier_hip_stft_describe_*: "<forward route>, istft composed: <the real plan's describe>"):
+ *   "stft composed"    any n_fft: a gather sweep windows the frames of a chunk into a handle-owned scratch (at most 1 GiB, never less
+ *                      than one frame), the real-input plan transforms them into the output.
+ *   "stft fused rows"  n_fft = 2h whose h-point plan is one whole-row kernel (n_fft 128 ... 1024, f32 also 2048): gather, window,
+ *                      transform and untangle in ONE launch, no scratch.  Option "fusion" = 0 forces the composed route, 1 takes the
+ *                      fused one wherever it exists.
+ * The inverse runs the real-input plan's inverse into the scratch and the overlap-add sweep, in chunks of whole rows, or of ranges of
+ * one row's samples where a row's frames exceed the bound.  fourier_hip_stft_reserve_*(h, length, batch) sizes everything forward calls
+ * of at most `batch` rows of `length` reals, and inverse calls to that length from frames(length) frames, need: they then never
+ * allocate.  Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_stft_last_status_*. */
+enum {
+  FOURIER_STFT_PAD_NONE = 0,
+  FOURIER_STFT_PAD_REFLECT = 1,
+  FOURIER_STFT_PAD_ZERO = 2,
+};
+struct fourier_stft_float;
+struct fourier_stft_double;
+
+/* NULL on failure (parameters outside the ranges above included). */
+struct fourier_stft_float *fourier_hip_stft_create_float(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                         int pad_mode, int device);
+struct fourier_stft_double *fourier_hip_stft_create_double(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                           int pad_mode, int device);
+/* NULL is a no-op. */
+void fourier_hip_stft_destroy_float(FOURIER_STRUCT fourier_stft_float *);
+void fourier_hip_stft_destroy_double(FOURIER_STRUCT fourier_stft_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_stft_n_fft_float(const FOURIER_STRUCT fourier_stft_float *);
+FOURIER_SIZE_TYPE fourier_hip_stft_n_fft_double(const FOURIER_STRUCT fourier_stft_double *);
+FOURIER_SIZE_TYPE fourier_hip_stft_hop_float(const FOURIER_STRUCT fourier_stft_float *);
+FOURIER_SIZE_TYPE fourier_hip_stft_hop_double(const FOURIER_STRUCT fourier_stft_double *);
+FOURIER_SIZE_TYPE fourier_hip_stft_win_length_float(const FOURIER_STRUCT fourier_stft_float *);
+FOURIER_SIZE_TYPE fourier_hip_stft_win_length_double(const FOURIER_STRUCT fourier_stft_double *);
+FOURIER_SIZE_TYPE fourier_hip_stft_bins_float(const FOURIER_STRUCT fourier_stft_float *);
+FOURIER_SIZE_TYPE fourier_hip_stft_bins_double(const FOURIER_STRUCT fourier_stft_double *);
+/* frames of a row of `length` reals; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_stft_frames_float(const FOURIER_STRUCT fourier_stft_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_stft_frames_double(const FOURIER_STRUCT fourier_stft_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_stft_set_window_float(FOURIER_STRUCT fourier_stft_float *, const void *d_window, void *stream);
+int fourier_hip_stft_set_window_double(FOURIER_STRUCT fourier_stft_double *, const void *d_window, void *stream);
+int fourier_hip_stft_forward_float(const FOURIER_STRUCT fourier_stft_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                   FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_stft_forward_double(const FOURIER_STRUCT fourier_stft_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                    FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_stft_inverse_float(const FOURIER_STRUCT fourier_stft_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                   FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_stft_inverse_double(const FOURIER_STRUCT fourier_stft_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                    FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_stft_reserve_float(const FOURIER_STRUCT fourier_stft_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_stft_reserve_double(const FOURIER_STRUCT fourier_stft_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed forward route, 1 = the fused one wherever it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_stft_set_option_float(FOURIER_STRUCT fourier_stft_float *, const char *key, long long value);
+int fourier_hip_stft_set_option_double(FOURIER_STRUCT fourier_stft_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_stft_describe_float(const FOURIER_STRUCT fourier_stft_float *);
+const char *fourier_hip_stft_describe_double(const FOURIER_STRUCT fourier_stft_double *);
+int fourier_hip_stft_last_status_float(const FOURIER_STRUCT fourier_stft_float *);
+int fourier_hip_stft_last_status_double(const FOURIER_STRUCT fourier_stft_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -784,6 +863,66 @@ template <typename T> struct r2r;
 FOURIER_DEFINE_CXX_R2R_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_R2R_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_R2R_WRAPPER
+
+/* short-time Fourier transform on device memory (extension): fourier::stft<float> / <double> */
+enum class stft_pad {
+  none = ::fourier::c::FOURIER_STFT_PAD_NONE,
+  reflect = ::fourier::c::FOURIER_STFT_PAD_REFLECT,
+  zero = ::fourier::c::FOURIER_STFT_PAD_ZERO,
+};
+template <typename T> struct stft;
+
+#define FOURIER_DEFINE_CXX_STFT_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct stft<T> {                                                                     \
+    stft(std::size_t n_fft, std::size_t hop, std::size_t win_length, stft_pad pad = stft_pad::reflect, int device = -1) \
+        : impl(::fourier::c::fourier_hip_stft_create_##SUFFIX(n_fft, hop, win_length, static_cast<int>(pad), device), \
+               ::fourier::c::fourier_hip_stft_destroy_##SUFFIX) {}                                 \
+    stft() = delete;                                                                               \
+    stft(const stft &) = delete;                                                                   \
+    stft(stft &&) = default;                                                                       \
+    stft &operator=(const stft &) = delete;                                                        \
+    stft &operator=(stft &&) = default;                                                            \
+    ~stft() = default;                                                                             \
+    std::size_t n_fft() const { return ::fourier::c::fourier_hip_stft_n_fft_##SUFFIX(impl.get()); } \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_stft_hop_##SUFFIX(impl.get()); }    \
+    std::size_t win_length() const { return ::fourier::c::fourier_hip_stft_win_length_##SUFFIX(impl.get()); } \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_stft_bins_##SUFFIX(impl.get()); }  \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_stft_frames_##SUFFIX(impl.get(), length);                   \
+    }                                                                                              \
+    /* win_length reals on the device; nullptr: all ones */                                        \
+    int set_window(const void *d_window, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_stft_set_window_##SUFFIX(impl.get(), d_window, stream);     \
+    }                                                                                              \
+    /* batch rows of `length` reals -> batch x frames x bins complex, frame-major */               \
+    int forward_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch,       \
+                       bool normalized = false, void *stream = nullptr) const {                    \
+      return ::fourier::c::fourier_hip_stft_forward_##SUFFIX(impl.get(), d_in, d_out, length, batch, \
+                                                             normalized ? 1 : 0, stream);          \
+    }                                                                                              \
+    /* batch x frames x bins complex -> batch rows of `length` reals */                            \
+    int inverse_device(const void *d_in, void *d_out, std::size_t frames, std::size_t length,      \
+                       std::size_t batch, bool normalized = false, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_stft_inverse_##SUFFIX(impl.get(), d_in, d_out, frames, length, \
+                                                             batch, normalized ? 1 : 0, stream);   \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_stft_reserve_##SUFFIX(impl.get(), length, batch);           \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_stft_set_option_##SUFFIX(impl.get(), key, value);           \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_stft_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_stft_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_stft_##SUFFIX,                                         \
+                      void (*)(::fourier::c::fourier_stft_##SUFFIX *)> impl;                       \
+  };
+FOURIER_DEFINE_CXX_STFT_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_STFT_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_STFT_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
