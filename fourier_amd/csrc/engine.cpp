@@ -19,6 +19,7 @@
 #include "lconv_plan.h"
 #include "r2r_plan.h"
 #include "stft_plan.h"
+#include "mdct_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -309,6 +310,45 @@ FOURIER_DEFINE_R2R_ABI(double, double)
 
 FOURIER_DEFINE_STFT_ABI(float, float)
 FOURIER_DEFINE_STFT_ABI(double, double)
+
+// modified discrete cosine transform and its inverse (fourier_hip_mdct_*)
+#define FOURIER_DEFINE_MDCT_ABI(T, SUFFIX)                                                                       \
+  extern "C" fc::fourier_mdct_##SUFFIX* fourier_hip_mdct_create_##SUFFIX(size_t n, int center, int device) {     \
+    return (fc::fourier_mdct_##SUFFIX*)create_handle<MdctPlan<T>>(n, center, device);                            \
+  }                                                                                                              \
+  extern "C" void fourier_hip_mdct_destroy_##SUFFIX(fc::fourier_mdct_##SUFFIX* h) { destroy_handle<MdctPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_mdct_describe_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h) { return describe_handle<MdctPlan<T>>(h); } \
+  extern "C" int fourier_hip_mdct_last_status_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h) { return last_status_of<MdctPlan<T>>(h); } \
+  extern "C" int fourier_hip_mdct_set_option_##SUFFIX(fc::fourier_mdct_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<MdctPlan<T>>(h, key, v);                                                            \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_mdct_size_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h) {                         \
+    return h ? ((const MdctPlan<T>*)h)->size() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_mdct_frames_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h, size_t length) {        \
+    return h ? ((const MdctPlan<T>*)h)->frames(length) : 0;                                                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_mdct_set_window_##SUFFIX(fc::fourier_mdct_##SUFFIX* h, const void* d_window, void* stream) { \
+    MdctPlan<T>* p = (MdctPlan<T>*)h;                                                                            \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_mdct_reserve_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h, size_t length, size_t batch) { \
+    const MdctPlan<T>* p = (const MdctPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_mdct_forward_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                   size_t batch, int normalized, void* stream) {                 \
+    const MdctPlan<T>* p = (const MdctPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, length, batch, normalized != 0, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_mdct_inverse_##SUFFIX(const fc::fourier_mdct_##SUFFIX* h, const void* d_in, void* d_out, size_t frames, \
+                                                   size_t length, size_t batch, int normalized, void* stream) {  \
+    const MdctPlan<T>* p = (const MdctPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, frames, length, batch, normalized != 0, (hipStream_t)stream); }); \
+  }
+
+FOURIER_DEFINE_MDCT_ABI(float, float)
+FOURIER_DEFINE_MDCT_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

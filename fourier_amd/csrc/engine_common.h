@@ -173,6 +173,9 @@ typedef void (*R2RKernel)(R2RArgs);
 typedef void (*StftKernel)(StftArgs);
 // the fused frame route of the STFT handle on a whole-row kernel's tile shape (kernels_stft.h); fn == nullptr: none for that length
 struct StftRowsKernel { StftKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
+typedef void (*MdctKernel)(MdctArgs);
+// the fused frame route of the MDCT handle on a whole-row kernel's tile shape (kernels_mdct.h); fn == nullptr: none for that length
+struct MdctRowsKernel { MdctKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -260,6 +263,10 @@ template <typename T> struct Real {};
   /* frame route for n_fft = 2 L on the whole-row kernel of length L                                                   */ \
   StftKernel get_stft_kernel(Real<T>, int which);                                                                      \
   StftRowsKernel get_stft_rows_kernel(Real<T>, int L);                                                                 \
+  /* kernels_mdct.cpp: the sweeps of the MDCT handle, which = MDCT_FOLD ... IMDCT_ODD_OLA (kernel_args.h); its fused frame */ \
+  /* route for n = 2 L coefficients on the whole-row kernel of length L                                                */ \
+  MdctKernel get_mdct_kernel(Real<T>, int which);                                                                      \
+  MdctRowsKernel get_mdct_rows_kernel(Real<T>, int L);                                                                 \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \

@@ -284,6 +284,24 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, stft_rows_.fn, (a.total + stft_rows_.COLS - 1) / stft_rows_.COLS, stft_rows_.NT, stft_rows_.smem, stream, a);
   }
 
+  // The fused frame route of the MDCT handle (mdct_rows_kernel; mdct_plan.h), under the same condition: this plan, of h = n / 2 points,
+  // is ONE whole-row pass and kernels_mdct.cpp holds the kernel on that pass's tile shape.
+  bool enable_mdct_rows() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
+    if (mdct_rows_.fn) return true;
+    const MdctRowsKernel k = get_mdct_rows_kernel(Real<T>{}, passes_[0]->k.L);
+    if (!k.fn || k.L != passes_[0]->k.L) return false;
+    raise_smem_limit((const void*)k.fn, k.smem);
+    mdct_rows_ = k;
+    return true;
+  }
+  void run_mdct_rows(MdctArgs a, hipStream_t stream) const {
+    if (a.total == 0) return;
+    const Pass& ps = *passes_[0];
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st->tw2.p;
+    launch(nullptr, 0, mdct_rows_.fn, (a.total + mdct_rows_.COLS - 1) / mdct_rows_.COLS, mdct_rows_.NT, mdct_rows_.smem, stream, a);
+  }
+
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
   void init_l2fused(int k) {
     FusedInfo fi;
@@ -679,6 +697,7 @@ template <typename T> class Pow2Engine {
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   StageTables<T>* conv_st_ = nullptr;
   StftRowsKernel stft_rows_;
+  MdctRowsKernel mdct_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -224,6 +224,31 @@ struct StftArgs {
   double scale;
 };
 
+// ---- modified discrete cosine transform (kernels_mdct.h; MdctPlan, mdct_plan.h)
+// A frame is 2n samples, the hop n; frame f of a row covers xpad[f n - pad ... f n - pad + 2n), zero outside the row.  The flat frame
+// index, `first`, `total` and the multiply-high division are StftArgs'.  Even n = 2h: a frame is h complex values in the scratch
+// (z before the inner plan, Z behind it); odd n: 2n complex values.  Forward sweeps and the fused kernel write frame i of the launch at
+// out + i * n reals.  Inverse: the pre sweeps read frame i at in + i * n reals; imdct_ola_kernel has one lane per output sample of
+// `rows` rows, sample t = t0 + i of `span` samples per row, over frames f_lo ... f_lo + nfr - 1 of every row in the scratch.
+enum { MDCT_FOLD = 0, MDCT_POST = 1, MDCT_ODD_PRE = 2, MDCT_ODD_POST = 3, IMDCT_PRE = 4, IMDCT_ODD_PRE = 5, IMDCT_OLA = 6, IMDCT_ODD_OLA = 7 };
+struct MdctArgs {
+  const void* in; void* out;
+  const void* win;            // the window, 2n reals
+  const void* twa;            // even n: exp(-i pi (4j + 1) / 4n), j < h; odd n: exp(-i pi m / 2n), m < 2n
+  const void* twb;            // even n: exp(-i pi j / n), j < h; odd n: exp(-i pi (n + 1)(2k + 1) / 4n), k < n
+  const void* tw1; const void* tw2;  // fused: the row core's stage tables
+  uint64_t length;            // reals per signal row
+  uint64_t total;             // forward, inverse pre sweeps: frames of this launch; overlap-add: rows * span
+  uint32_t frames;            // frames per signal row
+  uint32_t first;             // forward: frame index (within row 0 of the launch) of item 0
+  uint32_t fr_m, fr_l;        // x / frames = (umulhi(x, fr_m) + x) >> fr_l
+  uint32_t n, pad;
+  int pairs;                  // fused: every output frame starts on a 2 * sizeof(T)-aligned address
+  uint64_t t0, span, rows;    // overlap-add: first sample of the range, samples per row in it, rows
+  uint64_t f_lo, nfr;         // overlap-add: first frame in the scratch, frames per row there
+  double scale;
+};
+
 // ---- convolution with a filter bank (kernels_conv.h; ConvPlan, conv_plan.h)
 // conv_mul_kernel: Z[b][k] *= H[(first + b) mod filters][k] over a flat index of rows x len, one lane per element.
 // real_conv_mid_kernel: one lane per mirrored pair (j, h - j) of a row of the inner plan's output, as the real sweeps (`len` = h / 2 + 1

@@ -597,6 +597,18 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_stft_rows(a, stream);
   }
 
+  // ---- the hook of the MDCT handle (MdctPlan, mdct_plan.h), as the STFT's: a plan of h points that is one whole-row pass runs the frames
+  // of n = 2h coefficients in one launch of mdct_rows_kernel (fold, pre-twiddle, transform, post-twiddle).
+  bool enable_mdct() {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_mdct_rows();
+  }
+  void exec_mdct(const MdctArgs& a, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_mdct_rows(a, stream);
+  }
+
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).
   void synchronize(hipStream_t stream) const {
     DeviceGuard g(device_);

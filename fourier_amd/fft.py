@@ -858,6 +858,162 @@ def istft(X, n_fft, hop_length=None, win_length=None, window=None, center=True, 
     return p.inverse(X.transpose(-1, -2).contiguous(), length, normalized)
 
 
+class Mdct(_Handle):
+    """Batched modified discrete cosine transform and its inverse (include/fourier.h, fourier_hip_mdct_*) on device memory: rows of
+    `length` reals <-> frames x n reals per row, FRAME-MAJOR (frame f of row b at element offset (b * frames + f) * n).  A frame is 2n
+    samples, the hop n; `center` pads n zeros in front and zeros behind by index arithmetic.  The window is set afterwards (set_window;
+    default the sine window).  No envelope division: the inverse reconstructs where the window satisfies Princen-Bradley."""
+
+    _prefix = "fourier_hip_mdct_"
+    _destroy = "fourier_hip_mdct_destroy"
+
+    def __init__(self, n, real="f32", center=True, device=-1):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"need n >= 1, got {n}")
+        self.center = bool(center)
+        self._create(real, f"MDCT plan of {n} coefficients per frame, center {self.center}", n, int(self.center), int(device))
+        self._n = n
+
+    def size(self):
+        return self._n
+
+    def frames(self, length):
+        """Frames of a row of `length` reals; 0 where the length is invalid."""
+        return int(self._fn("frames")(self._h, int(length)))
+
+    def default_length(self, frames):
+        """The longest row `frames` frames give back: (frames - 1) n with center, (frames + 1) n without."""
+        return (int(frames) - 1) * self._n if self.center else (int(frames) + 1) * self._n
+
+    def set_option(self, key, value):
+        """"fusion": 0 = the composed forward route, 1 = the fused one-launch route wherever it exists."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def reserve(self, length, batch):
+        """Later forward calls of at most `batch` rows of `length` reals, and inverse calls to that length from frames(length) frames,
+        never allocate."""
+        self._call("reserve", int(length), int(batch))
+
+    def set_window_ptr(self, d_window, stream=0):
+        """2n reals of the handle's precision at d_window (0 / None: the sine window).  Waits for `stream`."""
+        self._call("set_window", d_window or None, stream)
+
+    def forward_ptr(self, d_in, d_out, length, batch, normalized=False, stream=0):
+        """`batch` rows of `length` reals at d_in -> batch x frames(length) x n reals at d_out, enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(length), int(batch), int(bool(normalized)), stream)
+
+    def inverse_ptr(self, d_in, d_out, frames, length, batch, normalized=False, stream=0):
+        """batch x frames x n reals at d_in -> `batch` rows of `length` reals at d_out, enqueued on `stream`."""
+        self._call("inverse", d_in, d_out, int(frames), int(length), int(batch), int(bool(normalized)), stream)
+
+    def set_window(self, window):
+        """A contiguous CUDA tensor of 2n reals of the handle's precision, or None for the sine window; on the current stream."""
+        if window is None:
+            return self.set_window_ptr(None)
+        _require_cuda(window, _torch_dtypes(self.real)[0])
+        if tuple(window.shape) != (2 * self._n,):
+            raise ValueError(f"window must have shape ({2 * self._n},), got {tuple(window.shape)}")
+        self.set_window_ptr(window.data_ptr(), _stream(window))
+
+    def forward(self, x, normalized=False, out=None):
+        """Contiguous (..., length) real CUDA tensor -> a new (..., frames, n) real tensor (frame-major), or `out`, on the current
+        stream."""
+        import torch
+
+        rdt = _torch_dtypes(self.real)[0]
+        _require_cuda(x, rdt)
+        if x.dim() == 0:
+            raise ValueError("expected at least one dimension")
+        length = int(x.shape[-1])
+        fr = self.frames(length)
+        if fr == 0:
+            raise ValueError(f"a row of {length} samples is too short for n {self._n} with center {self.center}")
+        shape = tuple(x.shape[:-1]) + (fr, self._n)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=x.device)
+        else:
+            _require_out(out, shape, rdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), length, batch, normalized, _stream(x))
+        return out
+
+    def inverse(self, X, length=None, normalized=False, out=None):
+        """Contiguous (..., frames, n) real CUDA tensor (frame-major) -> a new (..., length) real tensor, or `out`, on the current
+        stream; length defaults to default_length(frames)."""
+        import torch
+
+        rdt = _torch_dtypes(self.real)[0]
+        _require_cuda(X, rdt)
+        if X.dim() < 2 or X.shape[-1] != self._n or X.shape[-2] == 0:
+            raise ValueError(f"expected (..., frames >= 1, {self._n}), got {tuple(X.shape)}")
+        fr = int(X.shape[-2])
+        full = self.default_length(fr)
+        length = full if length is None else int(length)
+        if not 1 <= length <= full:
+            raise ValueError(f"length must be in 1 ... {full} for {fr} frames, got {length}")
+        shape = tuple(X.shape[:-2]) + (length,)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=X.device)
+        else:
+            _require_out(out, shape, rdt, X.device)
+        batch = X.numel() // (fr * self._n)
+        if batch:
+            self.inverse_ptr(X.data_ptr(), out.data_ptr(), fr, length, batch, normalized, _stream(X))
+        return out
+
+
+def create_mdct_f32(n, center=True, device=-1):
+    return Mdct(n, "f32", center, device)
+
+
+def create_mdct_f64(n, center=True, device=-1):
+    return Mdct(n, "f64", center, device)
+
+
+def _mdct_plan(x, n, window, center):
+    """The cached handle of these parameters with `window` set (on every call, like stft's)."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"need n >= 1, got {n}")
+    real = _precision(x.dtype)[0]
+    if window is not None:
+        if not (_is_torch(window) and window.is_cuda and window.dtype == x.dtype and window.device == x.device):
+            raise TypeError(f"window must be a CUDA {_names((x.dtype,))} tensor on the input's device")
+        if tuple(window.shape) != (2 * n,):
+            raise ValueError(f"window must have shape ({2 * n},), got {tuple(window.shape)}")
+        window = window.contiguous()
+    p = _cached_plan(Mdct, n, real, bool(center), int(_device_index(x)))
+    p.set_window(window)
+    return p
+
+
+def mdct(x, n, window=None, center=True, normalized=False):
+    """The MDCT of a float32 / float64 CUDA tensor of shape (..., length) on the current stream -> (..., frames, n), frames of 2n
+    samples every n samples, `window` of 2n reals (None: the sine window), `center` pads n zeros in front and zeros behind; times
+    sqrt(2 / n) where normalized.  Leading dimensions fold into the batch.  Handles are cached per (n, center, dtype, device) and the
+    window is set on EVERY call; keep an Mdct to reuse one."""
+    p = _mdct_plan(x, n, window, center)
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    return p.forward(x.contiguous(), normalized)
+
+
+def imdct(X, n, window=None, center=True, normalized=False, length=None):
+    """The inverse MDCT with overlap-add of a float32 / float64 CUDA tensor of shape (..., frames, n) on the current stream ->
+    (..., length) reals, length defaulting to (frames - 1) n with center and (frames + 1) n without.  No envelope division: it
+    reconstructs mdct's input where the window satisfies Princen-Bradley (the sine default does)."""
+    p = _mdct_plan(X, n, window, center)
+    if X.dim() < 2:
+        raise ValueError("expected shape (..., frames, n)")
+    return p.inverse(X.contiguous(), length, normalized)
+
+
 class RealFftN(_RealHandle):
     """Batched real-input N-D transforms (include/fourier.h, fourier_hip_realnd_*) over items of `shape` (1 ... 4 dimensions, the
     last one real) on device memory, numpy's rfftn / irfftn layout: an item of reals has `shape`, an item of the half spectrum has

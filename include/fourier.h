@@ -716,6 +716,78 @@ const char *fourier_hip_stft_describe_double(const FOURIER_STRUCT fourier_stft_d
 int fourier_hip_stft_last_status_float(const FOURIER_STRUCT fourier_stft_float *);
 int fourier_hip_stft_last_status_double(const FOURIER_STRUCT fourier_stft_double *);
 
+/* ---------------- modified discrete cosine transform and its inverse (extension; the reference has none) ----------
+ * The lapped transform of AAC, Vorbis and Opus, on DEVICE memory.  A handle is made for n >= 1 coefficients per frame and a `center`
+ * flag; a frame is 2n samples and the hop is n.
+ * Window: fourier_hip_mdct_set_window_* takes 2n reals T on the device; NULL restores the default, the sine window
+ * w[m] = sin(pi (m + 1/2) / 2n), computed on the host in f64 and cast.  A set-up call: it waits for `stream`.
+ * Padding: with center != 0 the row is treated as if n zeros stood in front of it and zeros behind it (xpad; p = n below, 0 without) --
+ * index arithmetic at the load, no padded copy exists.  Frames of a row of `length` reals (fourier_hip_mdct_frames_*; 0 where the
+ * length is invalid): with center ceil(length / n) + 1 for length >= 1; without, length / n - 1 (integer division) for length >= 2n,
+ * and the samples behind the last whole frame are ignored.
+ * Forward: `batch` contiguous rows of `length` reals in; batch x frames x n reals out, FRAME-MAJOR: frame f of row b at element offset
+ * (b * frames + f) * n,
+ *   X[b, f, k] = sum_{m=0}^{2n-1} w[m] xpad[b, f n + m] cos(pi/n (m + 1/2 + n/2)(k + 1/2)),  k = 0 ... n-1,
+ * times sqrt(2/n) where normalized != 0 (the orthogonal TDAC scaling).
+ * Inverse: batch x frames x n reals in, `batch` rows of `length` reals out, 1 <= length <= (frames - 1) n with center and
+ * 1 <= length <= (frames + 1) n without,
+ *   y[b, t] = (2/n) sum_f w[t + p - f n] Y_f[t + p - f n],   Y_f[m] = sum_k X[b, f, k] cos(pi/n (m + 1/2 + n/2)(k + 1/2)),
+ * over the at most two frames that cover t; sqrt(2/n) instead of 2/n where normalized != 0.  No envelope division is done:
+ * reconstruction is exact on samples covered by two frames exactly when the window satisfies Princen-Bradley,
+ * w[m]^2 + w[m + n]^2 = 1 with w[m] = w[2n - 1 - m]; the sine default does.  With center == 0 the first and the last n samples are
+ * covered by one frame only and carry uncancelled time-domain aliasing.  The overlap-add is a gather, one lane per output sample:
+ * no atomics, deterministic.
+ * A NULL handle or pointer, reals not aligned to sizeof(T), any overlap of d_in and d_out or an invalid length give
+ * FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_mdct_describe_*: "<forward route>, <inverse route>: <the inner plan's describe>"):
+ *   "mdct composed"     even n = 2h: a fold sweep (window, fold to n reals, pre-twiddle) into a handle-owned scratch (at most 1 GiB,
+ *                       never less than one frame forward and two frames inverse), the h-point complex plan, a post-twiddle sweep
+ *                       into the output.
+ *   "mdct fused rows"   n = 2h whose h-point plan is one whole-row kernel (n 128 ... 1024, f32 also 2048): fold, transform and
+ *                       post-twiddle in ONE launch, no scratch.  Option "fusion" = 0 forces the composed route, 1 takes the fused one
+ *                       wherever it exists.
+ *   "mdct full-length"  odd n, the correctness path: the 2n-point complex plan on w[m] x[m] exp(-i pi m / 2n).
+ * The inverse ("imdct composed" for even n, "imdct full-length" for odd n) is a pre sweep, the inner plan and the overlap-add sweep,
+ * in chunks of whole rows, or of ranges of one row's samples where a row's frames exceed the bound; there is no fused inverse.
+ * fourier_hip_mdct_reserve_*(h, length, batch) sizes everything forward calls of at most `batch` rows of `length` reals, and inverse
+ * calls to that length from frames(length) frames, need: they then never allocate.  Handles are Send, not Sync, like the complex
+ * ones; status of the last call: fourier_hip_mdct_last_status_*. */
+struct fourier_mdct_float;
+struct fourier_mdct_double;
+
+/* NULL on failure (n == 0 included). */
+struct fourier_mdct_float *fourier_hip_mdct_create_float(FOURIER_SIZE_TYPE n, int center, int device);
+struct fourier_mdct_double *fourier_hip_mdct_create_double(FOURIER_SIZE_TYPE n, int center, int device);
+/* NULL is a no-op. */
+void fourier_hip_mdct_destroy_float(FOURIER_STRUCT fourier_mdct_float *);
+void fourier_hip_mdct_destroy_double(FOURIER_STRUCT fourier_mdct_double *);
+/* n; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_mdct_size_float(const FOURIER_STRUCT fourier_mdct_float *);
+FOURIER_SIZE_TYPE fourier_hip_mdct_size_double(const FOURIER_STRUCT fourier_mdct_double *);
+/* frames of a row of `length` reals; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_mdct_frames_float(const FOURIER_STRUCT fourier_mdct_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_mdct_frames_double(const FOURIER_STRUCT fourier_mdct_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_mdct_set_window_float(FOURIER_STRUCT fourier_mdct_float *, const void *d_window, void *stream);
+int fourier_hip_mdct_set_window_double(FOURIER_STRUCT fourier_mdct_double *, const void *d_window, void *stream);
+int fourier_hip_mdct_forward_float(const FOURIER_STRUCT fourier_mdct_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                   FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_mdct_forward_double(const FOURIER_STRUCT fourier_mdct_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                    FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_mdct_inverse_float(const FOURIER_STRUCT fourier_mdct_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                   FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_mdct_inverse_double(const FOURIER_STRUCT fourier_mdct_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                    FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int normalized, void *stream);
+int fourier_hip_mdct_reserve_float(const FOURIER_STRUCT fourier_mdct_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_mdct_reserve_double(const FOURIER_STRUCT fourier_mdct_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed forward route, 1 = the fused one wherever it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_mdct_set_option_float(FOURIER_STRUCT fourier_mdct_float *, const char *key, long long value);
+int fourier_hip_mdct_set_option_double(FOURIER_STRUCT fourier_mdct_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_mdct_describe_float(const FOURIER_STRUCT fourier_mdct_float *);
+const char *fourier_hip_mdct_describe_double(const FOURIER_STRUCT fourier_mdct_double *);
+int fourier_hip_mdct_last_status_float(const FOURIER_STRUCT fourier_mdct_float *);
+int fourier_hip_mdct_last_status_double(const FOURIER_STRUCT fourier_mdct_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -923,6 +995,58 @@ template <typename T> struct stft;
 FOURIER_DEFINE_CXX_STFT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_STFT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_STFT_WRAPPER
+
+/* modified discrete cosine transform on device memory (extension): fourier::mdct<float> / <double> */
+template <typename T> struct mdct;
+
+#define FOURIER_DEFINE_CXX_MDCT_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct mdct<T> {                                                                     \
+    explicit mdct(std::size_t n, bool center = true, int device = -1)                              \
+        : impl(::fourier::c::fourier_hip_mdct_create_##SUFFIX(n, center ? 1 : 0, device),          \
+               ::fourier::c::fourier_hip_mdct_destroy_##SUFFIX) {}                                 \
+    mdct() = delete;                                                                               \
+    mdct(const mdct &) = delete;                                                                   \
+    mdct(mdct &&) = default;                                                                       \
+    mdct &operator=(const mdct &) = delete;                                                        \
+    mdct &operator=(mdct &&) = default;                                                            \
+    ~mdct() = default;                                                                             \
+    std::size_t size() const { return ::fourier::c::fourier_hip_mdct_size_##SUFFIX(impl.get()); }  \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_mdct_frames_##SUFFIX(impl.get(), length);                   \
+    }                                                                                              \
+    /* 2n reals on the device; nullptr: the sine window */                                         \
+    int set_window(const void *d_window, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_mdct_set_window_##SUFFIX(impl.get(), d_window, stream);     \
+    }                                                                                              \
+    /* batch rows of `length` reals -> batch x frames x n reals, frame-major */                    \
+    int forward_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch,       \
+                       bool normalized = false, void *stream = nullptr) const {                    \
+      return ::fourier::c::fourier_hip_mdct_forward_##SUFFIX(impl.get(), d_in, d_out, length, batch, \
+                                                             normalized ? 1 : 0, stream);          \
+    }                                                                                              \
+    /* batch x frames x n reals -> batch rows of `length` reals */                                 \
+    int inverse_device(const void *d_in, void *d_out, std::size_t frames, std::size_t length,      \
+                       std::size_t batch, bool normalized = false, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_mdct_inverse_##SUFFIX(impl.get(), d_in, d_out, frames, length, \
+                                                             batch, normalized ? 1 : 0, stream);   \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_mdct_reserve_##SUFFIX(impl.get(), length, batch);           \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_mdct_set_option_##SUFFIX(impl.get(), key, value);           \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_mdct_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_mdct_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_mdct_##SUFFIX,                                         \
+                      void (*)(::fourier::c::fourier_mdct_##SUFFIX *)> impl;                       \
+  };
+FOURIER_DEFINE_CXX_MDCT_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_MDCT_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_MDCT_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
