@@ -8,11 +8,12 @@ import numpy as np
 import pytest
 
 import stft_truth as truth
-from helpers import rel_l2
+from helpers import max_rel, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 FUSED_N = (256, 512, 1024, 2048)
+SENTINEL = 77.0
 
 
 @pytest.fixture(scope="module")
@@ -72,9 +73,13 @@ def check_forward(torch, fa, real, n_fft, hop, length, batch, pad_mode="reflect"
         d = plan.describe()
         assert d.startswith("stft fused rows, istft composed: real half-length: " if fused else "stft composed, istft composed: real "), d
         got[fusion] = plan.forward(x, normalized).cpu().numpy()
-        err = rel_l2(got[fusion], want)
-        print(f"stft {real} n_fft={n_fft} hop={hop} length={length} {pad_mode} fusion={fusion}: err {err:.3g} tol {tol(plan, real):.3g}")
+        err, emax = rel_l2(got[fusion], want), max_rel(got[fusion], want)
+        print(f"stft {real} n_fft={n_fft} hop={hop} length={length} {pad_mode} fusion={fusion}: err {err:.3g} tol {tol(plan, real):.3g} "
+              f"max_rel {emax:.3g}")
         assert err <= tol(plan, real), (real, n_fft, hop, length, pad_mode, fusion, err, d)
+        # the largest single error over the largest value, within twice the L2 bound (the ratio tests/test_gpu_parity.py grants,
+        # tmax = 2 tl2): one wrong element among thousands hides in the L2 norm, not here
+        assert emax <= 2 * tol(plan, real), (real, n_fft, hop, length, pad_mode, fusion, emax, d)
     assert rel_l2(got[1], got[0]) <= tol(plan, real)
     return plan
 
@@ -204,3 +209,105 @@ def test_torch_layer(torch, fa):
         fa.istft(torch.zeros(4, 100, 9, dtype=torch.complex64, device="cuda"), 256)
     with pytest.raises(ValueError):
         fa.istft(torch.zeros(4, 129, 9, dtype=torch.complex64, device="cuda"), 256, length=8 * 64 + 1)
+
+
+@pytest.mark.parametrize("n_fft", [128, 256, 1024])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_input_on_an_odd_element(torch, fa, real, n_fft):
+    """The output is complex and always aligned to a pair; the real input is not.  Rows that start one element into their allocation
+    (the fused route then loads single reals where it otherwise loads pairs): against the truth, bit-equal to the result from an
+    aligned copy of the same rows on the same route, the elements around the output and the input buffer itself untouched."""
+    n, hop = n_fft, n_fft // 4
+    dt, ct = rdtype(torch, real), torch.complex64 if real == "f32" else torch.complex128
+    g = torch.Generator(device="cuda").manual_seed(n)
+    length, batch = 3 * n + 2, 2
+    base = torch.randn(batch * length + 2, dtype=dt, device="cuda", generator=g)
+    before = base.clone()
+    x = base[1:-1].view(batch, length)
+    xa = x.clone()
+    assert x.data_ptr() % (2 * x.element_size()) != 0 and xa.data_ptr() % (2 * x.element_size()) == 0
+    plan = make(fa, real, n, hop)
+    w = 0.5 + torch.rand(n, dtype=dt, device="cuda", generator=g)
+    plan.set_window(w)
+    nf = plan.frames(length)
+    want = truth.stft(xa.cpu().numpy(), n, hop, n, w.cpu().numpy(), "reflect")
+    count = batch * nf * plan.bins()
+    for fusion in (1, 0):
+        plan.set_option("fusion", fusion)
+        fused = fusion == 1 and has_fused(real, n)
+        assert plan.describe().startswith("stft fused rows" if fused else "stft composed"), plan.describe()
+        aligned = plan.forward(xa)
+        buf = torch.full((count + 2,), SENTINEL, dtype=ct, device="cuda")
+        out = buf[1:1 + count].view(batch, nf, plan.bins())
+        assert plan.forward(x, out=out) is out
+        err, emax = rel_l2(out.cpu().numpy(), want), max_rel(out.cpu().numpy(), want)
+        print(f"stft odd input {real} n_fft={n} fusion={fusion}: err {err:.3g} max_rel {emax:.3g} tol {tol(plan, real):.3g}")
+        assert err <= tol(plan, real) and emax <= 2 * tol(plan, real), (real, n, fusion, err, emax)
+        assert buf[0].item() == SENTINEL and buf[-1].item() == SENTINEL, "an element beside the output was written"
+        assert torch.equal(torch.view_as_real(out), torch.view_as_real(aligned)), (real, n, fusion)
+        assert torch.equal(base, before), "forward modified its input"
+
+
+@pytest.mark.parametrize("n_fft", FUSED_N)
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_fused_forward_is_repeatable(torch, fa, real, n_fft):
+    """The same fused forward twenty times into fresh outputs: every result bit-equal to the first (a race on the kernel's LDS
+    buffers shows as a difference between runs).  Where the precision has no fused kernel of the length the composed route runs."""
+    n, hop = n_fft, n_fft // 4
+    g = torch.Generator(device="cuda").manual_seed(n)
+    dt, ct = rdtype(torch, real), torch.complex64 if real == "f32" else torch.complex128
+    length, batch = 5 * n + 3, 3
+    x = torch.randn(batch, length, dtype=dt, device="cuda", generator=g)
+    plan = make(fa, real, n, hop)
+    plan.set_option("fusion", 1)
+    assert plan.describe().startswith("stft fused rows" if has_fused(real, n) else "stft composed"), plan.describe()
+    nf = plan.frames(length)
+    outs = [torch.full((batch, nf, plan.bins()), float("nan"), dtype=ct, device="cuda") for _ in range(20)]
+    for out in outs:
+        plan.forward(x, out=out)
+    torch.cuda.synchronize()
+    err = rel_l2(outs[0].cpu().numpy(), truth.stft(x.cpu().numpy(), n, hop, n, None, "reflect"))
+    assert err <= tol(plan, real), (real, n, err)
+    for i, out in enumerate(outs[1:]):
+        assert torch.equal(torch.view_as_real(out), torch.view_as_real(outs[0])), (real, n, "run", i + 1)
+
+
+@pytest.mark.parametrize("fusion", [1, 0])
+def test_graph_replay_on_a_side_stream_after_reserve(torch, fa, fusion):
+    """Forward and inverse captured on a side stream as the first calls of a handle that reserved (they must not allocate), replayed
+    twice on new input contents: bit-equal to the eager calls, and within tolerance of the truth."""
+    n, hop, length, batch = 256, 64, 5 * 256, 3  # a length the frames give back in full: reserve() then covers the inverse to it
+    g = torch.Generator(device="cuda").manual_seed(12)
+    xs = [torch.randn(batch, length, dtype=torch.float32, device="cuda", generator=g) for _ in range(3)]
+    w = 0.5 + torch.rand(n, dtype=torch.float32, device="cuda", generator=g)
+    side = torch.cuda.Stream()
+    other = make(fa, "f32", n, hop)  # loads the kernels' code object (the first launch of a module is not capturable)
+    other.set_option("fusion", fusion)
+    with torch.cuda.stream(side):
+        other.inverse(other.forward(xs[0]), length)
+    side.synchronize()
+    plan = make(fa, "f32", n, hop)
+    plan.set_option("fusion", fusion)
+    plan.set_window(w)
+    assert plan.describe().startswith("stft fused rows" if fusion else "stft composed"), plan.describe()
+    plan.reserve(length, batch)
+    nf = plan.frames(length)
+    torch.cuda.synchronize()
+    d = xs[0].clone()
+    X = torch.empty(batch, nf, plan.bins(), dtype=torch.complex64, device="cuda")
+    y = torch.empty(batch, length, dtype=torch.float32, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        plan.forward(d, out=X)  # the first calls on this plan: captured
+        plan.inverse(X, length, out=y)
+    wh = w.cpu().numpy()
+    for x in xs[1:]:
+        d.copy_(x)
+        graph.replay()
+        torch.cuda.synchronize()
+        eX = plan.forward(x)
+        ey = plan.inverse(eX, length)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.view_as_real(X), torch.view_as_real(eX)) and torch.equal(y, ey), fusion
+        assert rel_l2(X.cpu().numpy(), truth.stft(x.cpu().numpy(), n, hop, n, wh, "reflect")) <= tol(plan, "f32")
+        assert rel_l2(y.cpu().numpy(), truth.istft(X.cpu().numpy(), n, hop, length, None, wh, "reflect")) <= tol(plan, "f32", True)
