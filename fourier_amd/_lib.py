@@ -55,6 +55,12 @@ _MDCT = ("fourier_hip_mdct_", {  # modified discrete cosine transform and its in
     "forward": (ci, [vp, vp, vp, sz, sz, ci, vp]),      # handle, d_in, d_out, length, batch, normalized, stream
     "inverse": (ci, [vp, vp, vp, sz, sz, sz, ci, vp]),  # handle, d_in, d_out, frames, length, batch, normalized, stream
     "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_SPECTROGRAM = ("fourier_hip_spectrogram_", {  # power spectrogram and Welch average on the STFT's frames
+    "create": (vp, [sz, sz, sz, ci, ci]), "destroy": (None, [vp]), "n_fft": (sz, [vp]), "hop": (sz, [vp]), "win_length": (sz, [vp]),
+    "bins": (sz, [vp]), "frames": (sz, [vp, sz]), "set_window": (ci, [vp, vp, vp]),
+    "forward": (ci, [vp, vp, vp, sz, sz, ci, ci, vp]),           # handle, d_in, d_out, length, batch, power, normalized, stream
+    "welch": (ci, [vp, vp, vp, sz, sz, ci, ctypes.c_double, vp]),  # handle, d_in, d_out, length, batch, onesided_fold, scale, stream
+    "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -74,7 +80,9 @@ CONV_SYMBOLS = list(_signatures(_CONV))
 LCONV_SYMBOLS = list(_signatures(_LCONV))
 STFT_SYMBOLS = list(_signatures(_STFT))
 MDCT_SYMBOLS = list(_signatures(_MDCT))
-ALL_SYMBOLS = LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
+SPECTROGRAM_SYMBOLS = list(_signatures(_SPECTROGRAM))
+ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
+               + SPECTROGRAM_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -84,7 +92,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -20,6 +20,7 @@
 #include "r2r_plan.h"
 #include "stft_plan.h"
 #include "mdct_plan.h"
+#include "spectrogram_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -349,6 +350,55 @@ FOURIER_DEFINE_STFT_ABI(double, double)
 
 FOURIER_DEFINE_MDCT_ABI(float, float)
 FOURIER_DEFINE_MDCT_ABI(double, double)
+
+// power spectrogram and Welch average on the STFT's frames (fourier_hip_spectrogram_*)
+#define FOURIER_DEFINE_SPECTROGRAM_ABI(T, SUFFIX)                                                                \
+  extern "C" fc::fourier_spectrogram_##SUFFIX* fourier_hip_spectrogram_create_##SUFFIX(size_t n_fft, size_t hop, size_t win_length, int pad_mode, \
+                                                                                      int device) {              \
+    return (fc::fourier_spectrogram_##SUFFIX*)create_handle<SpectrogramPlan<T>>(n_fft, hop, win_length, pad_mode, device); \
+  }                                                                                                              \
+  extern "C" void fourier_hip_spectrogram_destroy_##SUFFIX(fc::fourier_spectrogram_##SUFFIX* h) { destroy_handle<SpectrogramPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_spectrogram_describe_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) { return describe_handle<SpectrogramPlan<T>>(h); } \
+  extern "C" int fourier_hip_spectrogram_last_status_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) { return last_status_of<SpectrogramPlan<T>>(h); } \
+  extern "C" int fourier_hip_spectrogram_set_option_##SUFFIX(fc::fourier_spectrogram_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<SpectrogramPlan<T>>(h, key, v);                                                     \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_spectrogram_n_fft_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) {          \
+    return h ? ((const SpectrogramPlan<T>*)h)->n_fft() : 0;                                                      \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_spectrogram_hop_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) {            \
+    return h ? ((const SpectrogramPlan<T>*)h)->hop() : 0;                                                        \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_spectrogram_win_length_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) {     \
+    return h ? ((const SpectrogramPlan<T>*)h)->win_length() : 0;                                                 \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_spectrogram_bins_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h) {           \
+    return h ? ((const SpectrogramPlan<T>*)h)->bins() : 0;                                                       \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_spectrogram_frames_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h, size_t length) { \
+    return h ? ((const SpectrogramPlan<T>*)h)->frames(length) : 0;                                               \
+  }                                                                                                              \
+  extern "C" int fourier_hip_spectrogram_set_window_##SUFFIX(fc::fourier_spectrogram_##SUFFIX* h, const void* d_window, void* stream) { \
+    SpectrogramPlan<T>* p = (SpectrogramPlan<T>*)h;                                                              \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_spectrogram_reserve_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h, size_t length, size_t batch) { \
+    const SpectrogramPlan<T>* p = (const SpectrogramPlan<T>*)h;                                                  \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_spectrogram_forward_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                          size_t batch, int power, int normalized, void* stream) { \
+    const SpectrogramPlan<T>* p = (const SpectrogramPlan<T>*)h;                                                  \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, length, batch, power, normalized != 0, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_spectrogram_welch_##SUFFIX(const fc::fourier_spectrogram_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                        size_t batch, int onesided_fold, double scale, void* stream) { \
+    const SpectrogramPlan<T>* p = (const SpectrogramPlan<T>*)h;                                                  \
+    return guarded_handle(p, [&] { p->welch(d_in, d_out, length, batch, onesided_fold != 0, scale, (hipStream_t)stream); }); \
+  }
+
+FOURIER_DEFINE_SPECTROGRAM_ABI(float, float)
+FOURIER_DEFINE_SPECTROGRAM_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -176,6 +176,10 @@ struct StftRowsKernel { StftKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS
 typedef void (*MdctKernel)(MdctArgs);
 // the fused frame route of the MDCT handle on a whole-row kernel's tile shape (kernels_mdct.h); fn == nullptr: none for that length
 struct MdctRowsKernel { MdctKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
+typedef void (*SpectrogramKernel)(SpectrogramArgs);
+// the fused frame route of the spectrogram handle on a whole-row kernel's tile shape (kernels_spectrogram.h), one kernel per epilogue:
+// fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL]; fn[SPEC_POWER] == nullptr: none for that length
+struct SpectrogramRowsKernel { SpectrogramKernel fn[4] = {nullptr, nullptr, nullptr, nullptr}; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -267,6 +271,10 @@ template <typename T> struct Real {};
   /* route for n = 2 L coefficients on the whole-row kernel of length L                                                */ \
   MdctKernel get_mdct_kernel(Real<T>, int which);                                                                      \
   MdctRowsKernel get_mdct_rows_kernel(Real<T>, int L);                                                                 \
+  /* kernels_spectrogram.cpp: the sweeps of the spectrogram handle, which = SPECTROGRAM_POWER_SWEEP ... (kernel_args.h); its */ \
+  /* fused frame route for n_fft = 2 L on the whole-row kernel of length L                                             */ \
+  SpectrogramKernel get_spectrogram_kernel(Real<T>, int which);                                                        \
+  SpectrogramRowsKernel get_spectrogram_rows_kernel(Real<T>, int L);                                                   \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \

@@ -302,6 +302,26 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, mdct_rows_.fn, (a.total + mdct_rows_.COLS - 1) / mdct_rows_.COLS, mdct_rows_.NT, mdct_rows_.smem, stream, a);
   }
 
+  // The fused frame route of the spectrogram handle (spectrogram_rows_kernel; spectrogram_plan.h), under the same condition as the STFT's:
+  // this plan, of h = n_fft / 2 points, is ONE whole-row pass and kernels_spectrogram.cpp holds the kernels on that pass's tile shape.
+  bool enable_spectrogram_rows() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
+    if (spec_rows_.fn[SPEC_POWER]) return true;
+    const SpectrogramRowsKernel k = get_spectrogram_rows_kernel(Real<T>{}, passes_[0]->k.L);
+    if (!k.fn[SPEC_POWER] || k.L != passes_[0]->k.L) return false;
+    for (int out = SPEC_MAGNITUDE; out <= SPEC_PARTIAL; ++out) raise_smem_limit((const void*)k.fn[out], k.smem);
+    spec_rows_ = k;
+    return true;
+  }
+  int spectrogram_cols() const { return spec_rows_.COLS; }
+  // a: everything but the stage tables; `groups` workgroups of COLS frames each, below 2^31 (the caller bounds a launch)
+  void run_spectrogram_rows(SpectrogramArgs a, int out, uint64_t groups, hipStream_t stream) const {
+    if (groups == 0) return;
+    const Pass& ps = *passes_[0];
+    a.f.tw1 = ps.st->tw1.p; a.f.tw2 = ps.st->tw2.p;
+    launch(nullptr, 0, spec_rows_.fn[out], groups, spec_rows_.NT, spec_rows_.smem, stream, a);
+  }
+
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
   void init_l2fused(int k) {
     FusedInfo fi;
@@ -698,6 +718,7 @@ template <typename T> class Pow2Engine {
   StageTables<T>* conv_st_ = nullptr;
   StftRowsKernel stft_rows_;
   MdctRowsKernel mdct_rows_;
+  SpectrogramRowsKernel spec_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -224,6 +224,30 @@ struct StftArgs {
   double scale;
 };
 
+// ---- power spectrogram and Welch average (kernels_spectrogram.h; SpectrogramPlan, spectrogram_plan.h)
+// `f` is the STFT's argument block: the frame geometry, the window, the tables, and f.in / f.out of the launch.  The fused kernel reads
+// it as stft_rows_kernel does and writes reals: OUT = SPEC_POWER / SPEC_MAGNITUDE the h + 1 values of item i at f.out + i * (h + 1);
+// OUT = SPEC_PARTIAL one row of h + 1 partial sums per workgroup at part + blk * (h + 1), workgroup blk = row * tiles + tile over the
+// frames tile * COLS ... of that row (f.in at the first sample of row 0 of the launch).  The sweeps: spectrogram_power_kernel |z|^power
+// over `count` complex values f.in -> reals f.out; welch_colsum_kernel one lane per (slot, bin) of `count` / bins slots from slot0 on,
+// slot v = row * tiles + t the frames t * tile_frames ... of a row, over the flat frames g0 ... g1 - 1 whose transforms lie at f.in
+// (frame g at (g - g0) * bins); welch_reduce_kernel `count` = rows * bins lanes, f.out[b, k] = scale * c_k * sum_t part[b][t][k].
+enum { SPEC_MAGNITUDE = 1, SPEC_POWER = 2, SPEC_PARTIAL = 3 };  // 1, 2: FOURIER_SPECTROGRAM_MAGNITUDE / _POWER (include/fourier.h)
+enum { SPECTROGRAM_POWER_SWEEP = 0, WELCH_COLSUM = 1, WELCH_REDUCE = 2 };
+struct SpectrogramArgs {
+  StftArgs f;
+  void* part;                 // Welch: the partial sums, rows x tiles x bins reals
+  uint32_t tiles;             // Welch: slots per row
+  uint32_t tl_m, tl_l;        // fused: blk / tiles = (umulhi(blk, tl_m) + blk) >> tl_l
+  uint32_t bins;
+  uint32_t tile_frames;       // composed Welch: frames per slot
+  uint32_t power;             // spectrogram_power_kernel: SPEC_MAGNITUDE / SPEC_POWER
+  int fold;                   // reduce: c_k = 2 for the bins with a mirror, 0 < 2k < n_fft
+  uint64_t slot0, g0, g1;     // composed Welch: first slot of the launch, the chunk's flat frame range (from row 0 of the group)
+  uint64_t count;             // sweeps: lanes
+  double scale;               // reduce: the caller's scale over frames
+};
+
 // ---- modified discrete cosine transform (kernels_mdct.h; MdctPlan, mdct_plan.h)
 // A frame is 2n samples, the hop n; frame f of a row covers xpad[f n - pad ... f n - pad + 2n), zero outside the row.  The flat frame
 // index, `first`, `total` and the multiply-high division are StftArgs'.  Even n = 2h: a frame is h complex values in the scratch

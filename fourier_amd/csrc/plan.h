@@ -609,6 +609,19 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_mdct_rows(a, stream);
   }
 
+  // ---- the hook of the spectrogram handle (SpectrogramPlan, spectrogram_plan.h), as the STFT's: the frames of n_fft = 2h samples in one
+  // launch of spectrogram_rows_kernel, `out` = SPEC_MAGNITUDE / SPEC_POWER / SPEC_PARTIAL, `groups` workgroups of spectrogram_cols() frames.
+  bool enable_spectrogram() {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_spectrogram_rows();
+  }
+  int spectrogram_cols() const { return eng_->spectrogram_cols(); }
+  void exec_spectrogram(const SpectrogramArgs& a, int out, uint64_t groups, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_spectrogram_rows(a, out, groups, stream);
+  }
+
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).
   void synchronize(hipStream_t stream) const {
     DeviceGuard g(device_);

@@ -52,6 +52,21 @@ template <typename T> class StftPlan : public HandleBase {
   size_t win_length() const { return wl_; }
   size_t bins() const { return bins_; }
 
+  // what the spectrogram handle (spectrogram_plan.h) builds its routes from: the framing, the window table and the real plan
+  size_t pad() const { return pad_; }
+  const void* window() const { return win_.p; }
+  const RealPlan<T>& real() const { return *real_; }
+  bool enable_spectrogram() { return real_->enable_spectrogram(); }
+  // the argument block of a forward launch, all but in, out, first, total (and the fused route's tw, scale, pairs)
+  StftArgs frame_args(size_t length, size_t fr) const {
+    StftArgs a{};
+    a.win = win_.p;
+    a.length = length; a.frames = (uint32_t)fr;
+    divider(a.frames, a.fr_m, a.fr_l);
+    a.n_fft = (uint32_t)n_; a.hop = (uint32_t)hop_; a.pad = (uint32_t)pad_; a.mode = (uint32_t)mode_;
+    a.scale = 1.0;
+    return a;
+  }
   // frames of a row of `length` reals; 0 where the length is invalid
   size_t frames(size_t length) const {
     size_t f = 0;
@@ -189,15 +204,6 @@ template <typename T> class StftPlan : public HandleBase {
   }
   void refresh_desc() {
     desc_ = std::string(fused_ ? "stft fused rows" : "stft composed") + ", istft composed: " + real_->describe();
-  }
-  StftArgs frame_args(size_t length, size_t fr) const {
-    StftArgs a{};
-    a.win = win_.p;
-    a.length = length; a.frames = (uint32_t)fr;
-    divider(a.frames, a.fr_m, a.fr_l);
-    a.n_fft = (uint32_t)n_; a.hop = (uint32_t)hop_; a.pad = (uint32_t)pad_; a.mode = (uint32_t)mode_;
-    a.scale = 1.0;
-    return a;
   }
   // the window centred in the frame, (n_fft - win_length) / 2 zeros in front: the device table in T, the host copy in f64
   void load_window(const std::vector<T>& w) {

@@ -806,7 +806,7 @@ def create_stft_f64(n_fft, hop_length=None, win_length=None, center=True, pad_mo
     return Stft(n_fft, "f64", hop_length, win_length, center, pad_mode, device)
 
 
-def _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, real):
+def _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, real, cls=None):
     """The cached handle of these parameters with `window` set (on every call, like fftconv's filters)."""
     n_fft = int(n_fft)
     hop = n_fft // 4 if hop_length is None else int(hop_length)
@@ -820,7 +820,7 @@ def _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, real)
         if tuple(window.shape) != (wl,):
             raise ValueError(f"window must have shape ({wl},), got {tuple(window.shape)}")
         window = window.contiguous()
-    p = _cached_plan(Stft, n_fft, real, hop, wl, mode != "none", "reflect" if mode == "none" else mode, int(_device_index(x)))
+    p = _cached_plan(cls or Stft, n_fft, real, hop, wl, mode != "none", "reflect" if mode == "none" else mode, int(_device_index(x)))
     p.set_window(window)
     return p
 
@@ -856,6 +856,189 @@ def istft(X, n_fft, hop_length=None, win_length=None, window=None, center=True, 
         raise ValueError(f"expected (..., {int(n_fft) // 2 + 1}, frames >= 1), got {tuple(X.shape)}")
     p = _stft_plan(X, n_fft, hop_length, win_length, window, center, "reflect", _precision(X.dtype)[0])
     return p.inverse(X.transpose(-1, -2).contiguous(), length, normalized)
+
+
+SPECTROGRAM_POWERS = {"magnitude": 1, "power": 2}  # FOURIER_SPECTROGRAM_MAGNITUDE / _POWER
+
+
+def _spectrogram_power(power):
+    if power in (1, 2):  # (1.0 and 2.0 compare equal: torchaudio's power is a float)
+        return int(power)
+    raise ValueError(f"power must be 1 (magnitude) or 2 (power), got {power!r}")
+
+
+class Spectrogram(_Handle):
+    """Batched power spectrogram and Welch average (include/fourier.h, fourier_hip_spectrogram_*) on device memory: |X|^p of the frames X
+    an Stft of the same parameters gives, FRAME-MAJOR reals (frame f of row b at element offset (b * frames + f) * bins), and the mean
+    over the frames of |X|^2 -- neither writes the complex frames.  n_fft, hop, win_length and the padding are fixed at create; the
+    window is set afterwards (set_window; default all ones)."""
+
+    _prefix = "fourier_hip_spectrogram_"
+    _destroy = "fourier_hip_spectrogram_destroy"
+
+    def __init__(self, n_fft, real="f32", hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+        n_fft = int(n_fft)
+        hop = n_fft // 4 if hop_length is None else int(hop_length)
+        wl = n_fft if win_length is None else int(win_length)
+        self.pad_mode = _stft_pad_mode(center, pad_mode)
+        if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+            raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+        self._create(real, f"spectrogram plan of n_fft {n_fft}, hop {hop}, win_length {wl}, padding {self.pad_mode}", n_fft, hop, wl,
+                     STFT_PAD_MODES[self.pad_mode], int(device))
+        self._n, self._hop, self._wl = n_fft, hop, wl
+
+    def n_fft(self):
+        return self._n
+
+    def hop(self):
+        return self._hop
+
+    def win_length(self):
+        return self._wl
+
+    def bins(self):
+        return self._n // 2 + 1
+
+    def frames(self, length):
+        """Frames of a row of `length` reals; 0 where the length is invalid."""
+        return int(self._fn("frames")(self._h, int(length)))
+
+    def set_option(self, key, value):
+        """"fusion": 0 = the composed routes (the default), 1 = the fused one-launch routes wherever they exist."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def reserve(self, length, batch):
+        """Later forward and welch calls of at most `batch` rows of `length` reals never allocate (on the route selected now)."""
+        self._call("reserve", int(length), int(batch))
+
+    def set_window_ptr(self, d_window, stream=0):
+        """win_length() reals of the handle's precision at d_window (0 / None: all ones).  Waits for `stream`."""
+        self._call("set_window", d_window or None, stream)
+
+    def forward_ptr(self, d_in, d_out, length, batch, power=2, normalized=False, stream=0):
+        """`batch` rows of `length` reals at d_in -> batch x frames(length) x bins() reals |X|^power at d_out, enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(length), int(batch), int(power), int(bool(normalized)), stream)
+
+    def welch_ptr(self, d_in, d_out, length, batch, onesided_fold=True, scale=1.0, stream=0):
+        """`batch` rows of `length` reals at d_in -> batch x bins() reals scale * c_k / frames * sum_f |X|^2 at d_out, on `stream`."""
+        self._call("welch", d_in, d_out, int(length), int(batch), int(bool(onesided_fold)), float(scale), stream)
+
+    def set_window(self, window):
+        """A contiguous CUDA tensor of win_length() reals of the handle's precision, or None for all ones; on the current stream."""
+        if window is None:
+            return self.set_window_ptr(None)
+        _require_cuda(window, _torch_dtypes(self.real)[0])
+        if tuple(window.shape) != (self._wl,):
+            raise ValueError(f"window must have shape ({self._wl},), got {tuple(window.shape)}")
+        self.set_window_ptr(window.data_ptr(), _stream(window))
+
+    def _rows(self, x):
+        rdt = _torch_dtypes(self.real)[0]
+        _require_cuda(x, rdt)
+        if x.dim() == 0:
+            raise ValueError("expected at least one dimension")
+        length = int(x.shape[-1])
+        fr = self.frames(length)
+        if fr == 0:
+            raise ValueError(f"a row of {length} samples is too short for n_fft {self._n} with padding {self.pad_mode}")
+        return rdt, length, fr
+
+    def forward(self, x, power=2, normalized=False, out=None):
+        """Contiguous (..., length) real CUDA tensor -> a new (..., frames, bins) real tensor |X|^power (frame-major), or `out`, on the
+        current stream."""
+        import torch
+
+        power = _spectrogram_power(power)
+        rdt, length, fr = self._rows(x)
+        shape = tuple(x.shape[:-1]) + (fr, self.bins())
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=x.device)
+        else:
+            _require_out(out, shape, rdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), length, batch, power, normalized, _stream(x))
+        return out
+
+    def welch(self, x, onesided_fold=True, scale=1.0, out=None):
+        """Contiguous (..., length) real CUDA tensor -> a new (..., bins) real tensor scale * c_k / frames * sum_f |X|^2, or `out`, on
+        the current stream.  No detrending."""
+        import torch
+
+        rdt, length, fr = self._rows(x)
+        shape = tuple(x.shape[:-1]) + (self.bins(),)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=x.device)
+        else:
+            _require_out(out, shape, rdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.welch_ptr(x.data_ptr(), out.data_ptr(), length, batch, onesided_fold, scale, _stream(x))
+        return out
+
+
+def create_spectrogram_f32(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return Spectrogram(n_fft, "f32", hop_length, win_length, center, pad_mode, device)
+
+
+def create_spectrogram_f64(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return Spectrogram(n_fft, "f64", hop_length, win_length, center, pad_mode, device)
+
+
+def _real_rows(x):
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    return _precision(x.dtype)[0]
+
+
+def spectrogram(x, n_fft, hop_length=None, win_length=None, window=None, center=True, pad_mode="reflect", power=2.0, normalized=False):
+    """torchaudio.transforms.Spectrogram of a float32 / float64 CUDA tensor of shape (..., length) on the current stream: |stft|^power
+    with power 1 or 2, torch.stft's defaults (hop_length n_fft // 4, win_length n_fft, window of ones) and `normalized` as torch.stft's
+    flag (the frames times n_fft^-1/2).  Returns shape (..., frames, bins), FRAME-MAJOR and contiguous like the buffer the library
+    writes -- torchaudio's (..., bins, frames) is its transpose(-1, -2).  Leading dimensions fold into the batch.  Handles are cached
+    per (n_fft, hop, win_length, padding, dtype, device) and the window is set on EVERY call; keep a Spectrogram to reuse one."""
+    real = _real_rows(x)
+    power = _spectrogram_power(power)
+    p = _stft_plan(x, n_fft, hop_length, win_length, window, center, pad_mode, real, Spectrogram)
+    return p.forward(x.contiguous(), power, normalized)
+
+
+WELCH_SCALINGS = ("density", "spectrum")
+
+
+def welch(x, fs=1.0, window=None, nperseg=256, noverlap=None, scaling="density", return_onesided=True):
+    """scipy.signal.welch(x, fs, window, nperseg, noverlap, detrend=False, scaling=scaling, average="mean") along the last axis of a
+    float32 / float64 CUDA tensor of shape (..., length) on the current stream.  Segments of nperseg samples every nperseg - noverlap
+    (noverlap defaults to nperseg // 2), no padding, the periodic Hann window where `window` is None, else a CUDA tensor of nperseg
+    values.  scaling "density" gives V^2 / Hz (scale 1 / (fs sum w^2)), "spectrum" V^2 (1 / (sum w)^2), both computed on the host in
+    f64 from the window.  Returns (freqs, Pxx): nperseg // 2 + 1 frequencies k fs / nperseg and (..., nperseg // 2 + 1) values; with
+    return_onesided the bins that have a mirror count twice, without it they do not (the one-sided HALF of the two-sided spectrum).
+    NO DETRENDING: scipy's default, detrend="constant", removes every segment's mean first; this never does, and offers no `detrend`
+    argument.  Subtract the mean yourself where the difference at the lowest bins matters."""
+    import torch
+
+    real = _real_rows(x)
+    nperseg = int(nperseg)
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if nperseg < 1 or not 0 <= noverlap < nperseg:
+        raise ValueError(f"need nperseg >= 1 and 0 <= noverlap < nperseg, got {nperseg}, {noverlap}")
+    if scaling not in WELCH_SCALINGS:
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    if not float(fs) > 0:
+        raise ValueError(f"fs must be positive, got {fs!r}")
+    if x.shape[-1] < nperseg:
+        raise ValueError(f"a row of {x.shape[-1]} samples is shorter than nperseg {nperseg}")
+    if window is None:
+        window = torch.hann_window(nperseg, periodic=True, dtype=torch.float64, device=x.device).to(x.dtype)
+    p = _stft_plan(x, nperseg, nperseg - noverlap, nperseg, window, False, "reflect", real, Spectrogram)
+    w = window.detach().to(torch.float64).cpu()
+    scale = 1.0 / (float(fs) * float((w * w).sum())) if scaling == "density" else 1.0 / float(w.sum()) ** 2
+    freqs = torch.arange(nperseg // 2 + 1, dtype=x.dtype, device=x.device) * (float(fs) / nperseg)
+    return freqs, p.welch(x.contiguous(), bool(return_onesided), scale)
 
 
 class Mdct(_Handle):

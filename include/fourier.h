@@ -788,6 +788,86 @@ const char *fourier_hip_mdct_describe_double(const FOURIER_STRUCT fourier_mdct_d
 int fourier_hip_mdct_last_status_float(const FOURIER_STRUCT fourier_mdct_float *);
 int fourier_hip_mdct_last_status_double(const FOURIER_STRUCT fourier_mdct_double *);
 
+/* ---------------- power spectrogram and Welch power spectral density (extension; the reference has none) ----------
+ * |X|^p of the short-time Fourier transform's frames, and the mean of |X|^2 over a row's frames, on DEVICE memory, without the complex
+ * frames being written anywhere the caller sees.  A handle is made with the STFT handle's parameters (n_fft, hop, win_length, pad mode
+ * FOURIER_STFT_PAD_*): the framing, the centring of the window, fourier_hip_spectrogram_frames_* and fourier_hip_spectrogram_set_window_*
+ * (win_length reals T on the device, NULL: all ones; a set-up call that waits for `stream`) are exactly those of fourier_hip_stft_*, and
+ * X[b, f, k] below is exactly what fourier_hip_stft_forward_* produces for the same arguments.  bins = n_fft / 2 + 1.
+ * fourier_hip_spectrogram_forward_*: `batch` contiguous rows of `length` reals in; batch x frames x bins REALS out, FRAME-MAJOR (frame f of
+ * row b at element offset (b * frames + f) * bins),
+ *   out[b, f, k] = |X[b, f, k]|^power,   power = FOURIER_SPECTROGRAM_MAGNITUDE (1) or FOURIER_SPECTROGRAM_POWER (2),
+ * X times n_fft^-1/2 where normalized != 0.  Any other power gives FOURIER_HIP_INVALID_ARGUMENT.
+ * fourier_hip_spectrogram_welch_*: the same rows in; batch x bins reals out,
+ *   out[b, k] = scale * c_k / frames * sum_f |X[b, f, k]|^2   with the unnormalized X,
+ * c_k = 2 where onesided_fold != 0 and bin k has a mirror (0 < k < n_fft / 2, and also k = (n_fft - 1) / 2 for odd n_fft), else 1.
+ * Welch's method with the mean over the frames: scipy.signal.welch(detrend = False, average = "mean") with PAD_NONE,
+ * hop = nperseg - noverlap, scale = 1 / (fs sum w^2) for a density and 1 / (sum w)^2 for a spectrum.  There is NO detrending: scipy's
+ * default removes each segment's mean first, this does not.
+ * Determinism: no atomics.  Every sum over frames runs in an order fixed by the route, the shape and the scratch bound, so two calls
+ * with equal arguments on one handle give bit-equal results.
+ * A NULL handle or pointer, reals not aligned to sizeof(T), any overlap of d_in and d_out or an invalid length give
+ * FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_spectrogram_describe_*: "spectrogram <route>, welch <route>: <the real plan's describe>"):
+ *   "fused rows"  n_fft = 2h whose h-point plan is one whole-row kernel (n_fft 128 ... 1024, f32 also 2048), wherever "stft fused rows"
+ *                 exists: gather, window, transform, untangle and |.|^p in ONE launch, no scratch.  Welch: one workgroup per tile of
+ *                 frames of one row sums its frames' powers in ascending order into a row of partials in a handle-owned buffer, a
+ *                 second sweep sums a row's tiles in ascending order.
+ *   "composed"    any n_fft: per chunk of the flat frame index a gather sweep, the real-input plan into a handle-owned scratch (at
+ *                 most 1 GiB, never less than one frame), then a sweep that writes |.|^p or adds the chunk's powers to the partials.
+ * Option "fusion" = 1 takes the fused routes wherever they exist, 0 the composed ones (the default: the fused kernels have not been
+ * measured on the device yet).  The partials stay within
+ * the scratch bound too (never less than one row's): more rows are walked in groups.  fourier_hip_spectrogram_reserve_*(h, length, batch)
+ * sizes everything both entry points need for at most `batch` rows of `length` reals on the route selected at that time: they then
+ * never allocate.  Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_spectrogram_last_status_*. */
+enum {
+  FOURIER_SPECTROGRAM_MAGNITUDE = 1,
+  FOURIER_SPECTROGRAM_POWER = 2,
+};
+struct fourier_spectrogram_float;
+struct fourier_spectrogram_double;
+
+/* NULL on failure (parameters outside the STFT handle's ranges included). */
+struct fourier_spectrogram_float *fourier_hip_spectrogram_create_float(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop,
+                                                                       FOURIER_SIZE_TYPE win_length, int pad_mode, int device);
+struct fourier_spectrogram_double *fourier_hip_spectrogram_create_double(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop,
+                                                                         FOURIER_SIZE_TYPE win_length, int pad_mode, int device);
+/* NULL is a no-op. */
+void fourier_hip_spectrogram_destroy_float(FOURIER_STRUCT fourier_spectrogram_float *);
+void fourier_hip_spectrogram_destroy_double(FOURIER_STRUCT fourier_spectrogram_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_n_fft_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_n_fft_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_hop_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_hop_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_win_length_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_win_length_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_bins_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_bins_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+/* frames of a row of `length` reals; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_frames_float(const FOURIER_STRUCT fourier_spectrogram_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_spectrogram_frames_double(const FOURIER_STRUCT fourier_spectrogram_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_spectrogram_set_window_float(FOURIER_STRUCT fourier_spectrogram_float *, const void *d_window, void *stream);
+int fourier_hip_spectrogram_set_window_double(FOURIER_STRUCT fourier_spectrogram_double *, const void *d_window, void *stream);
+int fourier_hip_spectrogram_forward_float(const FOURIER_STRUCT fourier_spectrogram_float *, const void *d_in, void *d_out,
+                                          FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int power, int normalized, void *stream);
+int fourier_hip_spectrogram_forward_double(const FOURIER_STRUCT fourier_spectrogram_double *, const void *d_in, void *d_out,
+                                           FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int power, int normalized, void *stream);
+int fourier_hip_spectrogram_welch_float(const FOURIER_STRUCT fourier_spectrogram_float *, const void *d_in, void *d_out,
+                                        FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int onesided_fold, double scale, void *stream);
+int fourier_hip_spectrogram_welch_double(const FOURIER_STRUCT fourier_spectrogram_double *, const void *d_in, void *d_out,
+                                         FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int onesided_fold, double scale, void *stream);
+int fourier_hip_spectrogram_reserve_float(const FOURIER_STRUCT fourier_spectrogram_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_spectrogram_reserve_double(const FOURIER_STRUCT fourier_spectrogram_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed routes, 1 = the fused ones wherever they exist.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_spectrogram_set_option_float(FOURIER_STRUCT fourier_spectrogram_float *, const char *key, long long value);
+int fourier_hip_spectrogram_set_option_double(FOURIER_STRUCT fourier_spectrogram_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_spectrogram_describe_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+const char *fourier_hip_spectrogram_describe_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+int fourier_hip_spectrogram_last_status_float(const FOURIER_STRUCT fourier_spectrogram_float *);
+int fourier_hip_spectrogram_last_status_double(const FOURIER_STRUCT fourier_spectrogram_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1047,6 +1127,62 @@ template <typename T> struct mdct;
 FOURIER_DEFINE_CXX_MDCT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_MDCT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_MDCT_WRAPPER
+
+/* power spectrogram and Welch average on device memory (extension): fourier::spectrogram<float> / <double>; the pad modes are stft_pad */
+template <typename T> struct spectrogram;
+
+#define FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER(T, SUFFIX)                                          \
+  template <> struct spectrogram<T> {                                                              \
+    spectrogram(std::size_t n_fft, std::size_t hop, std::size_t win_length, stft_pad pad = stft_pad::reflect, int device = -1) \
+        : impl(::fourier::c::fourier_hip_spectrogram_create_##SUFFIX(n_fft, hop, win_length, static_cast<int>(pad), device), \
+               ::fourier::c::fourier_hip_spectrogram_destroy_##SUFFIX) {}                          \
+    spectrogram() = delete;                                                                        \
+    spectrogram(const spectrogram &) = delete;                                                     \
+    spectrogram(spectrogram &&) = default;                                                         \
+    spectrogram &operator=(const spectrogram &) = delete;                                          \
+    spectrogram &operator=(spectrogram &&) = default;                                              \
+    ~spectrogram() = default;                                                                      \
+    std::size_t n_fft() const { return ::fourier::c::fourier_hip_spectrogram_n_fft_##SUFFIX(impl.get()); } \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_spectrogram_hop_##SUFFIX(impl.get()); } \
+    std::size_t win_length() const { return ::fourier::c::fourier_hip_spectrogram_win_length_##SUFFIX(impl.get()); } \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_spectrogram_bins_##SUFFIX(impl.get()); } \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_spectrogram_frames_##SUFFIX(impl.get(), length);            \
+    }                                                                                              \
+    /* win_length reals on the device; nullptr: all ones */                                        \
+    int set_window(const void *d_window, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_spectrogram_set_window_##SUFFIX(impl.get(), d_window, stream); \
+    }                                                                                              \
+    /* batch rows of `length` reals -> batch x frames x bins reals |X|^power, frame-major */       \
+    int forward_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch,       \
+                       int power = ::fourier::c::FOURIER_SPECTROGRAM_POWER, bool normalized = false, \
+                       void *stream = nullptr) const {                                             \
+      return ::fourier::c::fourier_hip_spectrogram_forward_##SUFFIX(impl.get(), d_in, d_out, length, batch, \
+                                                                    power, normalized ? 1 : 0, stream); \
+    }                                                                                              \
+    /* batch rows of `length` reals -> batch x bins reals scale c_k / frames sum_f |X|^2 (no detrending) */ \
+    int welch_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch,         \
+                     bool onesided_fold = true, double scale = 1.0, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_spectrogram_welch_##SUFFIX(impl.get(), d_in, d_out, length, batch, \
+                                                                  onesided_fold ? 1 : 0, scale, stream); \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_spectrogram_reserve_##SUFFIX(impl.get(), length, batch);    \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_spectrogram_set_option_##SUFFIX(impl.get(), key, value);    \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_spectrogram_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_spectrogram_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_spectrogram_##SUFFIX,                                  \
+                      void (*)(::fourier::c::fourier_spectrogram_##SUFFIX *)> impl;                \
+  };
+FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
