@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 
@@ -171,15 +172,23 @@ typedef void (*BluKernel)(BluArgs);
 typedef void (*RealKernel)(RealArgs);
 typedef void (*R2RKernel)(R2RArgs);
 typedef void (*StftKernel)(StftArgs);
-// the fused frame route of the STFT handle on a whole-row kernel's tile shape (kernels_stft.h); fn == nullptr: none for that length
-struct StftRowsKernel { StftKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
 typedef void (*MdctKernel)(MdctArgs);
-// the fused frame route of the MDCT handle on a whole-row kernel's tile shape (kernels_mdct.h); fn == nullptr: none for that length
-struct MdctRowsKernel { MdctKernel fn = nullptr; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
 typedef void (*SpectrogramKernel)(SpectrogramArgs);
-// the fused frame route of the spectrogram handle on a whole-row kernel's tile shape (kernels_spectrogram.h), one kernel per epilogue:
-// fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL]; fn[SPEC_POWER] == nullptr: none for that length
-struct SpectrogramRowsKernel { SpectrogramKernel fn[4] = {nullptr, nullptr, nullptr, nullptr}; int L = 0, CG = 0, NT = 0, COLS = 0; size_t smem = 0; };
+// The fused frame route of a frame handle (STFT, MDCT, spectrogram) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
+// one shape.  STFT and MDCT have fn[0]; the spectrogram one per epilogue, fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL].
+// L == 0: none for that length
+template <typename Args> struct FrameRowsKernel {
+  void (*fn[4])(Args) = {nullptr, nullptr, nullptr, nullptr};
+  int L = 0, CG = 0, NT = 0, COLS = 0;
+  size_t smem = 0;
+};
+typedef FrameRowsKernel<StftArgs> StftRowsKernel;
+typedef FrameRowsKernel<MdctArgs> MdctRowsKernel;
+typedef FrameRowsKernel<SpectrogramArgs> SpectrogramRowsKernel;
+// the part of a frame kernel's argument block that holds the frame geometry and the row core's stage tables
+static inline StftArgs& frame_block(StftArgs& a) { return a; }
+static inline MdctArgs& frame_block(MdctArgs& a) { return a; }
+static inline StftArgs& frame_block(SpectrogramArgs& a) { return a.f; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -313,5 +322,9 @@ template <typename T> struct Real {};
 FOURIER_DECLARE_REGISTRY(float)
 FOURIER_DECLARE_REGISTRY(double)
 #undef FOURIER_DECLARE_REGISTRY
+// ... the three fused frame routes by their argument block
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, StftRowsKernel& k) { k = get_stft_rows_kernel(r, L); }
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, MdctRowsKernel& k) { k = get_mdct_rows_kernel(r, L); }
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, SpectrogramRowsKernel& k) { k = get_spectrogram_rows_kernel(r, L); }
 
 }  // namespace fourier_hip

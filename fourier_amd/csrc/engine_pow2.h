@@ -265,61 +265,33 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, (uint64_t)rows * g.wpr, k.NT, k.smem, stream, a);
   }
 
-  // The fused frame route of the STFT handle (stft_rows_kernel; stft_plan.h): available when this plan, of h = n_fft / 2 points, is ONE
-  // whole-row pass and kernels_stft.cpp holds the kernel on that pass's tile shape; it runs on this plan's stage tables.
-  bool enable_stft_rows() {
+  // The fused frame routes of the STFT, MDCT and spectrogram handles (stft_rows_kernel, mdct_rows_kernel, spectrogram_rows_kernel;
+  // stft_plan.h, mdct_plan.h, spectrogram_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
+  // is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
+  template <typename Args> bool enable_frame_rows() {
     if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
-    if (stft_rows_.fn) return true;
-    const StftRowsKernel k = get_stft_rows_kernel(Real<T>{}, passes_[0]->k.L);
-    if (!k.fn || k.L != passes_[0]->k.L) return false;
-    raise_smem_limit((const void*)k.fn, k.smem);
-    stft_rows_ = k;
+    FrameRowsKernel<Args>& slot = std::get<FrameRowsKernel<Args>>(frame_rows_);
+    if (slot.L) return true;
+    FrameRowsKernel<Args> k;
+    get_frame_rows_kernel(Real<T>{}, passes_[0]->k.L, k);
+    if (k.L != passes_[0]->k.L) return false;
+    for (auto fn : k.fn)
+      if (fn) raise_smem_limit((const void*)fn, k.smem);
+    slot = k;
     return true;
   }
-  // a: everything but the stage tables; a.total frames, below 2^31 workgroups (the caller bounds a launch)
-  void run_stft_rows(StftArgs a, hipStream_t stream) const {
-    if (a.total == 0) return;
-    const Pass& ps = *passes_[0];
-    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st->tw2.p;
-    launch(nullptr, 0, stft_rows_.fn, (a.total + stft_rows_.COLS - 1) / stft_rows_.COLS, stft_rows_.NT, stft_rows_.smem, stream, a);
-  }
-
-  // The fused frame route of the MDCT handle (mdct_rows_kernel; mdct_plan.h), under the same condition: this plan, of h = n / 2 points,
-  // is ONE whole-row pass and kernels_mdct.cpp holds the kernel on that pass's tile shape.
-  bool enable_mdct_rows() {
-    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
-    if (mdct_rows_.fn) return true;
-    const MdctRowsKernel k = get_mdct_rows_kernel(Real<T>{}, passes_[0]->k.L);
-    if (!k.fn || k.L != passes_[0]->k.L) return false;
-    raise_smem_limit((const void*)k.fn, k.smem);
-    mdct_rows_ = k;
-    return true;
-  }
-  void run_mdct_rows(MdctArgs a, hipStream_t stream) const {
-    if (a.total == 0) return;
-    const Pass& ps = *passes_[0];
-    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st->tw2.p;
-    launch(nullptr, 0, mdct_rows_.fn, (a.total + mdct_rows_.COLS - 1) / mdct_rows_.COLS, mdct_rows_.NT, mdct_rows_.smem, stream, a);
-  }
-
-  // The fused frame route of the spectrogram handle (spectrogram_rows_kernel; spectrogram_plan.h), under the same condition as the STFT's:
-  // this plan, of h = n_fft / 2 points, is ONE whole-row pass and kernels_spectrogram.cpp holds the kernels on that pass's tile shape.
-  bool enable_spectrogram_rows() {
-    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
-    if (spec_rows_.fn[SPEC_POWER]) return true;
-    const SpectrogramRowsKernel k = get_spectrogram_rows_kernel(Real<T>{}, passes_[0]->k.L);
-    if (!k.fn[SPEC_POWER] || k.L != passes_[0]->k.L) return false;
-    for (int out = SPEC_MAGNITUDE; out <= SPEC_PARTIAL; ++out) raise_smem_limit((const void*)k.fn[out], k.smem);
-    spec_rows_ = k;
-    return true;
-  }
-  int spectrogram_cols() const { return spec_rows_.COLS; }
-  // a: everything but the stage tables; `groups` workgroups of COLS frames each, below 2^31 (the caller bounds a launch)
-  void run_spectrogram_rows(SpectrogramArgs a, int out, uint64_t groups, hipStream_t stream) const {
+  // frames per workgroup of that route
+  template <typename Args> int frame_rows_cols() const { return std::get<FrameRowsKernel<Args>>(frame_rows_).COLS; }
+  // a: everything but the stage tables; kernel fn[which] on `groups` workgroups of COLS frames each, 0: those that cover the block's
+  // `total` frames; below 2^31 (the caller bounds a launch)
+  template <typename Args> void run_frame_rows(Args a, int which, uint64_t groups, hipStream_t stream) const {
+    const FrameRowsKernel<Args>& k = std::get<FrameRowsKernel<Args>>(frame_rows_);
+    auto& f = frame_block(a);
+    if (groups == 0) groups = (f.total + k.COLS - 1) / k.COLS;
     if (groups == 0) return;
     const Pass& ps = *passes_[0];
-    a.f.tw1 = ps.st->tw1.p; a.f.tw2 = ps.st->tw2.p;
-    launch(nullptr, 0, spec_rows_.fn[out], groups, spec_rows_.NT, spec_rows_.smem, stream, a);
+    f.tw1 = ps.st->tw1.p; f.tw2 = ps.st->tw2.p;
+    launch(nullptr, 0, k.fn[which], groups, k.NT, k.smem, stream, a);
   }
 
   // ---- XCD-fused two-pass plan (fft_l2fused_kernel): opt-in via the plan option "l2_fused"
@@ -716,9 +688,7 @@ template <typename T> class Pow2Engine {
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   StageTables<T>* conv_st_ = nullptr;
-  StftRowsKernel stft_rows_;
-  MdctRowsKernel mdct_rows_;
-  SpectrogramRowsKernel spec_rows_;
+  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel> frame_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -25,28 +25,11 @@ MdctKernel get_mdct_kernel(Real<TUReal>, int which) {
 }
 
 template <typename T, int L, int CG> static MdctRowsKernel make_mdct_rows() {
-  using C = TileCfg<T, L, CG>;
-  MdctRowsKernel k;
-  k.fn = &mdct_rows_kernel<T, L, CG>;
-  k.L = L; k.CG = CG; k.NT = C::NT; k.COLS = C::COLS;
-  k.smem = MdctRowsCfg<T, L, CG>::SMEM;
+  MdctRowsKernel k = frame_rows_shape<MdctRowsKernel, T, L, CG>();
+  k.fn[0] = &mdct_rows_kernel<T, L, CG>;
   return k;
 }
 
-// h = L: the tile width of the whole-row kernel of that length (get_kernel, MODE_ROWS); f64 h = 1024 is a one-launch 32 x 32 plan and
-// has no row kernel
-MdctRowsKernel get_mdct_rows_kernel(Real<TUReal>, int L) {
-  typedef TUReal T;
-  switch (L) {
-    case 64: return make_mdct_rows<T, 64, 16>();
-    case 128: return make_mdct_rows<T, 128, FOURIER_CG_128_ROWS>();
-    case 256: return make_mdct_rows<T, 256, 16>();
-    case 512: return make_mdct_rows<T, 512, FOURIER_CG_512>();
-    case 1024:
-      if constexpr (sizeof(T) == 4) return make_mdct_rows<T, 1024, 4>();
-      return MdctRowsKernel();
-    default: return MdctRowsKernel();
-  }
-}
+MdctRowsKernel get_mdct_rows_kernel(Real<TUReal>, int L) { FOURIER_FRAME_ROWS_TABLE(TUReal, L, make_mdct_rows) }
 
 }  // namespace fourier_hip

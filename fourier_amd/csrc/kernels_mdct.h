@@ -17,8 +17,7 @@
 //                       four window values it needs, the row core runs, the post-twiddled outputs go through LDS (even coefficients
 //                       ascending, odd ones descending) so that every store instruction writes one contiguous run of the frame.
 #pragma once
-#include "kernels_pass.h"
-#include "kernels_real.h"
+#include "kernels_frames.h"
 
 FOURIER_KERNELS_BEGIN
 
@@ -50,7 +49,8 @@ __device__ __forceinline__ cpx<T> mdct_fold(const T* row, const T* win, int64_t 
 
 // the frame of item i = blockIdx.x: its row and its first index in the padded row
 template <typename T> __device__ __forceinline__ const T* mdct_frame(const MdctArgs& a, uint32_t i, int64_t& t0) {
-  const uint32_t x = a.first + i, row = real_div(x, a.fr_m, a.fr_l), f = x - row * a.frames;
+  uint32_t row, f;
+  frame_of(a, i, row, f);
   t0 = (int64_t)f * a.n - (int64_t)a.pad;
   return (const T*)a.in + (uint64_t)row * a.length;
 }
@@ -176,29 +176,20 @@ __global__ void __launch_bounds__(MDCT_THREADS) imdct_odd_ola_kernel(MdctArgs a)
   }
 }
 
-// ---- the fused forward route
-template <typename T, int L, int CG> struct MdctRowsCfg {
-  using C = TileCfg<T, L, CG>;
-  static constexpr int HALF = C::COLS / 2;   // frames staged at a time: v = 0 / v = 1 (f32), cg below / above CG / 2 (f64)
-  static constexpr int LP = C::STAGE_LP;     // the staged frames' pitch in complex values: n = 2L reals and the pad
-  static constexpr size_t STAGE_BYTES = (size_t)HALF * LP * sizeof(cpx<T>);
-  static constexpr size_t SMEM = C::EXCH_BYTES > STAGE_BYTES ? C::EXCH_BYTES : STAGE_BYTES;
-};
-
+// ---- the fused forward route.  The staging area and the frame locator are the frame family's (kernels_frames.h); the half-tile staging
+// loop stays spelled out here: routed through a shared skeleton with put / get functors, the kernel's spills moved at every shape.
 // Four waves per SIMD asked for outright, as stft_rows_kernel does and for its reason: the fold's address arithmetic sits on top of the row
 // core ("Modified discrete cosine transform", lists the registers and spills of every instantiation).
 template <typename T, int L, int CG>
 __global__ void __launch_bounds__((L / 16) * CG, 4) mdct_rows_kernel(MdctArgs a) {
   using C = TileCfg<T, L, CG>;
-  using S = MdctRowsCfg<T, L, CG>;
-  constexpr int VEC = C::VEC, Q = C::Q, COLS = C::COLS, HALF = S::HALF, LP = S::LP;
+  constexpr int VEC = C::VEC, Q = C::Q, COLS = C::COLS, HALF = FrameRowsCfg<T, L, CG>::HALF, LP = FrameRowsCfg<T, L, CG>::LP;
   static_assert(Q > 1 && COLS % 2 == 0, "mdct rows kernel: L >= 32, an even number of frames per tile");
   FOURIER_DYN_SMEM(smem);
   const int tid = (int)threadIdx.x;
   int th = tid % Q, cg = tid / Q;
   // every XCD walks one contiguous range of the flat frame index: the two frames that read a sample meet in one L2
-  const uint32_t blk = real_xcd_block(blockIdx.x, gridDim.x);
-  const uint64_t g0 = (uint64_t)blk * COLS;
+  const uint64_t g0 = (uint64_t)real_xcd_block(blockIdx.x, gridDim.x) * COLS;
   const T* __restrict__ in = (const T*)a.in;
   const T* __restrict__ win = (const T*)a.win;
   const cpx<T>* __restrict__ A = (const cpx<T>*)a.twa + th;
@@ -216,7 +207,8 @@ __global__ void __launch_bounds__((L / 16) * CG, 4) mdct_rows_kernel(MdctArgs a)
       for (int r = 0; r < 16; ++r) x[v][r] = cpx<T>{0, 0};
       continue;
     }
-    const uint32_t xf = a.first + (uint32_t)g, row = real_div(xf, a.fr_m, a.fr_l), f = xf - row * a.frames;
+    uint32_t row, f;
+    frame_of(a, (uint32_t)g, row, f);
     const T* src = in + (uint64_t)row * a.length;
     const int64_t t0 = (int64_t)f * (2 * L) - (int64_t)a.pad;
     if (t0 >= 0 && t0 + 4 * L <= length) {

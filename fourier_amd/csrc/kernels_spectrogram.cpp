@@ -21,30 +21,13 @@ SpectrogramKernel get_spectrogram_kernel(Real<TUReal>, int which) {
 }
 
 template <typename T, int L, int CG> static SpectrogramRowsKernel make_spectrogram_rows() {
-  using C = TileCfg<T, L, CG>;
-  SpectrogramRowsKernel k;
+  SpectrogramRowsKernel k = frame_rows_shape<SpectrogramRowsKernel, T, L, CG>();
   k.fn[SPEC_MAGNITUDE] = &spectrogram_rows_kernel<T, L, CG, SPEC_MAGNITUDE>;
   k.fn[SPEC_POWER] = &spectrogram_rows_kernel<T, L, CG, SPEC_POWER>;
   k.fn[SPEC_PARTIAL] = &spectrogram_rows_kernel<T, L, CG, SPEC_PARTIAL>;
-  k.L = L; k.CG = CG; k.NT = C::NT; k.COLS = C::COLS;
-  k.smem = StftRowsCfg<T, L, CG>::SMEM;
   return k;
 }
 
-// h = L: the tile width of the whole-row kernel of that length (get_kernel, MODE_ROWS); f64 h = 1024 is a one-launch 32 x 32 plan and
-// has no row kernel
-SpectrogramRowsKernel get_spectrogram_rows_kernel(Real<TUReal>, int L) {
-  typedef TUReal T;
-  switch (L) {
-    case 64: return make_spectrogram_rows<T, 64, 16>();
-    case 128: return make_spectrogram_rows<T, 128, FOURIER_CG_128_ROWS>();
-    case 256: return make_spectrogram_rows<T, 256, 16>();
-    case 512: return make_spectrogram_rows<T, 512, FOURIER_CG_512>();
-    case 1024:
-      if constexpr (sizeof(T) == 4) return make_spectrogram_rows<T, 1024, 4>();
-      return SpectrogramRowsKernel();
-    default: return SpectrogramRowsKernel();
-  }
-}
+SpectrogramRowsKernel get_spectrogram_rows_kernel(Real<TUReal>, int L) { FOURIER_FRAME_ROWS_TABLE(TUReal, L, make_spectrogram_rows) }
 
 }  // namespace fourier_hip

@@ -70,11 +70,11 @@ __global__ void __launch_bounds__(STFT_THREADS) welch_reduce_kernel(SpectrogramA
   }
 }
 
-// ---- the fused route.  The occupancy request and the staging area are stft_rows_kernel's (StftRowsCfg).
+// ---- the fused route.  The occupancy request and the staging area are stft_rows_kernel's (FrameRowsCfg).
 template <typename T, int L, int CG, int OUT>
 __global__ void __launch_bounds__((L / 16) * CG, 4) spectrogram_rows_kernel(SpectrogramArgs a) {
   using C = TileCfg<T, L, CG>;
-  using S = StftRowsCfg<T, L, CG>;
+  using S = FrameRowsCfg<T, L, CG>;
   constexpr int VEC = C::VEC, Q = C::Q, COLS = C::COLS, HALF = S::HALF, LP = S::LP, NT = C::NT;
   constexpr int PS = L + 1;  // the reals of one frame's powers in LDS: an odd row pitch, neighbouring frames on neighbouring banks
   static_assert(Q > 1 && COLS % 2 == 0, "spectrogram rows kernel: L >= 32, an even number of frames per tile");
@@ -104,9 +104,7 @@ __global__ void __launch_bounds__((L / 16) * CG, 4) spectrogram_rows_kernel(Spec
     } else {
       const uint64_t g = g0 + (uint64_t)(cg * VEC + v);
       live[v] = g < a.f.total;
-      const uint32_t xf = a.f.first + (uint32_t)g;
-      row = real_div(xf, a.f.fr_m, a.f.fr_l);
-      f = xf - row * a.f.frames;
+      frame_of(a.f, (uint32_t)g, row, f);
     }
     if (!live[v]) {
 #pragma unroll

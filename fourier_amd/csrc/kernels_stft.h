@@ -13,8 +13,7 @@
 //                       kernels_real.h).  One launch, no scratch: a frame's samples are read hop-strided from the rows (the overlap of
 //                       neighbouring frames comes from the L2: consecutive frames stay on one XCD), the h + 1 bins are written once.
 #pragma once
-#include "kernels_pass.h"
-#include "kernels_real.h"
+#include "kernels_frames.h"
 
 FOURIER_KERNELS_BEGIN
 
@@ -34,7 +33,8 @@ template <typename T> __device__ __forceinline__ T stft_sample(const T* row, int
 template <typename T>
 __global__ void __launch_bounds__(STFT_THREADS) stft_frame_kernel(StftArgs a) {
   const uint32_t i = blockIdx.x;
-  const uint32_t x = a.first + i, row = real_div(x, a.fr_m, a.fr_l), f = x - row * a.frames;
+  uint32_t row, f;
+  frame_of(a, i, row, f);
   const T* src = (const T*)a.in + (uint64_t)row * a.length;
   const T* win = (const T*)a.win;
   T* dst = (T*)a.out + (uint64_t)i * a.n_fft;
@@ -63,21 +63,13 @@ __global__ void __launch_bounds__(STFT_THREADS) istft_ola_kernel(StftArgs a) {
 }
 
 // ---- the fused forward route
-template <typename T, int L, int CG> struct StftRowsCfg {
-  using C = TileCfg<T, L, CG>;
-  static constexpr int HALF = C::COLS / 2;   // frames staged at a time: v = 0 / v = 1 (f32), cg below / above CG / 2 (f64)
-  static constexpr int LP = C::STAGE_LP;     // the staged rows' pad
-  static constexpr size_t STAGE_BYTES = (size_t)HALF * LP * sizeof(cpx<T>);
-  static constexpr size_t SMEM = C::EXCH_BYTES > STAGE_BYTES ? C::EXCH_BYTES : STAGE_BYTES;
-};
-
 // Four waves per SIMD asked for outright: the gather's address arithmetic on top of the row core otherwise takes a few registers more than
 // 128 at f32 h = 512 and f64 h = 64, 256, 512, and with them a wave of the occupancy the row kernels of the same length have; the price
 // is 2 ... 16 spilled registers at those four shapes ("Short-time Fourier transform").
 template <typename T, int L, int CG>
 __global__ void __launch_bounds__((L / 16) * CG, 4) stft_rows_kernel(StftArgs a) {
   using C = TileCfg<T, L, CG>;
-  using S = StftRowsCfg<T, L, CG>;
+  using S = FrameRowsCfg<T, L, CG>;
   constexpr int VEC = C::VEC, Q = C::Q, COLS = C::COLS, HALF = S::HALF, LP = S::LP;
   static_assert(Q > 1 && COLS % 2 == 0, "stft rows kernel: L >= 32, an even number of frames per tile");
   FOURIER_DYN_SMEM(smem);
@@ -100,7 +92,8 @@ __global__ void __launch_bounds__((L / 16) * CG, 4) stft_rows_kernel(StftArgs a)
       for (int r = 0; r < 16; ++r) x[v][r] = cpx<T>{0, 0};
       continue;
     }
-    const uint32_t xf = a.first + (uint32_t)g, row = real_div(xf, a.fr_m, a.fr_l), f = xf - row * a.frames;
+    uint32_t row, f;
+    frame_of(a, (uint32_t)g, row, f);
     const T* src = in + (uint64_t)row * a.length;
     const int64_t t0 = (int64_t)f * a.hop - (int64_t)a.pad;
     if (t0 >= 0 && t0 + (int64_t)a.n_fft <= length) {

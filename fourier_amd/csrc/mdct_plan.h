@@ -6,7 +6,7 @@
 //                       one half of the scratch, the h-point plan takes them into the other half, mdct_post_kernel writes the caller's
 //                       output.
 //   "mdct fused rows"   n = 2h with a whole-row h-point kernel: mdct_rows_kernel in one launch, no scratch.  The default only where
-//                       fused_default() says it measured faster (nowhere yet); option "fusion" = 0 forces the composed route, 1 takes
+//                       the constructor records a faster measurement (nowhere yet); option "fusion" = 0 forces the composed route, 1 takes
 //                       the fused one wherever its kernel exists.
 //   "mdct full-length"  odd n, the correctness path: the 2n-point plan in place on the windowed frame times exp(-i pi m / 2n).
 //   inverse             "imdct composed" (even n) / "imdct full-length" (odd n): a pre sweep, the inner plan, and the overlap-add as a
@@ -14,6 +14,7 @@
 //                       scratch bound, else ranges of output samples of one row; the frame two neighbouring ranges both need is
 //                       transformed twice.  A range needs both frames that cover a sample, so the scratch never holds fewer than two.
 #pragma once
+#include "frame_plan_common.h"
 #include "real_plan.h"
 
 namespace fourier_hip {
@@ -39,8 +40,11 @@ template <typename T> class MdctPlan : public HandleBase {
     twa_.upload(ta);
     twb_.upload(tb);
     load_window(nullptr);
-    have_fused_ = even_ && inner_->enable_mdct();
-    fused_ = have_fused_ && fused_default();
+    // Where the fused route is the default.  The rule: only for a (precision, n) where it measured faster than the composed route by
+    // more than the composed arm's spread (tools/mdct_bench.py).  No such measurement exists yet ("Modified discrete
+    // cosine transform"), so the composed route is the default everywhere and option "fusion" = 1 takes the fused one.
+    // FOURIER_MDCT_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
+    fusion_.init(even_ && inner_->template enable_frames<MdctArgs>(), "FOURIER_MDCT_FUSION", false);
     refresh_desc();
   }
 
@@ -55,12 +59,9 @@ template <typename T> class MdctPlan : public HandleBase {
   }
 
   int set_option(const std::string& key, long long v) {
-    if (key == "fusion" && (v == 0 || v == 1)) {
-      fused_ = v == 1 && have_fused_;
-      refresh_desc();
-      return ::fourier::c::FOURIER_HIP_OK;
-    }
-    return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    if (!fusion_.set(key, v)) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    refresh_desc();
+    return ::fourier::c::FOURIER_HIP_OK;
   }
 
   // 2n reals T on the device, or nullptr for the sine window.  A set-up call: it waits for `stream` (the table is replaced in place).
@@ -79,10 +80,8 @@ template <typename T> class MdctPlan : public HandleBase {
     if (fr == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "invalid length");
     if (batch == 0) return;
     DeviceGuard g(device_);
-    if (!fused_) (void)prepare_forward(batch * fr);
-    size_t rows_per, nfr;
-    inverse_chunks(fr, batch, rows_per, nfr);
-    prepare(rows_per * nfr);
+    if (!fusion_.on) (void)prepare_forward(batch * fr);
+    prepare(inverse_chunks(fr, batch).frames());
   }
 
   void forward(const void* d_in, void* d_out, size_t length, size_t batch, bool normalized, hipStream_t stream) const {
@@ -97,18 +96,12 @@ template <typename T> class MdctPlan : public HandleBase {
     MdctArgs a = base_args(length, fr);
     divider(a.frames, a.fr_m, a.fr_l);
     a.scale = normalized ? std::sqrt(2.0 / (double)n_) : 1.0;
-    auto at = [&](size_t g0, size_t ng) {  // the launch's row base and first frame
-      const size_t row0 = g0 / fr;
-      a.in = in + row0 * length;
-      a.first = (uint32_t)(g0 - row0 * fr);
-      a.total = ng;
-    };
-    if (fused_) {
+    if (fusion_.on) {
       a.pairs = (uintptr_t)out % ELEM == 0;
       for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
-        at(g0, ng);
+        frame_launch_at(a, in, length, fr, g0, ng);
         a.out = out + g0 * n_;
-        inner_->exec_mdct(a, stream);
+        inner_->exec_frames(a, stream);
       });
       return;
     }
@@ -116,7 +109,7 @@ template <typename T> class MdctPlan : public HandleBase {
     cpx<T>* wa = (cpx<T>*)scratch_.p;
     const int code = ::fourier::c::FOURIER_TRANSFORM_FFT;
     for_chunks(total, chunk, [&](size_t g0, size_t ng) {
-      at(g0, ng);
+      frame_launch_at(a, in, length, fr, g0, ng);
       a.out = wa;
       if (even_) {
         cpx<T>* wb = wa + chunk * h_;
@@ -142,16 +135,15 @@ template <typename T> class MdctPlan : public HandleBase {
     DeviceGuard g(device_);
     const T* in = (const T*)d_in;
     T* out = (T*)d_out;
-    size_t rows_per, nfr_max;
-    inverse_chunks(fr, batch, rows_per, nfr_max);
-    const size_t cap_frames = rows_per * nfr_max;
+    const FrameInverseChunks chunks = inverse_chunks(fr, batch);
+    const size_t cap_frames = chunks.frames();
     prepare(cap_frames);
     cpx<T>* wa = (cpx<T>*)scratch_.p;
     cpx<T>* wb = even_ ? wa + cap_frames * h_ : wa;
     MdctArgs a = base_args(length, fr);
     const double scale = normalized ? std::sqrt(2.0 / (double)n_) : 2.0 / (double)n_;
     const int code = ::fourier::c::FOURIER_TRANSFORM_FFT;
-    auto ola = [&](size_t b0, size_t nb, size_t t0, size_t span, size_t f_lo, size_t nfr) {
+    frame_inverse_walk(overlap(), chunks, fr, batch, length, [&](size_t b0, size_t nb, size_t t0, size_t span, size_t f_lo, size_t nfr) {
       const size_t count = nb == 1 ? nfr : nb * fr;
       a.in = in + (b0 * fr + f_lo) * n_;
       a.out = wa;
@@ -164,33 +156,12 @@ template <typename T> class MdctPlan : public HandleBase {
       a.total = nb * span;
       a.scale = scale;
       FOURIER_LAUNCH(get_mdct_kernel(Real<T>{}, even_ ? IMDCT_OLA : IMDCT_ODD_OLA), elementwise_grid(a.total), 256, 0, stream, a);
-    };
-    if (nfr_max == fr) {  // whole rows
-      for_chunks(batch, rows_per, [&](size_t b0, size_t nb) { ola(b0, nb, 0, length, 0, fr); });
-      return;
-    }
-    for (size_t b = 0; b < batch; ++b)
-      for (size_t t0 = 0; t0 < length;) {
-        const size_t q = (t0 + pad_) / n_;
-        const size_t f_lo = std::min(q >= 2 ? q - 1 : 0, fr - 1);
-        const size_t nfr = std::min(nfr_max, fr - f_lo);
-        const size_t t1 = f_lo + nfr >= fr ? length : std::min(length, (f_lo + nfr) * n_ - pad_);
-        ola(b, 1, t0, t1 - t0, f_lo, nfr);
-        t0 = t1;
-      }
+    });
   }
 
  private:
-  // Where the fused route is the default.  The rule: only for a (precision, n) where it measured faster than the composed route by more
-  // than the composed arm's spread (tools/mdct_bench.py).  No such measurement exists yet ("Modified discrete
-  // cosine transform"), so the composed route is the default everywhere and option "fusion" = 1 takes the fused one.
-  // FOURIER_MDCT_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
-  bool fused_default() const {
-    if (const char* e = dev_env("FOURIER_MDCT_FUSION")) return atoi(e) != 0;
-    return false;
-  }
   void refresh_desc() {
-    desc_ = std::string(!even_ ? "mdct full-length, imdct full-length: " : fused_ ? "mdct fused rows, imdct composed: " : "mdct composed, imdct composed: ") +
+    desc_ = std::string(!even_ ? "mdct full-length, imdct full-length: " : fusion_.on ? "mdct fused rows, imdct composed: " : "mdct composed, imdct composed: ") +
             inner_->describe();
   }
   MdctArgs base_args(size_t length, size_t fr) const {
@@ -227,13 +198,11 @@ template <typename T> class MdctPlan : public HandleBase {
     prepare(chunk);
     return chunk;
   }
-  // rows per chunk and frames of a row per chunk: whole rows where a row's frames fit the bound, else ranges of one row over at least
-  // the two frames that cover one sample
-  void inverse_chunks(size_t fr, size_t batch, size_t& rows_per, size_t& nfr) const {
-    const size_t fit = std::min(scratch_cap_ / frame_bytes(), LAUNCH_ITEMS);
-    if (fit >= fr) { rows_per = std::min(batch, fit / fr); nfr = fr; return; }
-    rows_per = 1;
-    nfr = std::min(fr, std::max<size_t>(fit, 2));
+  // the inverse's framing -- 2n samples a frame, two frames cover a sample -- and its chunks under the scratch bound (reserve() and
+  // inverse() size from the same function)
+  FrameOverlap overlap() const { return {2 * n_, n_, pad_}; }
+  FrameInverseChunks inverse_chunks(size_t fr, size_t batch) const {
+    return frame_inverse_chunks(overlap(), fr, batch, std::min(scratch_cap_ / frame_bytes(), LAUNCH_ITEMS));
   }
 
   size_t n_, h_;
@@ -241,7 +210,7 @@ template <typename T> class MdctPlan : public HandleBase {
   size_t pad_;
   int device_ = 0;
   std::unique_ptr<Plan<T>> inner_;
-  bool have_fused_ = false, fused_ = false;
+  FusionSwitch fusion_;
   DevBuf win_, twa_, twb_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;

@@ -585,41 +585,19 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_lconv_small(d_in, d_out, rows, bank, (uint32_t)filters, (uint32_t)(first % filters), real_data, geo, stream, nxcd_);
   }
 
-  // ---- the hook of the STFT handle (StftPlan, stft_plan.h); exec() is not affected.  A plan of h points that is one whole-row pass runs
-  // the frames of n_fft = 2h samples in one launch of stft_rows_kernel (gather, window, transform, untangle).
-  bool enable_stft() {
+  // ---- the hooks of the frame handles (StftPlan, MdctPlan, SpectrogramPlan), selected by the kernels' argument block (StftArgs,
+  // MdctArgs, SpectrogramArgs); exec() is not affected.  A plan of h points that is one whole-row pass runs the frames of n = 2h samples in
+  // one launch of the family's rows kernel (kernels_frames.h): fn[which] on `groups` workgroups of frame_cols() frames, 0: those that
+  // cover the `total` frames of the block.
+  template <typename Args> bool enable_frames() {
     if (blu_ || !eng_) return false;
     DeviceGuard g(device_);
-    return eng_->enable_stft_rows();
+    return eng_->template enable_frame_rows<Args>();
   }
-  void exec_stft(const StftArgs& a, hipStream_t stream) const {
+  template <typename Args> int frame_cols() const { return eng_->template frame_rows_cols<Args>(); }
+  template <typename Args> void exec_frames(const Args& a, hipStream_t stream, int which = 0, uint64_t groups = 0) const {
     DeviceGuard g(device_);
-    eng_->run_stft_rows(a, stream);
-  }
-
-  // ---- the hook of the MDCT handle (MdctPlan, mdct_plan.h), as the STFT's: a plan of h points that is one whole-row pass runs the frames
-  // of n = 2h coefficients in one launch of mdct_rows_kernel (fold, pre-twiddle, transform, post-twiddle).
-  bool enable_mdct() {
-    if (blu_ || !eng_) return false;
-    DeviceGuard g(device_);
-    return eng_->enable_mdct_rows();
-  }
-  void exec_mdct(const MdctArgs& a, hipStream_t stream) const {
-    DeviceGuard g(device_);
-    eng_->run_mdct_rows(a, stream);
-  }
-
-  // ---- the hook of the spectrogram handle (SpectrogramPlan, spectrogram_plan.h), as the STFT's: the frames of n_fft = 2h samples in one
-  // launch of spectrogram_rows_kernel, `out` = SPEC_MAGNITUDE / SPEC_POWER / SPEC_PARTIAL, `groups` workgroups of spectrogram_cols() frames.
-  bool enable_spectrogram() {
-    if (blu_ || !eng_) return false;
-    DeviceGuard g(device_);
-    return eng_->enable_spectrogram_rows();
-  }
-  int spectrogram_cols() const { return eng_->spectrogram_cols(); }
-  void exec_spectrogram(const SpectrogramArgs& a, int out, uint64_t groups, hipStream_t stream) const {
-    DeviceGuard g(device_);
-    eng_->run_spectrogram_rows(a, out, groups, stream);
+    eng_->run_frame_rows(a, which, groups, stream);
   }
 
   // Wait for everything queued on `stream` of the plan's device (the blocking half of a stream-ordered batched call).

@@ -41,10 +41,9 @@ template <typename T> class RealPlan : public HandleBase {
   bool even() const { return even_; }
   const Plan<T>& inner() const { return *inner_; }
   const void* twiddles() const { return tw_.p; }
-  // the STFT handle's fused frame route (stft_plan.h): even N whose inner plan is one whole-row pass with a kernel for it
-  bool enable_stft() { return even_ && inner_->enable_stft(); }
-  // the spectrogram handle's fused frame route (spectrogram_plan.h), under the same condition
-  bool enable_spectrogram() { return even_ && inner_->enable_spectrogram(); }
+  // the fused frame route of the STFT / spectrogram handle (Args = StftArgs / SpectrogramArgs; stft_plan.h, spectrogram_plan.h): even N
+  // whose inner plan is one whole-row pass with a kernel for it
+  template <typename Args> bool enable_frames() { return even_ && inner_->template enable_frames<Args>(); }
 
   // rows per chunk for a call of `batch` rows; sizes the scratch and the inner plan's buffers for it (reserve: ahead of time, so
   // that later calls of at most `batch` rows never allocate)

@@ -9,7 +9,7 @@
 //                      windows into the scratch, RealPlan::run_forward transforms into a second region of it, then
 //                      spectrogram_power_kernel writes |.|^p to the output, or welch_colsum_kernel adds the chunk's |.|^2 to the slots
 //                      (WELCH_TILE frames of one row each) it meets, and welch_reduce_kernel finishes.  Chunks may end inside a row.
-// The default is the composed route until the fused one is measured (fused_default()); option "fusion" = 1 takes the fused route
+// The default is the composed route until the fused one is measured (the constructor); option "fusion" = 1 takes the fused route
 // wherever it exists, 0 the composed one.
 // Scratch: the frames of a chunk take n_fft reals + bins complex each, at most the bound of FOURIER_REAL_SCRATCH_BYTES and never less than
 // one frame; the partials are a buffer of their own under the same bound, never less than one row's, the rows walked in groups that fit.
@@ -30,8 +30,11 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     device_ = stft_->real().inner().device();
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
-    have_fused_ = stft_->enable_spectrogram();
-    fused_ = have_fused_ && fused_default();
+    // Where the fused route is the default: nowhere yet.  The project's rule is that a default follows a measurement (the STFT's fused
+    // route became one after tools/stft_bench.py), and tools/spectrogram_bench.py has not run on an MI355X -- DESIGN.md section 4, "Power
+    // spectrogram and Welch average".  Option "fusion" = 1 selects the fused kernels wherever they exist.
+    // FOURIER_SPECTROGRAM_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
+    fusion_.init(stft_->enable_spectrogram(), "FOURIER_SPECTROGRAM_FUSION", false);
     refresh_desc();
   }
 
@@ -42,12 +45,9 @@ template <typename T> class SpectrogramPlan : public HandleBase {
   size_t frames(size_t length) const { return stft_->frames(length); }
 
   int set_option(const std::string& key, long long v) {
-    if (key == "fusion" && (v == 0 || v == 1)) {
-      fused_ = v == 1 && have_fused_;
-      refresh_desc();
-      return ::fourier::c::FOURIER_HIP_OK;
-    }
-    return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    if (!fusion_.set(key, v)) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    refresh_desc();
+    return ::fourier::c::FOURIER_HIP_OK;
   }
 
   // the STFT handle's set-up call: win_length reals T on the device, or nullptr for all ones; waits for `stream`
@@ -59,7 +59,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     if (fr == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "invalid length");
     if (batch == 0) return;
     DeviceGuard g(device_);
-    if (!fused_) (void)prepare_frames(batch * fr);
+    if (!fusion_.on) (void)prepare_frames(batch * fr);
     (void)prepare_partials(fr, batch);
   }
 
@@ -76,22 +76,14 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     const T* in = (const T*)d_in;
     T* out = (T*)d_out;
     SpectrogramArgs a{};
-    a.f = stft_->frame_args(length, fr);
+    a.f = fusion_.on ? stft_->fused_args(length, fr, normalized) : stft_->frame_args(length, fr);
     a.bins = (uint32_t)bins;
     a.power = (uint32_t)power;
-    if (fused_) {
-      const Plan<T>& inner = stft_->real().inner();
-      const size_t cols = (size_t)inner.spectrogram_cols();
-      a.f.tw = stft_->real().twiddles();
-      a.f.scale = normalized ? code_scale<T>(::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT, (T)n_fft()) : 1.0;
+    if (fusion_.on) {
       for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
-        const size_t row0 = g0 / fr;
-        a.f.in = in + row0 * length;
+        stft_->fused_launch_at(a.f, in, length, fr, g0, ng);
         a.f.out = out + g0 * bins;
-        a.f.first = (uint32_t)(g0 - row0 * fr);
-        a.f.total = ng;
-        a.f.pairs = pairs(a.f.in, length);
-        inner.exec_spectrogram(a, power, (ng + cols - 1) / cols, stream);
+        stft_->real().inner().exec_frames(a, stream, power);
       });
       return;
     }
@@ -118,7 +110,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     const size_t tiles = tiles_of(fr);
     const size_t rows_per = prepare_partials(fr, batch);
     SpectrogramArgs a{};
-    a.f = stft_->frame_args(length, fr);
+    a.f = fusion_.on ? stft_->fused_args(length, fr, false) : stft_->frame_args(length, fr);
     a.bins = (uint32_t)bins;
     a.part = part_.p;
     a.tiles = (uint32_t)tiles;
@@ -126,13 +118,11 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     a.tile_frames = (uint32_t)WELCH_TILE;
     a.fold = fold ? 1 : 0;
     a.scale = scale / (double)fr;
-    const size_t chunk = fused_ ? 0 : prepare_frames(std::min(batch, rows_per) * fr);
-    if (fused_) a.f.tw = stft_->real().twiddles();
+    const size_t chunk = fusion_.on ? 0 : prepare_frames(std::min(batch, rows_per) * fr);
     for_chunks(batch, rows_per, [&](size_t b0, size_t nb) {
-      if (fused_) {
-        a.f.in = in + b0 * length;
-        a.f.pairs = pairs(a.f.in, length);
-        stft_->real().inner().exec_spectrogram(a, SPEC_PARTIAL, nb * tiles, stream);
+      if (fusion_.on) {
+        stft_->fused_launch_at(a.f, in + b0 * length, length, fr, 0, 0);  // (tiled per row: the kernel reads neither first nor total)
+        stft_->real().inner().exec_frames(a, stream, SPEC_PARTIAL, nb * tiles);
       } else {
         for_chunks(nb * fr, chunk, [&](size_t g0, size_t ng) {
           transform_chunk(a, in + b0 * length, length, fr, g0, ng, chunk, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
@@ -151,24 +141,12 @@ template <typename T> class SpectrogramPlan : public HandleBase {
   }
 
  private:
-  // Where the fused route is the default: nowhere yet.  The project's rule is that a default follows a measurement (the STFT's fused
-  // route became one after tools/stft_bench.py), and tools/spectrogram_bench.py has not run on an MI355X -- DESIGN.md section 4, "Power
-  // spectrogram and Welch average".  Option "fusion" = 1 selects the fused kernels wherever they exist.
-  // FOURIER_SPECTROGRAM_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
-  bool fused_default() const {
-    if (const char* e = dev_env("FOURIER_SPECTROGRAM_FUSION")) return atoi(e) != 0;
-    return false;
-  }
   void refresh_desc() {
-    desc_ = std::string(fused_ ? "spectrogram fused rows, welch fused rows: " : "spectrogram composed, welch composed: ") + stft_->real().describe();
-  }
-  // the fused load takes two reals per access where every interior frame starts on an even element of a 2 * sizeof(T)-aligned row
-  int pairs(const void* in, size_t length) const {
-    return hop() % 2 == 0 && stft_->pad() % 2 == 0 && length % 2 == 0 && (uintptr_t)in % (2 * sizeof(T)) == 0;
+    desc_ = std::string(fusion_.on ? "spectrogram fused rows, welch fused rows: " : "spectrogram composed, welch composed: ") + stft_->real().describe();
   }
   // partial slots per row: the fused kernel's tiles of COLS frames, the composed route's runs of WELCH_TILE frames
   size_t tiles_of(size_t fr) const {
-    const size_t per = fused_ ? (size_t)stft_->real().inner().spectrogram_cols() : WELCH_TILE;
+    const size_t per = fusion_.on ? (size_t)stft_->real().inner().template frame_cols<SpectrogramArgs>() : WELCH_TILE;
     return (fr + per - 1) / per;
   }
   // rows per group of a Welch call: their partials fit the bound (never less than one row's) and one launch's 32-bit indices
@@ -191,19 +169,16 @@ template <typename T> class SpectrogramPlan : public HandleBase {
   // frames g0 ... g0 + ng - 1 of the flat frame index counted from the row at `in`: gathered, windowed, transformed into spectra()
   void transform_chunk(SpectrogramArgs& a, const T* in, size_t length, size_t fr, size_t g0, size_t ng, size_t chunk, int code,
                        hipStream_t stream) const {
-    const size_t row0 = g0 / fr;
     StftArgs f = a.f;
-    f.in = in + row0 * length;
+    frame_launch_at(f, in, length, fr, g0, ng);
     f.out = gathered(chunk);
-    f.first = (uint32_t)(g0 - row0 * fr);
-    f.total = ng;
     FOURIER_LAUNCH(get_stft_kernel(Real<T>{}, STFT_FRAME), ng, 256, 0, stream, f);
     stft_->real().run_forward(gathered(chunk), spectra(chunk), ng, code, stream);
   }
 
   std::unique_ptr<StftPlan<T>> stft_;
   int device_ = 0;
-  bool have_fused_ = false, fused_ = false;
+  FusionSwitch fusion_;
   mutable DevBuf scratch_, part_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
 };

@@ -5,7 +5,7 @@
 //   "stft composed"    every n_fft: stft_frame_kernel gathers, pads and windows the frames of a chunk of the flat frame index into the
 //                      scratch (rows of n_fft reals), RealPlan::run_forward takes them straight into the caller's output.
 //   "stft fused rows"  n_fft = 2h with a whole-row h-point kernel: stft_rows_kernel in one launch, no scratch (kernels_stft.h).  The
-//                      default where fused_default() says it measured faster; option "fusion" = 0 forces the composed route, 1 takes the
+//                      default where the measurements at the constructor say so; option "fusion" = 0 forces the composed route, 1 takes the
 //                      fused one wherever its kernel exists.
 //   inverse            "istft composed" only: RealPlan::run_inverse (unscaled) takes the frames of a chunk into the scratch,
 //                      istft_ola_kernel gathers the overlap-add, times the reciprocal envelope 1 / sum_f w^2.  The envelope depends on
@@ -17,6 +17,7 @@
 #pragma once
 #include <map>
 
+#include "frame_plan_common.h"
 #include "real_plan.h"
 
 namespace fourier_hip {
@@ -42,8 +43,10 @@ template <typename T> class StftPlan : public HandleBase {
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     load_window(std::vector<T>(wl_, (T)1));
-    have_fused_ = real_->enable_stft();
-    fused_ = have_fused_ && fused_default();
+    // Where the fused route is the default: wherever its kernel exists.  Every (precision, n_fft) measured 0.31 - 0.42 of the composed
+    // route's time at hop = n_fft / 4 and n_fft / 2, against a spread of 1 - 4 % ("Short-time Fourier transform";
+    // profiles/stft/stft_bench.jsonl).  FOURIER_STFT_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
+    fusion_.init(real_->template enable_frames<StftArgs>(), "FOURIER_STFT_FUSION", true);
     refresh_desc();
   }
 
@@ -56,7 +59,7 @@ template <typename T> class StftPlan : public HandleBase {
   size_t pad() const { return pad_; }
   const void* window() const { return win_.p; }
   const RealPlan<T>& real() const { return *real_; }
-  bool enable_spectrogram() { return real_->enable_spectrogram(); }
+  bool enable_spectrogram() { return real_->template enable_frames<SpectrogramArgs>(); }
   // the argument block of a forward launch, all but in, out, first, total (and the fused route's tw, scale, pairs)
   StftArgs frame_args(size_t length, size_t fr) const {
     StftArgs a{};
@@ -67,6 +70,19 @@ template <typename T> class StftPlan : public HandleBase {
     a.scale = 1.0;
     return a;
   }
+  // ... of a fused launch (stft_rows_kernel, spectrogram_rows_kernel): with the untangle's table and the scale of the bins
+  StftArgs fused_args(size_t length, size_t fr, bool normalized) const {
+    StftArgs a = frame_args(length, fr);
+    a.tw = real_->twiddles();
+    a.scale = normalized ? code_scale<T>(::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT, (T)n_) : 1.0;
+    return a;
+  }
+  // ... and its row base: the fused load takes two reals per access where every interior frame starts on an even element of a
+  // 2 * sizeof(T)-aligned row
+  void fused_launch_at(StftArgs& a, const T* in, size_t length, size_t fr, size_t g0, size_t ng) const {
+    frame_launch_at(a, in, length, fr, g0, ng);
+    a.pairs = hop_ % 2 == 0 && pad_ % 2 == 0 && length % 2 == 0 && (uintptr_t)a.in % (2 * sizeof(T)) == 0;
+  }
   // frames of a row of `length` reals; 0 where the length is invalid
   size_t frames(size_t length) const {
     size_t f = 0;
@@ -76,12 +92,9 @@ template <typename T> class StftPlan : public HandleBase {
   }
 
   int set_option(const std::string& key, long long v) {
-    if (key == "fusion" && (v == 0 || v == 1)) {
-      fused_ = v == 1 && have_fused_;
-      refresh_desc();
-      return ::fourier::c::FOURIER_HIP_OK;
-    }
-    return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    if (!fusion_.set(key, v)) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+    refresh_desc();
+    return ::fourier::c::FOURIER_HIP_OK;
   }
 
   // win_length reals T on the device, or nullptr for all ones.  A set-up call: it waits for `stream` (the tables are replaced in place
@@ -101,10 +114,8 @@ template <typename T> class StftPlan : public HandleBase {
     if (fr == 0) throw EngineError(::fourier::c::FOURIER_HIP_INVALID_ARGUMENT, "invalid length");
     if (batch == 0) return;
     DeviceGuard g(device_);
-    if (!fused_) (void)prepare_forward(batch * fr);
-    size_t rows_per, nfr;
-    inverse_chunks(fr, batch, rows_per, nfr);
-    (void)prepare_inverse(rows_per * nfr);
+    if (!fusion_.on) (void)prepare_forward(batch * fr);
+    (void)prepare_inverse(inverse_chunks(fr, batch).frames());
     const size_t full = hop_ * (fr - 1) + n_ - 2 * pad_;
     if (length <= full) {
       try { (void)envelope(fr, length); } catch (const EngineError& e) { if (e.status != ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT) throw; }  // (a window without an inverse)
@@ -122,29 +133,21 @@ template <typename T> class StftPlan : public HandleBase {
     const size_t total = batch * fr;
     const T* in = (const T*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
-    StftArgs a = frame_args(length, fr);
-    if (fused_) {
-      a.tw = real_->twiddles();
-      a.scale = normalized ? code_scale<T>(::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT, (T)n_) : 1.0;
+    if (fusion_.on) {
+      StftArgs a = fused_args(length, fr, normalized);
       for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
-        const size_t row0 = g0 / fr;
-        a.in = in + row0 * length;
+        fused_launch_at(a, in, length, fr, g0, ng);
         a.out = out + g0 * bins_;
-        a.first = (uint32_t)(g0 - row0 * fr);
-        a.total = ng;
-        a.pairs = hop_ % 2 == 0 && pad_ % 2 == 0 && length % 2 == 0 && (uintptr_t)a.in % (2 * sizeof(T)) == 0;
-        real_->inner().exec_stft(a, stream);
+        real_->inner().exec_frames(a, stream);
       });
       return;
     }
+    StftArgs a = frame_args(length, fr);
     const size_t chunk = prepare_forward(total);
     const int code = normalized ? ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT : ::fourier::c::FOURIER_TRANSFORM_FFT;
     for_chunks(total, chunk, [&](size_t g0, size_t ng) {
-      const size_t row0 = g0 / fr;
-      a.in = in + row0 * length;
+      frame_launch_at(a, in, length, fr, g0, ng);
       a.out = scratch_.p;
-      a.first = (uint32_t)(g0 - row0 * fr);
-      a.total = ng;
       FOURIER_LAUNCH(get_stft_kernel(Real<T>{}, STFT_FRAME), ng, 256, 0, stream, a);
       real_->run_forward(scratch_.p, out + g0 * bins_, ng, code, stream);
     });
@@ -162,9 +165,8 @@ template <typename T> class StftPlan : public HandleBase {
     if (batch == 0) return;
     const cpx<T>* in = (const cpx<T>*)d_in;
     T* out = (T*)d_out;
-    size_t rows_per, nfr_max;
-    inverse_chunks(fr, batch, rows_per, nfr_max);
-    (void)prepare_inverse(rows_per * nfr_max);
+    const FrameInverseChunks chunks = inverse_chunks(fr, batch);
+    (void)prepare_inverse(chunks.frames());
     StftArgs a{};
     a.win = win_.p; a.env = env;
     a.length = length; a.frames = (uint32_t)fr;
@@ -172,38 +174,18 @@ template <typename T> class StftPlan : public HandleBase {
     a.scale = (normalized ? std::sqrt((double)n_) : 1.0) / (double)n_;  // the inner inverse runs unscaled
     a.in = scratch_.p;
     const int code = ::fourier::c::FOURIER_TRANSFORM_UNSCALED_IFFT;
-    auto ola = [&](size_t b0, size_t nb, size_t t0, size_t span, size_t f_lo, size_t nfr) {
+    frame_inverse_walk(overlap(), chunks, fr, batch, length, [&](size_t b0, size_t nb, size_t t0, size_t span, size_t f_lo, size_t nfr) {
       real_->run_inverse(in + (b0 * fr + f_lo) * bins_, scratch_.p, nb == 1 ? nfr : nb * fr, code, stream);
       a.out = out + b0 * length;
       a.t0 = t0; a.span = span; a.rows = nb; a.f_lo = f_lo; a.nfr = nfr;
       a.total = nb * span;
       FOURIER_LAUNCH(get_stft_kernel(Real<T>{}, STFT_OLA), elementwise_grid(a.total), 256, 0, stream, a);
-    };
-    if (nfr_max == fr) {  // whole rows
-      for_chunks(batch, rows_per, [&](size_t b0, size_t nb) { ola(b0, nb, 0, length, 0, fr); });
-      return;
-    }
-    for (size_t b = 0; b < batch; ++b)
-      for (size_t t0 = 0; t0 < length;) {
-        const size_t u0 = t0 + pad_;
-        const size_t f_lo = u0 >= n_ ? (u0 - n_) / hop_ + 1 : 0;
-        const size_t nfr = std::min(nfr_max, fr - f_lo);
-        const size_t t1 = f_lo + nfr >= fr ? length : std::min(length, (f_lo + nfr) * hop_ - pad_);
-        ola(b, 1, t0, t1 - t0, f_lo, nfr);
-        t0 = t1;
-      }
+    });
   }
 
  private:
-  // Where the fused route is the default: wherever its kernel exists.  Every (precision, n_fft) measured 0.31 - 0.42 of the composed route's
-  // time at hop = n_fft / 4 and n_fft / 2, against a spread of 1 - 4 % ("Short-time Fourier transform";
-  // profiles/stft/stft_bench.jsonl).  FOURIER_STFT_FUSION = 0 / 1 is the development switch of the experiments library and the emulator build.
-  bool fused_default() const {
-    if (const char* e = dev_env("FOURIER_STFT_FUSION")) return atoi(e) != 0;
-    return true;
-  }
   void refresh_desc() {
-    desc_ = std::string(fused_ ? "stft fused rows" : "stft composed") + ", istft composed: " + real_->describe();
+    desc_ = std::string(fusion_.on ? "stft fused rows" : "stft composed") + ", istft composed: " + real_->describe();
   }
   // the window centred in the frame, (n_fft - win_length) / 2 zeros in front: the device table in T, the host copy in f64
   void load_window(const std::vector<T>& w) {
@@ -226,13 +208,10 @@ template <typename T> class StftPlan : public HandleBase {
     real_->reserve(frames_in_scratch);
     return frames_in_scratch;
   }
-  // rows per chunk and frames of a row per chunk: whole rows where a row's frames fit the bound, else ranges of one row over at least
-  // the frames that cover one sample
-  void inverse_chunks(size_t fr, size_t batch, size_t& rows_per, size_t& nfr) const {
-    const size_t fit = scratch_cap_ / (n_ * sizeof(T));
-    if (fit >= fr) { rows_per = std::min(batch, fit / fr); nfr = fr; return; }
-    rows_per = 1;
-    nfr = std::min(fr, std::max(fit, (n_ + hop_ - 1) / hop_));
+  // the inverse's framing and its chunks under the scratch bound (reserve() and inverse() size from the same function)
+  FrameOverlap overlap() const { return {n_, hop_, pad_}; }
+  FrameInverseChunks inverse_chunks(size_t fr, size_t batch) const {
+    return frame_inverse_chunks(overlap(), fr, batch, scratch_cap_ / (n_ * sizeof(T)));
   }
   // 1 / sum_f w[t + p - f hop]^2, t < length, on the device; built on first use of (frames, length)
   const void* envelope(size_t fr, size_t length) const {
@@ -261,7 +240,7 @@ template <typename T> class StftPlan : public HandleBase {
   size_t pad_ = 0, bins_ = 0;
   int device_ = 0;
   std::unique_ptr<RealPlan<T>> real_;
-  bool have_fused_ = false, fused_ = false;
+  FusionSwitch fusion_;
   DevBuf win_;
   std::vector<double> win_host_;
   mutable std::map<std::pair<size_t, size_t>, std::unique_ptr<DevBuf>> env_;

@@ -13,3 +13,18 @@
 #define FOURIER_CG_2048_FIRST 4
 
 #define FOURIER_CG_4096 2
+
+// The whole-row kernels' tile shapes (kernels_pass.cpp's MODE_ROWS table) the fused frame kernels are instantiated on, as the body of a
+// get_*_rows_kernel(Real<T>, int L): `return MAKE<T, L, CG>();` for h = L, the tile width of the whole-row kernel of that length, a
+// descriptor without a kernel otherwise -- f64 h = 1024 is a one-launch 32 x 32 plan and has no row kernel.
+#define FOURIER_FRAME_ROWS_TABLE(T, L, MAKE)                 \
+  switch (L) {                                               \
+    case 64: return MAKE<T, 64, 16>();                       \
+    case 128: return MAKE<T, 128, FOURIER_CG_128_ROWS>();    \
+    case 256: return MAKE<T, 256, 16>();                     \
+    case 512: return MAKE<T, 512, FOURIER_CG_512>();         \
+    case 1024:                                               \
+      if constexpr (sizeof(T) == 4) return MAKE<T, 1024, 4>(); \
+      return {};                                             \
+    default: return {};                                      \
+  }
