@@ -21,6 +21,7 @@
 #include "stft_plan.h"
 #include "mdct_plan.h"
 #include "spectrogram_plan.h"
+#include "csd_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -399,6 +400,48 @@ FOURIER_DEFINE_MDCT_ABI(double, double)
 
 FOURIER_DEFINE_SPECTROGRAM_ABI(float, float)
 FOURIER_DEFINE_SPECTROGRAM_ABI(double, double)
+
+// cross-spectral density and coherence of two signals on the STFT's frames (fourier_hip_csd_*)
+#define FOURIER_DEFINE_CSD_ABI(T, SUFFIX)                                                                        \
+  extern "C" fc::fourier_csd_##SUFFIX* fourier_hip_csd_create_##SUFFIX(size_t n_fft, size_t hop, size_t win_length, int pad_mode, int device) { \
+    return (fc::fourier_csd_##SUFFIX*)create_handle<CsdPlan<T>>(n_fft, hop, win_length, pad_mode, device);       \
+  }                                                                                                              \
+  extern "C" void fourier_hip_csd_destroy_##SUFFIX(fc::fourier_csd_##SUFFIX* h) { destroy_handle<CsdPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_csd_describe_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) { return describe_handle<CsdPlan<T>>(h); } \
+  extern "C" int fourier_hip_csd_last_status_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) { return last_status_of<CsdPlan<T>>(h); } \
+  extern "C" int fourier_hip_csd_set_option_##SUFFIX(fc::fourier_csd_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<CsdPlan<T>>(h, key, v);                                                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_csd_n_fft_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) { return h ? ((const CsdPlan<T>*)h)->n_fft() : 0; } \
+  extern "C" size_t fourier_hip_csd_hop_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) { return h ? ((const CsdPlan<T>*)h)->hop() : 0; } \
+  extern "C" size_t fourier_hip_csd_win_length_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) {                     \
+    return h ? ((const CsdPlan<T>*)h)->win_length() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_csd_bins_##SUFFIX(const fc::fourier_csd_##SUFFIX* h) { return h ? ((const CsdPlan<T>*)h)->bins() : 0; } \
+  extern "C" size_t fourier_hip_csd_frames_##SUFFIX(const fc::fourier_csd_##SUFFIX* h, size_t length) {          \
+    return h ? ((const CsdPlan<T>*)h)->frames(length) : 0;                                                       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_csd_set_window_##SUFFIX(fc::fourier_csd_##SUFFIX* h, const void* d_window, void* stream) { \
+    CsdPlan<T>* p = (CsdPlan<T>*)h;                                                                              \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_csd_reserve_##SUFFIX(const fc::fourier_csd_##SUFFIX* h, size_t length, size_t batch) { \
+    const CsdPlan<T>* p = (const CsdPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_csd_csd_##SUFFIX(const fc::fourier_csd_##SUFFIX* h, const void* d_x, const void* d_y, void* d_out, size_t length, \
+                                              size_t batch, int onesided_fold, double scale, void* stream) {     \
+    const CsdPlan<T>* p = (const CsdPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->csd(d_x, d_y, d_out, length, batch, onesided_fold != 0, scale, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_csd_coherence_##SUFFIX(const fc::fourier_csd_##SUFFIX* h, const void* d_x, const void* d_y, void* d_out, \
+                                                    size_t length, size_t batch, void* stream) {                 \
+    const CsdPlan<T>* p = (const CsdPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->coherence(d_x, d_y, d_out, length, batch, (hipStream_t)stream); });        \
+  }
+
+FOURIER_DEFINE_CSD_ABI(float, float)
+FOURIER_DEFINE_CSD_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -174,9 +174,10 @@ typedef void (*R2RKernel)(R2RArgs);
 typedef void (*StftKernel)(StftArgs);
 typedef void (*MdctKernel)(MdctArgs);
 typedef void (*SpectrogramKernel)(SpectrogramArgs);
-// The fused frame route of a frame handle (STFT, MDCT, spectrogram) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
+typedef void (*CsdKernel)(CsdArgs);
+// The fused frame route of a frame handle (STFT, MDCT, spectrogram, cross spectrum) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
 // one shape.  STFT and MDCT have fn[0]; the spectrogram one per epilogue, fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL].
-// L == 0: none for that length
+// The cross spectrum has fn[0].  L == 0: none for that length
 template <typename Args> struct FrameRowsKernel {
   void (*fn[4])(Args) = {nullptr, nullptr, nullptr, nullptr};
   int L = 0, CG = 0, NT = 0, COLS = 0;
@@ -185,10 +186,12 @@ template <typename Args> struct FrameRowsKernel {
 typedef FrameRowsKernel<StftArgs> StftRowsKernel;
 typedef FrameRowsKernel<MdctArgs> MdctRowsKernel;
 typedef FrameRowsKernel<SpectrogramArgs> SpectrogramRowsKernel;
+typedef FrameRowsKernel<CsdArgs> CsdRowsKernel;
 // the part of a frame kernel's argument block that holds the frame geometry and the row core's stage tables
 static inline StftArgs& frame_block(StftArgs& a) { return a; }
 static inline MdctArgs& frame_block(MdctArgs& a) { return a; }
 static inline StftArgs& frame_block(SpectrogramArgs& a) { return a.f; }
+static inline StftArgs& frame_block(CsdArgs& a) { return a.f; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*MixKernelFn)(MixArgs);
@@ -284,6 +287,10 @@ template <typename T> struct Real {};
   /* fused frame route for n_fft = 2 L on the whole-row kernel of length L                                             */ \
   SpectrogramKernel get_spectrogram_kernel(Real<T>, int which);                                                        \
   SpectrogramRowsKernel get_spectrogram_rows_kernel(Real<T>, int L);                                                   \
+  /* kernels_csd.cpp: the sweeps of the cross-spectrum handle, which = CSD_COLSUM / CSD_REDUCE (kernel_args.h); its fused */ \
+  /* frame route for n_fft = 2 L on the whole-row kernel of length L                                                   */ \
+  CsdKernel get_csd_kernel(Real<T>, int which);                                                                        \
+  CsdRowsKernel get_csd_rows_kernel(Real<T>, int L);                                                                   \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
@@ -322,9 +329,10 @@ template <typename T> struct Real {};
 FOURIER_DECLARE_REGISTRY(float)
 FOURIER_DECLARE_REGISTRY(double)
 #undef FOURIER_DECLARE_REGISTRY
-// ... the three fused frame routes by their argument block
+// ... the fused frame routes by their argument block
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, StftRowsKernel& k) { k = get_stft_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, MdctRowsKernel& k) { k = get_mdct_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, SpectrogramRowsKernel& k) { k = get_spectrogram_rows_kernel(r, L); }
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, CsdRowsKernel& k) { k = get_csd_rows_kernel(r, L); }
 
 }  // namespace fourier_hip

@@ -265,8 +265,8 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, (uint64_t)rows * g.wpr, k.NT, k.smem, stream, a);
   }
 
-  // The fused frame routes of the STFT, MDCT and spectrogram handles (stft_rows_kernel, mdct_rows_kernel, spectrogram_rows_kernel;
-  // stft_plan.h, mdct_plan.h, spectrogram_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
+  // The fused frame routes of the STFT, MDCT, spectrogram and cross-spectrum handles (stft_rows_kernel, mdct_rows_kernel,
+  // spectrogram_rows_kernel, csd_rows_kernel; stft_plan.h, mdct_plan.h, spectrogram_plan.h, csd_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
   // is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
   template <typename Args> bool enable_frame_rows() {
     if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
@@ -688,7 +688,7 @@ template <typename T> class Pow2Engine {
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   StageTables<T>* conv_st_ = nullptr;
-  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel> frame_rows_;
+  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel> frame_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -248,6 +248,32 @@ struct SpectrogramArgs {
   double scale;               // reduce: the caller's scale over frames
 };
 
+// ---- cross-spectral density and coherence (kernels_csd.h; CsdPlan, csd_plan.h)
+// `f` is the STFT's argument block with f.in at the first sample of x's row 0 of the launch; `in2` is the same row of y.  The partial
+// sums are four planes of `bins` reals per (row, slot): |X|^2, |Y|^2, Re and Im of conj(X) Y, slot v = row * tiles + t at
+// part + v * 4 * bins.  csd_rows_kernel: workgroup blk = row * tiles + tile over the frame pairs tile * COLS / 2 ... of that row.
+// csd_colsum_kernel: one lane per (slot, bin) of `count` / bins slots from slot0 on, slot v the frames t * tile_frames ... of a row, over
+// the flat frames g0 ... g1 - 1 whose transforms lie at f.in: X of frame g at (g - g0) * bins, Y of it `ystride` complex values behind.
+// csd_reduce_kernel: `count` = rows * bins lanes, the slots of a row summed in ascending order; coherence == 0 writes the complex
+// f.out[b, k] = scale * c_k * (Re, Im), else the real |(Re, Im)|^2 / (sum |X|^2 * sum |Y|^2).
+enum { CSD_COLSUM = 0, CSD_REDUCE = 1 };
+enum { CSD_PXX = 0, CSD_PYY = 1, CSD_RE = 2, CSD_IM = 3, CSD_PLANES = 4 };
+struct CsdArgs {
+  StftArgs f;
+  const void* in2;            // y: the rows of the second signal, laid out as f.in
+  void* part;                 // the partial sums, rows x tiles x 4 x bins reals
+  uint32_t tiles;             // slots per row
+  uint32_t tl_m, tl_l;        // fused: blk / tiles = (umulhi(blk, tl_m) + blk) >> tl_l
+  uint32_t bins;
+  uint32_t tile_frames;       // composed: frames per slot
+  int fold;                   // reduce: c_k = 2 for the bins with a mirror, 0 < 2k < n_fft
+  int coherence;              // reduce: the coherence instead of the cross spectrum
+  uint64_t slot0, g0, g1;     // composed: first slot of the launch, the chunk's flat frame range (from row 0 of the group)
+  uint64_t ystride;           // composed: complex values between X and Y of a frame in the scratch
+  uint64_t count;             // sweeps: lanes
+  double scale;               // reduce: the caller's scale over frames
+};
+
 // ---- modified discrete cosine transform (kernels_mdct.h; MdctPlan, mdct_plan.h)
 // A frame is 2n samples, the hop n; frame f of a row covers xpad[f n - pad ... f n - pad + 2n), zero outside the row.  The flat frame
 // index, `first`, `total` and the multiply-high division are StftArgs'.  Even n = 2h: a frame is h complex values in the scratch

@@ -1019,6 +1019,87 @@ def welch(x, fs=1.0, window=None, nperseg=256, noverlap=None, scaling="density",
     return_onesided the bins that have a mirror count twice, without it they do not (the one-sided HALF of the two-sided spectrum).
     NO DETRENDING: scipy's default, detrend="constant", removes every segment's mean first; this never does, and offers no `detrend`
     argument.  Subtract the mean yourself where the difference at the lowest bins matters."""
+    p, scale, freqs = _welch_plan(x, fs, window, nperseg, noverlap, scaling, Spectrogram)
+    return freqs, p.welch(x.contiguous(), bool(return_onesided), scale)
+
+
+class CrossSpectrum(_Handle):
+    """Batched cross-spectral density and coherence of two signals (include/fourier.h, fourier_hip_csd_*) on device memory: of the frames
+    X and Y an Stft of the same parameters gives for a row of x and the same row of y, scale * c_k / frames * sum_f conj(X) Y (complex)
+    and |sum_f conj(X) Y|^2 / (sum_f |X|^2 sum_f |Y|^2) (real) -- neither writes a frame.  n_fft, hop, win_length and the padding are
+    fixed at create; the window is set afterwards (set_window; default all ones)."""
+
+    _prefix = "fourier_hip_csd_"
+    _destroy = "fourier_hip_csd_destroy"
+
+    def __init__(self, n_fft, real="f32", hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+        n_fft = int(n_fft)
+        hop = n_fft // 4 if hop_length is None else int(hop_length)
+        wl = n_fft if win_length is None else int(win_length)
+        self.pad_mode = _stft_pad_mode(center, pad_mode)
+        if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+            raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+        self._create(real, f"cross-spectrum plan of n_fft {n_fft}, hop {hop}, win_length {wl}, padding {self.pad_mode}", n_fft, hop, wl,
+                     STFT_PAD_MODES[self.pad_mode], int(device))
+        self._n, self._hop, self._wl = n_fft, hop, wl
+
+    # the framing, the window and the options are the spectrogram handle's
+    n_fft, hop, win_length, bins, frames = Spectrogram.n_fft, Spectrogram.hop, Spectrogram.win_length, Spectrogram.bins, Spectrogram.frames
+    set_option, set_window_ptr, set_window, _rows = Spectrogram.set_option, Spectrogram.set_window_ptr, Spectrogram.set_window, Spectrogram._rows
+
+    def reserve(self, length, batch):
+        """Later csd and coherence calls of at most `batch` rows of `length` reals never allocate (on the route selected now)."""
+        self._call("reserve", int(length), int(batch))
+
+    def csd_ptr(self, d_x, d_y, d_out, length, batch, onesided_fold=True, scale=1.0, stream=0):
+        """`batch` rows of `length` reals at d_x and at d_y -> batch x bins() complex values scale * c_k / frames * sum_f conj(X) Y at
+        d_out, enqueued on `stream`."""
+        self._call("csd", d_x, d_y, d_out, int(length), int(batch), int(bool(onesided_fold)), float(scale), stream)
+
+    def coherence_ptr(self, d_x, d_y, d_out, length, batch, stream=0):
+        """... -> batch x bins() reals |sum_f conj(X) Y|^2 / (sum_f |X|^2 sum_f |Y|^2) at d_out, on `stream`."""
+        self._call("coherence", d_x, d_y, d_out, int(length), int(batch), stream)
+
+    def _pair(self, x, y, out, out_dtype):
+        import torch
+
+        rdt, length, _ = self._rows(x)
+        _require_cuda(y, rdt)
+        if tuple(y.shape) != tuple(x.shape) or y.device != x.device:
+            raise ValueError(f"x and y must have the same shape and device, got {tuple(x.shape)} and {tuple(y.shape)}")
+        shape = tuple(x.shape[:-1]) + (self.bins(),)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=x.device)
+        else:
+            _require_out(out, shape, out_dtype, x.device)
+        return out, length, x.numel() // length
+
+    def csd(self, x, y, onesided_fold=True, scale=1.0, out=None):
+        """Contiguous (..., length) real CUDA tensors x and y of one shape -> a new (..., bins) complex tensor
+        scale * c_k / frames * sum_f conj(X) Y, or `out`, on the current stream.  No detrending."""
+        out, length, batch = self._pair(x, y, out, _torch_dtypes(self.real)[1])
+        if batch:
+            self.csd_ptr(x.data_ptr(), y.data_ptr(), out.data_ptr(), length, batch, onesided_fold, scale, _stream(x))
+        return out
+
+    def coherence(self, x, y, out=None):
+        """... -> a new (..., bins) real tensor |sum_f conj(X) Y|^2 / (sum_f |X|^2 sum_f |Y|^2), or `out`.  No detrending."""
+        out, length, batch = self._pair(x, y, out, _torch_dtypes(self.real)[0])
+        if batch:
+            self.coherence_ptr(x.data_ptr(), y.data_ptr(), out.data_ptr(), length, batch, _stream(x))
+        return out
+
+
+def create_csd_f32(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return CrossSpectrum(n_fft, "f32", hop_length, win_length, center, pad_mode, device)
+
+
+def create_csd_f64(n_fft, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return CrossSpectrum(n_fft, "f64", hop_length, win_length, center, pad_mode, device)
+
+
+def _welch_plan(x, fs, window, nperseg, noverlap, scaling, cls):
+    """welch's argument rules: the cached handle of class `cls` with the window set, the scale of `scaling` and the frequencies"""
     import torch
 
     real = _real_rows(x)
@@ -1034,11 +1115,43 @@ def welch(x, fs=1.0, window=None, nperseg=256, noverlap=None, scaling="density",
         raise ValueError(f"a row of {x.shape[-1]} samples is shorter than nperseg {nperseg}")
     if window is None:
         window = torch.hann_window(nperseg, periodic=True, dtype=torch.float64, device=x.device).to(x.dtype)
-    p = _stft_plan(x, nperseg, nperseg - noverlap, nperseg, window, False, "reflect", real, Spectrogram)
+    p = _stft_plan(x, nperseg, nperseg - noverlap, nperseg, window, False, "reflect", real, cls)
     w = window.detach().to(torch.float64).cpu()
     scale = 1.0 / (float(fs) * float((w * w).sum())) if scaling == "density" else 1.0 / float(w.sum()) ** 2
     freqs = torch.arange(nperseg // 2 + 1, dtype=x.dtype, device=x.device) * (float(fs) / nperseg)
-    return freqs, p.welch(x.contiguous(), bool(return_onesided), scale)
+    return p, scale, freqs
+
+
+def _same_rows(x, y):
+    _real_rows(x)
+    if not (_is_torch(y) and y.is_cuda and y.dtype == x.dtype):
+        raise TypeError(f"y must be a CUDA {_names((x.dtype,))} tensor like x")
+    if tuple(y.shape) != tuple(x.shape) or y.device != x.device:
+        raise ValueError(f"x and y must have the same shape and device, got {tuple(x.shape)} and {tuple(y.shape)}")
+
+
+def csd(x, y, fs=1.0, window=None, nperseg=256, noverlap=None, scaling="density", return_onesided=True):
+    """scipy.signal.csd(x, y, fs, window, nperseg, noverlap, detrend=False, scaling=scaling, average="mean") along the last axis of two
+    float32 / float64 CUDA tensors of one shape (..., length) on the current stream.  Segments, window default, scaling and
+    return_onesided are welch's: segments of nperseg samples every nperseg - noverlap (noverlap defaults to nperseg // 2), no padding,
+    the periodic Hann window where `window` is None.  Returns (freqs, Pxy): nperseg // 2 + 1 frequencies k fs / nperseg and
+    (..., nperseg // 2 + 1) complex values, the mean over the segments of conj(X) Y times the scale.
+    NO DETRENDING: scipy's default, detrend="constant", removes every segment's mean first; this never does, and offers no `detrend`
+    argument.  Subtract the mean yourself where the difference at the lowest bins matters."""
+    _same_rows(x, y)
+    p, scale, freqs = _welch_plan(x, fs, window, nperseg, noverlap, scaling, CrossSpectrum)
+    return freqs, p.csd(x.contiguous(), y.contiguous(), bool(return_onesided), scale)
+
+
+def coherence(x, y, fs=1.0, window=None, nperseg=256, noverlap=None):
+    """scipy.signal.coherence(x, y, fs, window, nperseg, noverlap, detrend=False): |Pxy|^2 / (Pxx Pyy) of welch's segments along the last
+    axis of two float32 / float64 CUDA tensors of one shape (..., length) on the current stream.  Returns (freqs, Cxy) with
+    (..., nperseg // 2 + 1) reals; a bin whose denominator is 0 gives what the IEEE division gives.
+    NO DETRENDING: scipy's default, detrend="constant", removes every segment's mean first; this never does, and offers no `detrend`
+    argument.  Subtract the mean yourself where the difference at the lowest bins matters."""
+    _same_rows(x, y)
+    p, _, freqs = _welch_plan(x, fs, window, nperseg, noverlap, "density", CrossSpectrum)
+    return freqs, p.coherence(x.contiguous(), y.contiguous())
 
 
 class Mdct(_Handle):

@@ -868,6 +868,84 @@ const char *fourier_hip_spectrogram_describe_double(const FOURIER_STRUCT fourier
 int fourier_hip_spectrogram_last_status_float(const FOURIER_STRUCT fourier_spectrogram_float *);
 int fourier_hip_spectrogram_last_status_double(const FOURIER_STRUCT fourier_spectrogram_double *);
 
+/* ---------------- cross-spectral density and coherence (extension; the reference has none) ----------
+ * Of two signals x and y on DEVICE memory, the averaged cross spectrum of their short-time Fourier transforms' frames and the
+ * magnitude-squared coherence, without a frame being written anywhere the caller sees.  A handle is made with the STFT handle's parameters
+ * (n_fft, hop, win_length, pad mode FOURIER_STFT_PAD_*): the framing, the centring of the window, fourier_hip_csd_frames_* and
+ * fourier_hip_csd_set_window_* (win_length reals T on the device, NULL: all ones; a set-up call that waits for `stream`) are exactly those
+ * of fourier_hip_stft_*, and X[b, f, k] and Y[b, f, k] below are exactly what fourier_hip_stft_forward_* (unnormalized) produces for row b of
+ * x and of y.  bins = n_fft / 2 + 1.  d_x and d_y are each `batch` contiguous rows of `length` reals; they may be the same buffer.
+ * fourier_hip_csd_csd_*: batch x bins interleaved COMPLEX values out,
+ *   out[b, k] = scale * c_k / frames * sum_f conj(X[b, f, k]) * Y[b, f, k],
+ * c_k = 2 where onesided_fold != 0 and bin k has a mirror (0 < k < n_fft / 2, and also k = (n_fft - 1) / 2 for odd n_fft), else 1: the fold
+ * factor of fourier_hip_spectrogram_welch_*.  scipy.signal.csd(detrend = False, average = "mean") with PAD_NONE, hop = nperseg - noverlap,
+ * scale = 1 / (fs sum w^2) for a density and 1 / (sum w)^2 for a spectrum.
+ * fourier_hip_csd_coherence_*: batch x bins REALS out,
+ *   out[b, k] = |sum_f conj(X) Y|^2 / (sum_f |X|^2 * sum_f |Y|^2)
+ * (scale and fold cancel): scipy.signal.coherence(detrend = False).  A plain IEEE division: a bin whose denominator is 0 gives what the
+ * division gives.  There is NO detrending: scipy's default removes each segment's mean first, this does not.
+ * Determinism: no atomics.  Every sum over frames runs in an order fixed by the route, the shape and the scratch bound -- ascending
+ * frames inside a tile, then ascending tiles -- so two calls with equal arguments on one handle give bit-equal results.
+ * A NULL handle or pointer, reals not aligned to sizeof(T), a cross spectrum not aligned to 2 sizeof(T), any overlap of d_out with d_x or
+ * d_y, or an invalid length give FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  Stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_csd_describe_*: "csd <route>, coherence <route>: <the real plan's describe>"):
+ *   "fused rows"  n_fft = 2h whose h-point plan is one whole-row kernel (n_fft 128 ... 1024, f32 also 2048), wherever "stft fused rows"
+ *                 exists: gather, window, transform and untangle of the frames of BOTH signals and their products in ONE launch.  One
+ *                 workgroup per tile of frame pairs of one row sums |X|^2, |Y|^2 and conj(X) Y in ascending frame order into four rows
+ *                 of partials in a handle-owned buffer; a second sweep sums a row's tiles in ascending order and writes the result.
+ *   "composed"    any n_fft: per chunk of the flat frame index a gather sweep per signal and one run of the real-input plan over both
+ *                 into a handle-owned scratch (2 x (n_fft reals + bins complex) per frame pair, at most 1 GiB, never less than one pair),
+ *                 then a sweep that adds the chunk's products to the partials, and the same final sweep.
+ * Option "fusion" = 1 takes the fused route wherever it exists, 0 the composed one (the default: DESIGN.md section 4, "Cross-spectral
+ * density and coherence", has the measurement the default follows).  The partials stay within the scratch bound too (never less than one
+ * row's): more rows are walked in groups.  fourier_hip_csd_reserve_*(h, length, batch) sizes everything both entry points need for at
+ * most `batch` rows of `length` reals on the route selected at that time: they then never allocate.  Handles are Send, not Sync, like
+ * the complex ones; status of the last call: fourier_hip_csd_last_status_*. */
+struct fourier_csd_float;
+struct fourier_csd_double;
+
+/* NULL on failure (parameters outside the STFT handle's ranges included). */
+struct fourier_csd_float *fourier_hip_csd_create_float(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                       int pad_mode, int device);
+struct fourier_csd_double *fourier_hip_csd_create_double(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                         int pad_mode, int device);
+/* NULL is a no-op. */
+void fourier_hip_csd_destroy_float(FOURIER_STRUCT fourier_csd_float *);
+void fourier_hip_csd_destroy_double(FOURIER_STRUCT fourier_csd_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_csd_n_fft_float(const FOURIER_STRUCT fourier_csd_float *);
+FOURIER_SIZE_TYPE fourier_hip_csd_n_fft_double(const FOURIER_STRUCT fourier_csd_double *);
+FOURIER_SIZE_TYPE fourier_hip_csd_hop_float(const FOURIER_STRUCT fourier_csd_float *);
+FOURIER_SIZE_TYPE fourier_hip_csd_hop_double(const FOURIER_STRUCT fourier_csd_double *);
+FOURIER_SIZE_TYPE fourier_hip_csd_win_length_float(const FOURIER_STRUCT fourier_csd_float *);
+FOURIER_SIZE_TYPE fourier_hip_csd_win_length_double(const FOURIER_STRUCT fourier_csd_double *);
+FOURIER_SIZE_TYPE fourier_hip_csd_bins_float(const FOURIER_STRUCT fourier_csd_float *);
+FOURIER_SIZE_TYPE fourier_hip_csd_bins_double(const FOURIER_STRUCT fourier_csd_double *);
+/* frames of a row of `length` reals; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_csd_frames_float(const FOURIER_STRUCT fourier_csd_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_csd_frames_double(const FOURIER_STRUCT fourier_csd_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_csd_set_window_float(FOURIER_STRUCT fourier_csd_float *, const void *d_window, void *stream);
+int fourier_hip_csd_set_window_double(FOURIER_STRUCT fourier_csd_double *, const void *d_window, void *stream);
+int fourier_hip_csd_csd_float(const FOURIER_STRUCT fourier_csd_float *, const void *d_x, const void *d_y, void *d_out,
+                              FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int onesided_fold, double scale, void *stream);
+int fourier_hip_csd_csd_double(const FOURIER_STRUCT fourier_csd_double *, const void *d_x, const void *d_y, void *d_out,
+                               FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, int onesided_fold, double scale, void *stream);
+int fourier_hip_csd_coherence_float(const FOURIER_STRUCT fourier_csd_float *, const void *d_x, const void *d_y, void *d_out,
+                                    FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_csd_coherence_double(const FOURIER_STRUCT fourier_csd_double *, const void *d_x, const void *d_y, void *d_out,
+                                     FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_csd_reserve_float(const FOURIER_STRUCT fourier_csd_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_csd_reserve_double(const FOURIER_STRUCT fourier_csd_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed route, 1 = the fused one wherever it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_csd_set_option_float(FOURIER_STRUCT fourier_csd_float *, const char *key, long long value);
+int fourier_hip_csd_set_option_double(FOURIER_STRUCT fourier_csd_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_csd_describe_float(const FOURIER_STRUCT fourier_csd_float *);
+const char *fourier_hip_csd_describe_double(const FOURIER_STRUCT fourier_csd_double *);
+int fourier_hip_csd_last_status_float(const FOURIER_STRUCT fourier_csd_float *);
+int fourier_hip_csd_last_status_double(const FOURIER_STRUCT fourier_csd_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1183,6 +1261,60 @@ template <typename T> struct spectrogram;
 FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_SPECTROGRAM_WRAPPER
+
+/* cross-spectral density and coherence of two signals on device memory (extension): fourier::csd<float> / <double>; the pad modes are stft_pad */
+template <typename T> struct csd;
+
+#define FOURIER_DEFINE_CXX_CSD_WRAPPER(T, SUFFIX)                                                  \
+  template <> struct csd<T> {                                                                      \
+    csd(std::size_t n_fft, std::size_t hop, std::size_t win_length, stft_pad pad = stft_pad::reflect, int device = -1) \
+        : impl(::fourier::c::fourier_hip_csd_create_##SUFFIX(n_fft, hop, win_length, static_cast<int>(pad), device), \
+               ::fourier::c::fourier_hip_csd_destroy_##SUFFIX) {}                                  \
+    csd() = delete;                                                                                \
+    csd(const csd &) = delete;                                                                     \
+    csd(csd &&) = default;                                                                         \
+    csd &operator=(const csd &) = delete;                                                          \
+    csd &operator=(csd &&) = default;                                                              \
+    ~csd() = default;                                                                              \
+    std::size_t n_fft() const { return ::fourier::c::fourier_hip_csd_n_fft_##SUFFIX(impl.get()); } \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_csd_hop_##SUFFIX(impl.get()); }     \
+    std::size_t win_length() const { return ::fourier::c::fourier_hip_csd_win_length_##SUFFIX(impl.get()); } \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_csd_bins_##SUFFIX(impl.get()); }   \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_csd_frames_##SUFFIX(impl.get(), length);                    \
+    }                                                                                              \
+    /* win_length reals on the device; nullptr: all ones */                                        \
+    int set_window(const void *d_window, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_csd_set_window_##SUFFIX(impl.get(), d_window, stream);      \
+    }                                                                                              \
+    /* batch rows of `length` reals each -> batch x bins complex scale c_k / frames sum_f conj(X) Y (no detrending) */ \
+    int csd_device(const void *d_x, const void *d_y, void *d_out, std::size_t length, std::size_t batch, \
+                   bool onesided_fold = true, double scale = 1.0, void *stream = nullptr) const {  \
+      return ::fourier::c::fourier_hip_csd_csd_##SUFFIX(impl.get(), d_x, d_y, d_out, length, batch, \
+                                                        onesided_fold ? 1 : 0, scale, stream);     \
+    }                                                                                              \
+    /* ... -> batch x bins reals |sum_f conj(X) Y|^2 / (sum_f |X|^2 sum_f |Y|^2) */                \
+    int coherence_device(const void *d_x, const void *d_y, void *d_out, std::size_t length, std::size_t batch, \
+                         void *stream = nullptr) const {                                           \
+      return ::fourier::c::fourier_hip_csd_coherence_##SUFFIX(impl.get(), d_x, d_y, d_out, length, batch, stream); \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_csd_reserve_##SUFFIX(impl.get(), length, batch);            \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_csd_set_option_##SUFFIX(impl.get(), key, value);            \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_csd_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_csd_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_csd_##SUFFIX,                                          \
+                      void (*)(::fourier::c::fourier_csd_##SUFFIX *)> impl;                        \
+  };
+FOURIER_DEFINE_CXX_CSD_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_CSD_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_CSD_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
