@@ -67,6 +67,10 @@ _CSD = ("fourier_hip_csd_", {  # cross-spectral density and coherence of two sig
     "csd": (ci, [vp, vp, vp, vp, sz, sz, ci, ctypes.c_double, vp]),  # handle, d_x, d_y, d_out, length, batch, onesided_fold, scale, stream
     "coherence": (ci, [vp, vp, vp, vp, sz, sz, vp]),                 # handle, d_x, d_y, d_out, length, batch, stream
     "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_HILBERT = ("fourier_hip_hilbert_", {  # analytic signal and envelope of real rows
+    "create": (vp, [sz, ci]), "destroy": (None, [vp]), "size": (sz, [vp]),
+    "analytic": (ci, [vp, vp, vp, sz, vp]), "envelope": (ci, [vp, vp, vp, sz, vp]),  # handle, d_in, d_out, batch, stream
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -88,8 +92,9 @@ STFT_SYMBOLS = list(_signatures(_STFT))
 MDCT_SYMBOLS = list(_signatures(_MDCT))
 SPECTROGRAM_SYMBOLS = list(_signatures(_SPECTROGRAM))
 CSD_SYMBOLS = list(_signatures(_CSD))
+HILBERT_SYMBOLS = list(_signatures(_HILBERT))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -99,7 +104,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -22,6 +22,7 @@
 #include "mdct_plan.h"
 #include "spectrogram_plan.h"
 #include "csd_plan.h"
+#include "hilbert_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -442,6 +443,32 @@ FOURIER_DEFINE_SPECTROGRAM_ABI(double, double)
 
 FOURIER_DEFINE_CSD_ABI(float, float)
 FOURIER_DEFINE_CSD_ABI(double, double)
+
+// analytic signal and envelope of real rows (fourier_hip_hilbert_*)
+#define FOURIER_DEFINE_HILBERT_ABI(T, SUFFIX)                                                                    \
+  FOURIER_DEFINE_HANDLE_ABI(hilbert, fourier_hilbert_##SUFFIX, HilbertPlan<T>, SUFFIX)                           \
+  extern "C" fc::fourier_hilbert_##SUFFIX* fourier_hip_hilbert_create_##SUFFIX(size_t size, int device) {        \
+    return (fc::fourier_hilbert_##SUFFIX*)create_handle<HilbertPlan<T>>(size, device);                           \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_hilbert_size_##SUFFIX(const fc::fourier_hilbert_##SUFFIX* h) {                   \
+    return h ? ((const HilbertPlan<T>*)h)->size() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" int fourier_hip_hilbert_analytic_##SUFFIX(const fc::fourier_hilbert_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                       size_t batch, void* stream) {                             \
+    const HilbertPlan<T>* p = (const HilbertPlan<T>*)h;                                                          \
+    return guarded_handle(p, [&] { p->analytic(d_in, d_out, batch, (hipStream_t)stream); });                     \
+  }                                                                                                              \
+  extern "C" int fourier_hip_hilbert_envelope_##SUFFIX(const fc::fourier_hilbert_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                       size_t batch, void* stream) {                             \
+    const HilbertPlan<T>* p = (const HilbertPlan<T>*)h;                                                          \
+    return guarded_handle(p, [&] { p->envelope(d_in, d_out, batch, (hipStream_t)stream); });                     \
+  }                                                                                                              \
+  extern "C" int fourier_hip_hilbert_set_option_##SUFFIX(fc::fourier_hilbert_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<HilbertPlan<T>>(h, key, v);                                                         \
+  }
+
+FOURIER_DEFINE_HILBERT_ABI(float, float)
+FOURIER_DEFINE_HILBERT_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

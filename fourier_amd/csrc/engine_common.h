@@ -194,6 +194,7 @@ static inline StftArgs& frame_block(SpectrogramArgs& a) { return a.f; }
 static inline StftArgs& frame_block(CsdArgs& a) { return a.f; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
+typedef void (*HilbertKernel)(HilbertArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -293,6 +294,10 @@ template <typename T> struct Real {};
   CsdRowsKernel get_csd_rows_kernel(Real<T>, int L);                                                                   \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
+  /* kernels_hilbert.cpp: the analytic signal or the envelope of real rows in one launch on the shapes of the two-level */ \
+  /* plans of 2^11 ... 2^15 (hilbert_small_kernel); the sweeps of the composed route, which = HILBERT_EXPAND / HILBERT_ABS */ \
+  bool get_hilbert_small_kernel(Real<T>, int k, bool envelope, KernelInfo& info);                                      \
+  HilbertKernel get_hilbert_kernel(Real<T>, int which);                                                                \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

@@ -265,6 +265,32 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, (uint64_t)rows * g.wpr, k.NT, k.smem, stream, a);
   }
 
+  // The analytic signal or the envelope of real rows in one launch (hilbert_small_kernel; the analytic-signal handle): conv_small_kernel's
+  // shapes and tables; one kernel for each output.
+  bool enable_hilbert_small() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    if (hilbert_small_[0].fn) return true;
+    KernelInfo k[2];
+    for (int e = 0; e < 2; ++e)
+      if (!get_hilbert_small_kernel(Real<T>{}, ilog2(n_), e == 1, k[e])) return false;
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    for (int e = 0; e < 2; ++e) { set_smem_attribute(k[e]); hilbert_small_[e] = k[e]; }
+    return true;
+  }
+  // in: `batch` rows of n reals; out: rows of n complex values, apart from the input, or (envelope) of n reals, in == out allowed
+  void run_hilbert_small(const void* in, void* out, size_t batch, bool envelope, hipStream_t stream, unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    const KernelInfo& k = hilbert_small_[envelope ? 1 : 0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
+  }
+
   // The fused frame routes of the STFT, MDCT, spectrogram and cross-spectrum handles (stft_rows_kernel, mdct_rows_kernel,
   // spectrogram_rows_kernel, csd_rows_kernel; stft_plan.h, mdct_plan.h, spectrogram_plan.h, csd_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
   // is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
@@ -687,6 +713,7 @@ template <typename T> class Pow2Engine {
   bool tiny_ = false;
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
+  KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
   StageTables<T>* conv_st_ = nullptr;
   std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel> frame_rows_;
   FusedInfo fused_;

@@ -332,6 +332,20 @@ struct ConvArgs {
   int widen, real;            // lconv taps: real taps -> complex rows; the values are reals (else complex)
 };
 
+// ---- analytic signal and envelope (kernels_hilbert.h; HilbertPlan, hilbert_plan.h): the sweeps of the composed route, one lane per
+// element over a flat index of rows x n; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of the complex side per launch).
+// hilbert_expand_kernel: rows of h + 1 complex values X (a half spectrum) -> rows of n complex values X[k] m[k] * scale, m = 1 for
+// k = 0 and 2k = n, 2 for the other k <= h, 0 above.  hilbert_abs_kernel: `total` complex values z -> `total` reals |z|.
+enum { HILBERT_EXPAND = 0, HILBERT_ABS = 1 };
+struct HilbertArgs {
+  const void* in; void* out;
+  uint32_t n, h;              // values per row, n / 2
+  uint32_t total;             // rows * n
+  uint32_t div_m, div_l;      // idx / n = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  double scale;               // the inverse's 1 / n, computed in T
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

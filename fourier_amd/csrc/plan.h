@@ -585,6 +585,19 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_lconv_small(d_in, d_out, rows, bank, (uint32_t)filters, (uint32_t)(first % filters), real_data, geo, stream, nxcd_);
   }
 
+  // ---- the hook of the analytic-signal handle (HilbertPlan, hilbert_plan.h); exec() is not affected.  A one-launch two-level plan
+  // (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n reals in one launch of hilbert_small_kernel: rows of n complex values out, or
+  // (envelope) rows of n reals, which may be the input.  The caller keeps `batch` below 2^31.
+  bool enable_hilbert() {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_hilbert_small();
+  }
+  void exec_hilbert(const void* d_in, void* d_out, size_t batch, bool envelope, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_hilbert_small(d_in, d_out, batch, envelope, stream, nxcd_);
+  }
+
   // ---- the hooks of the frame handles (StftPlan, MdctPlan, SpectrogramPlan), selected by the kernels' argument block (StftArgs,
   // MdctArgs, SpectrogramArgs); exec() is not affected.  A plan of h points that is one whole-row pass runs the frames of n = 2h samples in
   // one launch of the family's rows kernel (kernels_frames.h): fn[which] on `groups` workgroups of frame_cols() frames, 0: those that

@@ -1154,6 +1154,117 @@ def coherence(x, y, fs=1.0, window=None, nperseg=256, noverlap=None):
     return freqs, p.coherence(x.contiguous(), y.contiguous())
 
 
+class Hilbert(_Handle):
+    """Batched analytic signal and envelope (include/fourier.h, fourier_hip_hilbert_*) on device memory: of rows of N reals x,
+    z = ifft(fft(x) * m) with m = 1 at bin 0 and (N even) N/2, 2 between them and 0 above -- scipy.signal.hilbert(x), N complex values a
+    row with Re z = x -- or the envelope |z|, N reals a row.  The envelope is abs(scipy.signal.hilbert(x)); it is NOT
+    scipy.signal.envelope, which filters and returns a residual as well."""
+
+    _prefix = "fourier_hip_hilbert_"
+    _destroy = "fourier_hip_hilbert_destroy"
+
+    def __init__(self, size, real="f32", device=-1):
+        if int(size) < 1:
+            raise ValueError(f"need size >= 1, got {size}")
+        self._create(real, f"analytic-signal plan of size {size}", int(size), int(device))
+        self._n = int(size)
+
+    def size(self):
+        return self._n
+
+    def set_option(self, key, value):
+        """"fusion": 1 = the one-launch kernel where the length has one (2^11 ... 2^15, f64 ... 2^14), 0 (default) = the composed route
+        (real forward transform, expand sweep, inverse transform)."""
+        self._call("set_option", key.encode(), int(value))
+
+    def analytic_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of N reals at d_in -> `batch` rows of N complex values at d_out (no overlap), enqueued on `stream`."""
+        self._call("analytic", d_in, d_out, int(batch), stream)
+
+    def envelope_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of N reals at d_in -> `batch` rows of N reals at d_out (d_out may be d_in), enqueued on `stream`."""
+        self._call("envelope", d_in, d_out, int(batch), stream)
+
+    def _run(self, x, out, complex_out):
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(x, rdt)
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        if out is None:
+            out = torch.empty(x.shape, dtype=cdt if complex_out else rdt, device=x.device)
+        elif complex_out or out is not x:
+            _require_out(out, x.shape, cdt if complex_out else rdt, x.device)
+        batch = x.numel() // self._n
+        if batch:
+            (self.analytic_ptr if complex_out else self.envelope_ptr)(x.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+    def analytic(self, x, out=None):
+        """Contiguous (..., N) float32 / float64 CUDA tensor -> a new complex tensor of the same shape, scipy.signal.hilbert along the
+        last axis, or `out` (which may not overlap `x`), on the current stream."""
+        return self._run(x, out, True)
+
+    def envelope(self, x, out=None):
+        """... -> a new real tensor of the same shape, abs(scipy.signal.hilbert(x)), or `out` (which may be `x`).  Not
+        scipy.signal.envelope."""
+        return self._run(x, out, False)
+
+
+def create_hilbert_f32(size, device=-1):
+    return Hilbert(size, "f32", device)
+
+
+def create_hilbert_f64(size, device=-1):
+    return Hilbert(size, "f64", device)
+
+
+def _hilbert(x, n, dim, out, complex_out):
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    d = _normalise_dims(x.dim(), (dim,))[0]
+    length = int(x.shape[d]) if n is None else int(n)
+    if length < 1:
+        raise ValueError(f"the transformed dimension must have length >= 1, got {length}")
+    real = _precision(x.dtype)[0]
+    shape = tuple(x.shape[:d]) + (length,) + tuple(x.shape[d + 1:])
+    odt = _torch_dtypes(real)[1 if complex_out else 0]
+    if out is not None and not (out is x and not complex_out):
+        if not (_is_torch(out) and out.is_cuda and out.dtype == odt and tuple(out.shape) == shape and out.device == x.device):
+            raise TypeError(f"out must be a CUDA {_names((odt,))} tensor of shape {shape} on the input's device")
+    plan = _cached_plan(Hilbert, length, real, int(_device_index(x)))
+    run = plan.analytic if complex_out else plan.envelope
+    if d == x.dim() - 1 and length == x.shape[d] and x.is_contiguous() and (out is None or out.is_contiguous()):
+        return run(x, out)
+    # any other dim, layout or length: a torch copy that makes the axis last, contiguous and `length` long (zero-padded or truncated)
+    src = x.movedim(d, -1)[..., :length]
+    if length > src.shape[-1]:
+        src = torch.nn.functional.pad(src, (0, length - src.shape[-1]))
+    res = run(src.contiguous()).movedim(-1, d)
+    if out is None:
+        return res.contiguous()
+    out.copy_(res)
+    return out
+
+
+def hilbert(x, N=None, dim=-1, out=None):
+    """scipy.signal.hilbert(x, N, axis=dim) of a float32 / float64 CUDA tensor on the current stream: the analytic signal, complex, whose
+    real part is x.  `N` zero-pads or truncates the axis first (a torch copy).  Returns a new tensor or `out`.  Only the last dimension of
+    a contiguous tensor is native (one cached Hilbert handle per (N, dtype, device)); any other `dim` is moved last with a torch copy."""
+    return _hilbert(x, N, dim, out, True)
+
+
+def envelope(x, dim=-1, out=None):
+    """abs(scipy.signal.hilbert(x, axis=dim)) of a float32 / float64 CUDA tensor on the current stream, without writing the analytic
+    signal; returns a new tensor or `out`, which may be `x`.  NOT scipy.signal.envelope (which band-limits and returns a residual)."""
+    return _hilbert(x, None, dim, out, False)
+
+
 class Mdct(_Handle):
     """Batched modified discrete cosine transform and its inverse (include/fourier.h, fourier_hip_mdct_*) on device memory: rows of
     `length` reals <-> frames x n reals per row, FRAME-MAJOR (frame f of row b at element offset (b * frames + f) * n).  A frame is 2n

@@ -946,6 +946,62 @@ const char *fourier_hip_csd_describe_double(const FOURIER_STRUCT fourier_csd_dou
 int fourier_hip_csd_last_status_float(const FOURIER_STRUCT fourier_csd_float *);
 int fourier_hip_csd_last_status_double(const FOURIER_STRUCT fourier_csd_double *);
 
+/* ---------------- analytic signal and envelope of real rows (extension; the reference has none) ----------
+ * Of `batch` rows of N >= 1 reals T on DEVICE memory, row b at element offset b*N, with X = fft(x) and
+ *   m[k] = 1 for k = 0 and (N even) k = N/2,  2 for 0 < k < N/2 (odd N: k <= (N-1)/2),  0 above,
+ * fourier_hip_hilbert_analytic_*: z = ifft(X (.) m), `batch` rows of N interleaved COMPLEX values out, Re z = x: scipy.signal.hilbert
+ * along the last axis;
+ * fourier_hip_hilbert_envelope_*: |z|, `batch` rows of N REALS out.  This is abs(scipy.signal.hilbert(x)); it is NOT
+ * scipy.signal.envelope.
+ * A NULL pointer, an input not aligned to sizeof(T), an analytic output not aligned to one complex value (2*sizeof(T)), an envelope
+ * output not aligned to sizeof(T) give FOURIER_HIP_INVALID_ARGUMENT.  analytic: ANY overlap of input and output is
+ * FOURIER_HIP_INVALID_ARGUMENT (the output is twice the input's size: rows do not line up).  envelope: d_out == d_in is in place and
+ * allowed, any other overlap is not.  batch == 0 is a successful no-op.  A row above 2^31 - 1 bytes of complex values cannot be
+ * carried by one launch: create fails (as fourier_hip_conv_create_*).  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_hilbert_describe_* begins with the route's name):
+ *   "hilbert one-launch"  N = 2^11 ... 2^15 (double: ... 2^14): load, FFT, multiplier computed from the bin index, inverse FFT, store
+ *                         z or |z| in ONE launch on register-resident data; no scratch.
+ *   "hilbert composed"    every N: real forward transform -> half spectrum (N/2 + 1 values a row) in the plan's scratch, one sweep that
+ *                         writes X[k] m[k] / N, zeros above, into the caller's output, the unscaled inverse in place there.  The
+ *                         envelope runs the sweep and the inverse in a second scratch array of N complex values a row, and a second
+ *                         sweep writes |z|.
+ * Option "fusion" (fourier_hip_hilbert_set_option_*): 1 = the one-launch route where the length has one, 0 = the composed route, the
+ * DEFAULT (the two routes have not been measured against each other).  The plan owns a scratch of at most 1 GiB (never less than one
+ * row) and walks larger batches in chunks of it; the first call with a batch larger than any before allocates it unless
+ * fourier_hip_hilbert_reserve_* was called for at least that batch (one size covers both entry points).  A NULL handle gives
+ * FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_hilbert_size_* and "" from fourier_hip_hilbert_describe_*.  Handles are Send, not
+ * Sync, like the complex ones; status of the last call: fourier_hip_hilbert_last_status_*. */
+struct fourier_hilbert_float;
+struct fourier_hilbert_double;
+
+/* NULL on failure (size 0 included). */
+struct fourier_hilbert_float *fourier_hip_hilbert_create_float(FOURIER_SIZE_TYPE size, int device);
+struct fourier_hilbert_double *fourier_hip_hilbert_create_double(FOURIER_SIZE_TYPE size, int device);
+/* NULL is a no-op. */
+void fourier_hip_hilbert_destroy_float(FOURIER_STRUCT fourier_hilbert_float *);
+void fourier_hip_hilbert_destroy_double(FOURIER_STRUCT fourier_hilbert_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_hilbert_size_float(const FOURIER_STRUCT fourier_hilbert_float *);
+FOURIER_SIZE_TYPE fourier_hip_hilbert_size_double(const FOURIER_STRUCT fourier_hilbert_double *);
+int fourier_hip_hilbert_analytic_float(const FOURIER_STRUCT fourier_hilbert_float *, const void *d_in, void *d_out,
+                                       FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_hilbert_analytic_double(const FOURIER_STRUCT fourier_hilbert_double *, const void *d_in, void *d_out,
+                                        FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_hilbert_envelope_float(const FOURIER_STRUCT fourier_hilbert_float *, const void *d_in, void *d_out,
+                                       FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_hilbert_envelope_double(const FOURIER_STRUCT fourier_hilbert_double *, const void *d_in, void *d_out,
+                                        FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_hilbert_reserve_float(const FOURIER_STRUCT fourier_hilbert_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_hilbert_reserve_double(const FOURIER_STRUCT fourier_hilbert_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed route, 1 = the one-launch route where it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_hilbert_set_option_float(FOURIER_STRUCT fourier_hilbert_float *, const char *key, long long value);
+int fourier_hip_hilbert_set_option_double(FOURIER_STRUCT fourier_hilbert_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_hilbert_describe_float(const FOURIER_STRUCT fourier_hilbert_float *);
+const char *fourier_hip_hilbert_describe_double(const FOURIER_STRUCT fourier_hilbert_double *);
+int fourier_hip_hilbert_last_status_float(const FOURIER_STRUCT fourier_hilbert_float *);
+int fourier_hip_hilbert_last_status_double(const FOURIER_STRUCT fourier_hilbert_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1315,6 +1371,47 @@ template <typename T> struct csd;
 FOURIER_DEFINE_CXX_CSD_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CSD_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CSD_WRAPPER
+
+/* analytic signal and envelope of real rows on device memory (extension): fourier::hilbert<float> / <double> */
+template <typename T> struct hilbert;
+
+#define FOURIER_DEFINE_CXX_HILBERT_WRAPPER(T, SUFFIX)                                              \
+  template <> struct hilbert<T> {                                                                  \
+    explicit hilbert(std::size_t size, int device = -1)                                            \
+        : impl(::fourier::c::fourier_hip_hilbert_create_##SUFFIX(size, device),                    \
+               ::fourier::c::fourier_hip_hilbert_destroy_##SUFFIX) {}                              \
+    hilbert() = delete;                                                                            \
+    hilbert(const hilbert &) = delete;                                                             \
+    hilbert(hilbert &&) = default;                                                                 \
+    hilbert &operator=(const hilbert &) = delete;                                                  \
+    hilbert &operator=(hilbert &&) = default;                                                      \
+    ~hilbert() = default;                                                                          \
+    std::size_t size() const { return ::fourier::c::fourier_hip_hilbert_size_##SUFFIX(impl.get()); }\
+    /* `batch` rows of N reals -> rows of N complex values z (no overlap) */                       \
+    int analytic_device(const void *d_in, void *d_out, std::size_t batch, void *stream = nullptr) const {\
+      return ::fourier::c::fourier_hip_hilbert_analytic_##SUFFIX(impl.get(), d_in, d_out, batch, stream);\
+    }                                                                                              \
+    /* ... -> rows of N reals |z| (d_out may be d_in) */                                           \
+    int envelope_device(const void *d_in, void *d_out, std::size_t batch, void *stream = nullptr) const {\
+      return ::fourier::c::fourier_hip_hilbert_envelope_##SUFFIX(impl.get(), d_in, d_out, batch, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_hilbert_reserve_##SUFFIX(impl.get(), batch);                \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_hilbert_set_option_##SUFFIX(impl.get(), key, value);        \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_hilbert_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_hilbert_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_hilbert_##SUFFIX,                                      \
+                      void (*)(::fourier::c::fourier_hilbert_##SUFFIX *)> impl;                    \
+  };
+FOURIER_DEFINE_CXX_HILBERT_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_HILBERT_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_HILBERT_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
