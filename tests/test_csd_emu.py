@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import chunk_walks
 import csd_truth as truth
 import spectrogram_truth
 from helpers import rel_l2
@@ -233,6 +234,24 @@ def test_chunk_and_group_walks_equal_the_unchunked_result(fa, monkeypatch):
     assert np.array_equal(csd(one, xx, yy), csd(big, xx, yy)) and np.array_equal(coherence(one, xx, yy), coherence(big, xx, yy))
     one.set_option("fusion", 0)  # and one frame pair per chunk on the composed route
     assert rel_l2(csd(one, xx, yy), truth.csd(xx, yy, 256, 64, pad_mode="reflect")) <= tol(one, "f64")
+
+
+@pytest.mark.parametrize("n_fft", chunk_walks.N_FFTS)
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_chunk_walks_at_two_slots_a_row(fa, monkeypatch, real, n_fft):
+    """tests/chunk_walks.py's cases, the ones tests/test_gpu_chunks.py runs on the MI355X: 64 frames a row under bounds of 32, 64 and 96
+    frame pairs (every chunk ends on a slot boundary: bit-equal to the unbounded handle) and 35 frames a row under bounds of 1 ... 40
+    pairs (chunks that end inside a slot: the re-associated sums within 32 eps of the norm of sqrt(Pxx Pyy))."""
+    chunk_walks.csd_chunks(chunk_walks.HostApi(fa, monkeypatch), real, n_fft)
+    chunk_walks.print_worst()
+
+
+@pytest.mark.parametrize("n_fft,fused", [(64, False), (250, False), (63, False), (256, True)])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_row_groups(fa, monkeypatch, real, n_fft, fused):
+    """A batch of five in groups of one row and of 2, 2 and 1 rows through one partials buffer (tests/chunk_walks.py)."""
+    chunk_walks.csd_groups(chunk_walks.HostApi(fa, monkeypatch), real, n_fft, fused)
+    chunk_walks.print_worst()
 
 
 @pytest.mark.parametrize("real", ["f32", "f64"])

@@ -1,14 +1,17 @@
 """The handles' chunk walks on the MI355X.  Every handle family that runs through a bounded scratch (RealPlan, R2RPlan, StftPlan,
-MdctPlan, ConvPlan, LinearConvPlan, RealNdPlan, the transpose route of the axis plan) cuts a call that does not fit the bound into
-chunks; the product library's bound is 1 GiB, so at test shapes it runs one chunk.  fourier_amd/lib/libfourier_experiments.so is built
+MdctPlan, SpectrogramPlan, CsdPlan, ConvPlan, LinearConvPlan, RealNdPlan, the transpose route of the axis plan) cuts a call that does not
+fit the bound into chunks; the product library's bound is 1 GiB, so at test shapes it runs one chunk.  fourier_amd/lib/libfourier_experiments.so is built
 from the same objects and reads the bound from the environment at create (scratch_bound, handle_common.h), which brings the walks --
 other grids of every launch, a second scratch half on an 8-byte and not 16-byte aligned address, seam frames transformed twice -- down
 to shapes of a few thousand elements.  The CPU twins are the chunk tests of tests/test_*_emu.py.
 
 Every case compares a handle created under a small bound against
   (a) the family's f64 truth, within the tolerance the family's own GPU test grants (restated here from tol() of test_gpu_real.py,
-      test_gpu_r2r.py, test_gpu_stft.py, test_gpu_mdct.py, test_gpu_conv.py, test_gpu_lconv.py, test_gpu_realnd.py, test_gpu_axis.py), and
-  (b) the result of a handle of the same library created without the bound, on the same input buffers, bit for bit.
+      test_gpu_r2r.py, test_gpu_stft.py, test_gpu_mdct.py, test_gpu_conv.py, test_gpu_lconv.py, test_gpu_realnd.py, test_gpu_axis.py;
+      tests/chunk_walks.py restates those of test_gpu_spectrogram.py and test_gpu_csd.py), and
+  (b) the result of a handle of the same library created without the bound, on the same input buffers, bit for bit.  The Welch
+      average, the cross spectrum and the coherence sum over frames: where a chunk ends inside a slot of partials the sum is
+      re-associated, and (b) becomes the bound tests/chunk_walks.py derives for that.
 How many chunks a case walks follows from the bound and the per-row scratch bytes stated beside it (the formulas of the plans'
 prepare()); each case asserts that the call is larger than one chunk.  Outputs lie between guard elements that must stay untouched."""
 import ctypes
@@ -17,6 +20,7 @@ import os
 import numpy as np
 import pytest
 
+import chunk_walks
 import mdct_truth
 import r2r_truth
 import stft_truth
@@ -255,6 +259,87 @@ def test_stft(torch, fx, monkeypatch, real, n_fft):
                 err = rel_l2(got.cpu().numpy(), want_y)
                 assert err <= ti, (real, n, hop, pad_mode, frames_in_scratch, err)
                 assert torch.equal(got, y), ("inverse", real, n, hop, pad_mode, frames_in_scratch)
+
+
+# ---- power spectrogram, Welch average, cross-spectral density and coherence
+class DeviceApi:
+    """tests/chunk_walks.py's adapter for the experiments library: handles created under bounded(), inputs on the device, every
+    output inside Guarded, results back as numpy arrays"""
+
+    def __init__(self, torch, fx, monkeypatch):
+        self.torch, self.fx, self.monkeypatch = torch, fx, monkeypatch
+
+    def _create(self, cls, real, n_fft, hop, pad_mode, w, bound, fusion):
+        create = lambda: cls(n_fft, real, hop, None, pad_mode != "none", "reflect", 0)  # noqa: E731
+        plan = create() if bound is None else bounded(self.monkeypatch, create, **{REAL: bound})
+        plan.set_option("fusion", fusion)
+        plan.set_window(self.put(w))
+        return plan
+
+    def spectrogram(self, real, n_fft, hop, pad_mode, w, bound, fusion=0):
+        return self._create(self.fx.Spectrogram, real, n_fft, hop, pad_mode, w, bound, fusion)
+
+    def cross_spectrum(self, real, n_fft, hop, pad_mode, w, bound, fusion=0):
+        return self._create(self.fx.CrossSpectrum, real, n_fft, hop, pad_mode, w, bound, fusion)
+
+    def put(self, a):
+        return self.torch.from_numpy(a).cuda()
+
+    def _run(self, call, shape, dtype):
+        out = Guarded(self.torch, shape, dtype)
+        call(out.out)
+        return out.checked().cpu().numpy()
+
+    def forward(self, plan, x, batch, length, power, normalized):
+        return self._run(lambda out: plan.forward(x, power, normalized, out=out), (batch, plan.frames(length), plan.bins()), x.dtype)
+
+    def welch(self, plan, x, batch, length, fold, scale):
+        return self._run(lambda out: plan.welch(x, fold, scale, out=out), (batch, plan.bins()), x.dtype)
+
+    def csd(self, plan, x, y, batch, length, fold, scale):
+        return self._run(lambda out: plan.csd(x, y, fold, scale, out=out), (batch, plan.bins()),
+                         self.torch.complex64 if x.dtype == self.torch.float32 else self.torch.complex128)
+
+    def coherence(self, plan, x, y, batch, length):
+        return self._run(lambda out: plan.coherence(x, y, out=out), (batch, plan.bins()), x.dtype)
+
+
+@pytest.mark.parametrize("n_fft", chunk_walks.N_FFTS)
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_spectrogram_and_welch(torch, fx, monkeypatch, real, n_fft):
+    """Scratch bytes per frame: bins * ELEM + n_fft * sizeof(T), the transformed frames first and the windowed frames behind
+    chunk * bins complex values; one row of partials: tiles * bins * sizeof(T).  64 frames a row under bounds of 32, 64 and 96 frames
+    (chunks end on slot boundaries, 96 inside a row: forward and Welch bit-equal to the unbounded handle); 35 frames a row under bounds
+    of 1, 2, 3, 7, 20, 35 and 40 frames (chunks end inside slots: a later launch adds to what an earlier one wrote).  The cases, the
+    walk each bound gives and the assertions are chunk_walks.spectrogram_chunks, which the CPU emulation runs too."""
+    chunk_walks.spectrogram_chunks(DeviceApi(torch, fx, monkeypatch), real, n_fft)
+
+
+@pytest.mark.parametrize("n_fft", chunk_walks.N_FFTS)
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_csd_and_coherence(torch, fx, monkeypatch, real, n_fft):
+    """Scratch bytes per frame pair: 2 * (bins * ELEM + n_fft * sizeof(T)), the y frames behind the chunk's ng x frames on both sides of
+    the transform (ystride = ng * bins); one row of partials: tiles * CSD_PLANES * bins * sizeof(T).  The shapes and bounds of
+    test_spectrogram_and_welch, in frame pairs; the smallest bounds also cut the batch into row groups.  The cases, the walk each
+    bound gives and the assertions are chunk_walks.csd_chunks, which the CPU emulation runs too."""
+    chunk_walks.csd_chunks(DeviceApi(torch, fx, monkeypatch), real, n_fft)
+
+
+@pytest.mark.parametrize("n_fft,fused", [(64, False), (250, False), (63, False), (256, True)])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_welch_row_groups(torch, fx, monkeypatch, real, n_fft, fused):
+    """A batch of five under a bound of 8 bytes (rows one by one, one frame per chunk) and of exactly two rows of partials (groups of
+    2, 2 and 1 rows), every group through the same partials buffer, an odd and an even row length; n_fft = 256 on the fused route,
+    bit-equal to the unbounded fused handle (chunk_walks.welch_groups)."""
+    chunk_walks.welch_groups(DeviceApi(torch, fx, monkeypatch), real, n_fft, fused)
+
+
+@pytest.mark.parametrize("n_fft,fused", [(64, False), (250, False), (63, False), (256, True)])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_csd_row_groups(torch, fx, monkeypatch, real, n_fft, fused):
+    """test_welch_row_groups for the cross spectrum and the coherence: the fused route takes its bases from x and from y again for
+    every group (chunk_walks.csd_groups)."""
+    chunk_walks.csd_groups(DeviceApi(torch, fx, monkeypatch), real, n_fft, fused)
 
 
 # ---- real-input transforms and DCT / DST

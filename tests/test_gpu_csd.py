@@ -1,6 +1,7 @@
 """The cross-spectrum handle on the MI355X: fourier_hip_csd_* through fourier_amd.CrossSpectrum and csd / coherence on torch tensors,
 against tests/csd_truth.py (f64 numpy on the rounded input).  The CPU twin is tests/test_csd_emu.py (it also covers the argument
-checks of the C ABI, the chunk walks and the allocation-free property after reserve).
+checks of the C ABI and the allocation-free property after reserve); the chunk and row-group walks under a small scratch bound run on
+the MI355X in tests/test_gpu_chunks.py, through the experiments library.
 
 Inputs of every accuracy check: x white Gaussian, y = 0.6 roll(x, 5) + 0.8 independent white Gaussian (|Pxy| stays near 0.6 of
 sqrt(Pxx Pyy), no bin near zero in norm), a window 0.5 + rand.  Tolerances, relative L2 over the whole output, with `base`
@@ -79,13 +80,13 @@ def pair(torch, g, shape, dt):
     return x, y
 
 
-def check(torch, fa, real, n_fft, hop, pad_mode="reflect", extra=3, batch=3, win_length=None):
-    """Frames per row = pairs per tile + 3: the last tile of every row is partly empty.  Both "fusion" values: the CSD with the fold
+def check(torch, fa, real, n_fft, hop, pad_mode="reflect", extra=3, batch=3, win_length=None, frames=None):
+    """Frames per row = pairs per tile + 3 unless given: the last tile of every row is partly empty.  Both "fusion" values: the CSD with the fold
     and scale 0.37 into a buffer that starts on an odd element with a sentinel on both sides, and the coherence, against the truth; the
     two routes within tolerance of each other."""
     plan = make(fa, real, n_fft, hop, win_length, pad_mode)
     rt, ct = dtypes(torch, real)
-    frames = pairs(real, n_fft) + 3
+    frames = pairs(real, n_fft) + 3 if frames is None else frames
     length = length_for(frames, n_fft, hop, pad_mode, extra)
     g = torch.Generator(device="cuda").manual_seed(n_fft + hop + length)
     w = 0.5 + torch.rand(plan.win_length(), dtype=rt, device="cuda", generator=g)
@@ -134,6 +135,71 @@ def test_fused_shapes(torch, fa, real):
         check(torch, fa, real, n, n // 4, "constant", extra=5)       # zero padding, an odd length
         check(torch, fa, real, n, n // 4, "none", extra=6)           # no padding: every frame interior
         check(torch, fa, real, n, n // 4, "reflect", extra=2, win_length=n - 56)
+
+
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_more_workgroups_than_xcds(torch, fa, real):
+    """6 tiles + 3 frames a row, batch 3: 3 * 7 = 21 workgroups, above 8 and no multiple of 8 -- the workgroup-to-block map
+    (real_xcd_block) gives the first XCDs one block more than the rest, and the tile-to-row division (real_div) runs on blocks past the
+    eighth.  check()'s assertions, with pairs of reals (even rows) and single reals (an odd length)."""
+    for n in (256, largest_fused(real)):
+        frames = 6 * pairs(real, n) + 3
+        assert 3 * -(-frames // pairs(real, n)) == 21
+        for pad_mode, extra in (("reflect", 2), ("none", 5)):
+            plan = check(torch, fa, real, n, n // 4, pad_mode, extra=extra, frames=frames)
+            plan.set_option("fusion", 1)
+            assert plan.describe().startswith("csd fused rows, coherence fused rows"), plan.describe()
+
+
+@pytest.mark.parametrize("fusion", [1, 0])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_input_on_an_odd_element(torch, fa, real, fusion):
+    """tests/test_gpu_stft.py's test of the same name for this handle.  An even hop, padding and row length: only the two base
+    addresses decide whether the fused kernel loads pairs of reals, and it does only where both are aligned.  x aligned and y one
+    element into its allocation, the reverse, both odd, and one odd buffer for both: against the truth, and bit-equal to what the
+    same handle gives from aligned copies.  One buffer for both: conj(X) X is real, but a product contracted into a fused multiply-add
+    may leave a rounding residue in Im, so the CSD is held to the truth's csd(x, x) and the coherence to 1."""
+    rt, _ = dtypes(torch, real)
+    for n in (256, largest_fused(real)):
+        hop, batch = n // 4, 3
+        frames = pairs(real, n) + 3
+        length = length_for(frames, n, hop, "reflect", 2)
+        assert hop % 2 == 0 and length % 2 == 0
+        g = torch.Generator(device="cuda").manual_seed(n + fusion)
+        xa, ya = pair(torch, g, (batch, length), rt)
+        holders = [torch.zeros(batch * length + 2, dtype=rt, device="cuda") for _ in range(2)]
+        xo, yo = (h[1:-1].view(batch, length) for h in holders)
+        xo.copy_(xa)
+        yo.copy_(ya)
+        before = [h.clone() for h in holders]
+        two = 2 * xa.element_size()
+        assert xo.data_ptr() % two != 0 and yo.data_ptr() % two != 0 and xa.data_ptr() % two == 0 and ya.data_ptr() % two == 0
+        plan = make(fa, real, n, hop)
+        w = 0.5 + torch.rand(n, dtype=rt, device="cuda", generator=g)
+        plan.set_window(w)
+        plan.set_option("fusion", fusion)
+        assert plan.describe().startswith("csd fused rows" if fusion else "csd composed"), plan.describe()
+        assert plan.frames(length) == frames
+        xh, yh, wh = xa.cpu().numpy(), ya.cpu().numpy(), w.cpu().numpy()
+        want_p = truth.csd(xh, yh, n, hop, n, wh, "reflect", True, 0.37)
+        want_c = truth.coherence(xh, yh, n, hop, n, wh, "reflect")
+        aligned_p, aligned_c = plan.csd(xa, ya, True, 0.37), plan.coherence(xa, ya)
+        for name, x, y in (("x aligned, y odd", xa, yo), ("x odd, y aligned", xo, ya), ("both odd", xo, yo)):
+            got_p, got_c = plan.csd(x, y, True, 0.37), plan.coherence(x, y)
+            ep, ec = rel_l2(got_p.cpu().numpy(), want_p), rel_l2(got_c.cpu().numpy(), want_c)
+            print(f"csd odd input {real} n_fft={n} fusion={fusion} {name}: csd err {ep:.3g} tol {tol(plan, real):.3g} "
+                  f"coherence err {ec:.3g} tol {tol_coherence(plan, real):.3g}")
+            assert ep <= tol(plan, real) and ec <= tol_coherence(plan, real), (real, n, fusion, name, ep, ec)
+            assert torch.equal(torch.view_as_real(got_p), torch.view_as_real(aligned_p)) and torch.equal(got_c, aligned_c), (real, n, fusion, name)
+        got_p, got_c = plan.csd(xo, xo, True, 0.37), plan.coherence(xo, xo)
+        ep = rel_l2(got_p.cpu().numpy(), truth.csd(xh, xh, n, hop, n, wh, "reflect", True, 0.37))
+        ec = float(np.max(np.abs(got_c.cpu().numpy().astype(np.float64) - 1)))
+        print(f"csd odd input {real} n_fft={n} fusion={fusion} y is x: csd err {ep:.3g} tol {tol(plan, real):.3g} "
+              f"max |coherence - 1| {ec:.3g} tol {tol_coherence(plan, real):.3g}")
+        assert ep <= tol(plan, real) and ec <= tol_coherence(plan, real), (real, n, fusion, ep, ec)
+        assert torch.equal(torch.view_as_real(got_p), torch.view_as_real(plan.csd(xa, xa, True, 0.37))), (real, n, fusion, "y is x")
+        assert torch.equal(got_c, plan.coherence(xa, xa)), (real, n, fusion, "y is x")
+        assert all(torch.equal(h, b) for h, b in zip(holders, before)), "a call modified an input"
 
 
 @pytest.mark.parametrize("real", ["f32", "f64"])

@@ -1,6 +1,7 @@
 """The spectrogram handle on the MI355X: fourier_hip_spectrogram_* through fourier_amd.Spectrogram and spectrogram / welch on torch
 tensors, against tests/spectrogram_truth.py (f64 numpy on the rounded input).  The CPU twin is tests/test_spectrogram_emu.py (it also
-covers the argument checks, the chunk walks and the allocation-free property after reserve).
+covers the argument checks and the allocation-free property after reserve); the chunk and row-group walks under a small scratch bound
+run on the MI355X in tests/test_gpu_chunks.py, through the experiments library.
 
 Tolerance, relative L2 over the whole output on white Gaussian input (no bin near zero in norm): twice the forward tolerance
 tests/test_gpu_stft.py's tol() gives the same inner plan and precision.  d|X|^2 = 2 Re(conj X dX) makes the relative error of a power
@@ -63,13 +64,13 @@ def length_for(frames, n_fft, hop, pad_mode, extra):
     return (frames - 1) * hop + extra + (n_fft if pad_mode == "none" else 0)
 
 
-def check(torch, fa, real, n_fft, hop, pad_mode="reflect", extra=3, batch=3, win_length=None):
-    """Frames per row = tile + 3: the last tile of every row is partly empty (Welch) and tiles straddle rows (spectrogram).  Both
+def check(torch, fa, real, n_fft, hop, pad_mode="reflect", extra=3, batch=3, win_length=None, frames=None):
+    """Frames per row = tile + 3 unless given: the last tile of every row is partly empty (Welch) and tiles straddle rows (spectrogram).  Both
     "fusion" values, magnitude and power into a buffer that starts on an odd element with a sentinel on both sides, Welch with the
     fold against the truth and without it against the mean of the handle's own power spectrogram."""
     plan = make(fa, real, n_fft, hop, win_length, pad_mode)
     dt = rdtype(torch, real)
-    frames = cols(real, n_fft) + 3
+    frames = cols(real, n_fft) + 3 if frames is None else frames
     length = length_for(frames, n_fft, hop, pad_mode, extra)
     g = torch.Generator(device="cuda").manual_seed(n_fft + hop + length)
     w = 0.5 + torch.rand(plan.win_length(), dtype=dt, device="cuda", generator=g)
@@ -125,6 +126,62 @@ def test_fused_shapes(torch, fa, real):
         check(torch, fa, real, n, n // 4, "constant", extra=5)       # zero padding, an odd length
         check(torch, fa, real, n, n // 4, "none", extra=6)           # no padding: every frame interior
     check(torch, fa, real, 256, 64, "reflect", extra=2, win_length=200)
+
+
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_more_workgroups_than_xcds(torch, fa, real):
+    """6 tiles + 3 frames a row, batch 3: the spectrogram launches ceil(3 * (6 tile + 3) / tile) = 19 workgroups (20 at a tile of 8
+    frames, n_fft = 2048) and Welch 3 * 7 = 21, all above 8 and no multiple of 8 -- the workgroup-to-block map (real_xcd_block) gives the first XCDs one block more than the rest,
+    and the tile-to-row division (real_div) runs on blocks past the eighth.  check()'s assertions, with pairs of reals (even rows) and
+    single reals (an odd length)."""
+    for n in (256, largest_fused(real)):
+        frames = 6 * cols(real, n) + 3
+        forward_wgs, welch_wgs = -(-3 * frames // cols(real, n)), 3 * -(-frames // cols(real, n))
+        assert forward_wgs == (20 if cols(real, n) == 8 else 19) and welch_wgs == 21
+        assert all(wgs > 8 and wgs % 8 != 0 for wgs in (forward_wgs, welch_wgs))
+        for pad_mode, extra in (("reflect", 2), ("none", 5)):
+            plan = check(torch, fa, real, n, n // 4, pad_mode, extra=extra, frames=frames)
+            plan.set_option("fusion", 1)
+            assert plan.describe().startswith("spectrogram fused rows, welch fused rows"), plan.describe()
+
+
+@pytest.mark.parametrize("fusion", [1, 0])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_input_on_an_odd_element(torch, fa, real, fusion):
+    """tests/test_gpu_stft.py's test of the same name for this handle.  An even hop, padding and row length: only the base address
+    decides whether the fused kernels load pairs of reals.  Rows that start one element into their allocation against the truth, and
+    bit-equal to what the same handle gives from an aligned copy of them; the input buffer itself untouched."""
+    dt = rdtype(torch, real)
+    for n in (256, largest_fused(real)):
+        hop, batch = n // 4, 3
+        frames = cols(real, n) + 3
+        length = length_for(frames, n, hop, "reflect", 2)
+        assert hop % 2 == 0 and length % 2 == 0
+        g = torch.Generator(device="cuda").manual_seed(n + fusion)
+        holder = torch.randn(batch * length + 2, dtype=dt, device="cuda", generator=g)
+        before = holder.clone()
+        x = holder[1:-1].view(batch, length)
+        xa = x.clone()
+        assert x.data_ptr() % (2 * x.element_size()) != 0 and xa.data_ptr() % (2 * x.element_size()) == 0
+        plan = make(fa, real, n, hop)
+        w = 0.5 + torch.rand(n, dtype=dt, device="cuda", generator=g)
+        plan.set_window(w)
+        plan.set_option("fusion", fusion)
+        assert plan.describe().startswith("spectrogram fused rows" if fusion else "spectrogram composed"), plan.describe()
+        assert plan.frames(length) == frames
+        xh, wh = xa.cpu().numpy(), w.cpu().numpy()
+        for power, normalized in ((2, False), (1, True)):
+            got, aligned = plan.forward(x, power, normalized), plan.forward(xa, power, normalized)
+            err = rel_l2(got.cpu().numpy(), truth.spectrogram(xh, n, hop, n, wh, "reflect", power, normalized))
+            print(f"spectrogram odd input {real} n_fft={n} fusion={fusion} power={power}: err {err:.3g} tol {tol(plan, real):.3g}")
+            assert err <= tol(plan, real), (real, n, fusion, power, err)
+            assert torch.equal(got, aligned), (real, n, fusion, power)
+        got, aligned = plan.welch(x, True, 0.37), plan.welch(xa, True, 0.37)
+        err = rel_l2(got.cpu().numpy(), truth.welch(xh, n, hop, n, wh, "reflect", True, 0.37))
+        print(f"welch odd input {real} n_fft={n} fusion={fusion}: err {err:.3g} tol {tol(plan, real):.3g}")
+        assert err <= tol(plan, real), (real, n, fusion, err)
+        assert torch.equal(got, aligned), (real, n, fusion, "welch")
+        assert torch.equal(holder, before), "a call modified its input"
 
 
 @pytest.mark.parametrize("real", ["f32", "f64"])

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import chunk_walks
 import spectrogram_truth as truth
 from helpers import rel_l2
 
@@ -187,6 +188,24 @@ def test_chunk_walks_equal_the_unchunked_result(fa, monkeypatch):
     assert np.array_equal(welch(one, xx), welch(big, xx))
     one.set_option("fusion", 0)  # and one frame per chunk on the composed route
     assert rel_l2(welch(one, xx), truth.welch(xx, 256, 64, pad_mode="reflect")) <= tol(one, "f64") / 2
+
+
+@pytest.mark.parametrize("n_fft", chunk_walks.N_FFTS)
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_chunk_walks_at_two_slots_a_row(fa, monkeypatch, real, n_fft):
+    """tests/chunk_walks.py's cases, the ones tests/test_gpu_chunks.py runs on the MI355X: 64 frames a row under bounds of 32, 64 and 96
+    frames (every chunk ends on a slot boundary: bit-equal to the unbounded handle) and 35 frames a row under bounds of 1 ... 40 frames
+    (chunks that end inside a slot: the re-associated sum within 32 eps of the truth's norm)."""
+    chunk_walks.spectrogram_chunks(chunk_walks.HostApi(fa, monkeypatch), real, n_fft)
+    chunk_walks.print_worst()
+
+
+@pytest.mark.parametrize("n_fft,fused", [(64, False), (250, False), (63, False), (256, True)])
+@pytest.mark.parametrize("real", ["f32", "f64"])
+def test_row_groups(fa, monkeypatch, real, n_fft, fused):
+    """A batch of five in groups of one row and of 2, 2 and 1 rows through one partials buffer (tests/chunk_walks.py)."""
+    chunk_walks.welch_groups(chunk_walks.HostApi(fa, monkeypatch), real, n_fft, fused)
+    chunk_walks.print_worst()
 
 
 @pytest.mark.parametrize("real", ["f32", "f64"])
