@@ -71,6 +71,11 @@ _HILBERT = ("fourier_hip_hilbert_", {  # analytic signal and envelope of real ro
     "create": (vp, [sz, ci]), "destroy": (None, [vp]), "size": (sz, [vp]),
     "analytic": (ci, [vp, vp, vp, sz, vp]), "envelope": (ci, [vp, vp, vp, sz, vp]),  # handle, d_in, d_out, batch, stream
     "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_CZT = ("fourier_hip_czt_", {  # chirp-z transform: n samples in, m points of a z-plane arc or spiral out
+    "create": (vp, [sz, sz, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ci, ci]),  # n, m, w_abs, w_turns, a_abs, a_turns, real_input, device
+    "destroy": (None, [vp]), "size": (sz, [vp]), "points": (sz, [vp]),
+    "transform": (ci, [vp, vp, vp, sz, vp]),  # handle, d_in, d_out, batch, stream
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -93,8 +98,9 @@ MDCT_SYMBOLS = list(_signatures(_MDCT))
 SPECTROGRAM_SYMBOLS = list(_signatures(_SPECTROGRAM))
 CSD_SYMBOLS = list(_signatures(_CSD))
 HILBERT_SYMBOLS = list(_signatures(_HILBERT))
+CZT_SYMBOLS = list(_signatures(_CZT))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -104,7 +110,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

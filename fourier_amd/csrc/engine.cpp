@@ -23,6 +23,7 @@
 #include "spectrogram_plan.h"
 #include "csd_plan.h"
 #include "hilbert_plan.h"
+#include "czt_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -469,6 +470,31 @@ FOURIER_DEFINE_CSD_ABI(double, double)
 
 FOURIER_DEFINE_HILBERT_ABI(float, float)
 FOURIER_DEFINE_HILBERT_ABI(double, double)
+
+// chirp-z transform and zoom FFT (fourier_hip_czt_*)
+#define FOURIER_DEFINE_CZT_ABI(T, SUFFIX)                                                                        \
+  FOURIER_DEFINE_HANDLE_ABI(czt, fourier_czt_##SUFFIX, CztPlan<T>, SUFFIX)                                       \
+  extern "C" fc::fourier_czt_##SUFFIX* fourier_hip_czt_create_##SUFFIX(size_t n, size_t m, double w_abs, double w_turns, double a_abs, \
+                                                                       double a_turns, int real_input, int device) { \
+    return (fc::fourier_czt_##SUFFIX*)create_handle<CztPlan<T>>(n, m, w_abs, w_turns, a_abs, a_turns, real_input != 0, device); \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_czt_size_##SUFFIX(const fc::fourier_czt_##SUFFIX* h) {                           \
+    return h ? ((const CztPlan<T>*)h)->size() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_czt_points_##SUFFIX(const fc::fourier_czt_##SUFFIX* h) {                         \
+    return h ? ((const CztPlan<T>*)h)->points() : 0;                                                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_czt_transform_##SUFFIX(const fc::fourier_czt_##SUFFIX* h, const void* d_in, void* d_out, size_t batch, \
+                                                    void* stream) {                                              \
+    const CztPlan<T>* p = (const CztPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->transform(d_in, d_out, batch, (hipStream_t)stream); });                    \
+  }                                                                                                              \
+  extern "C" int fourier_hip_czt_set_option_##SUFFIX(fc::fourier_czt_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<CztPlan<T>>(h, key, v);                                                             \
+  }
+
+FOURIER_DEFINE_CZT_ABI(float, float)
+FOURIER_DEFINE_CZT_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -195,6 +195,7 @@ static inline StftArgs& frame_block(CsdArgs& a) { return a.f; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*HilbertKernel)(HilbertArgs);
+typedef void (*CztKernel)(CztArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -298,6 +299,10 @@ template <typename T> struct Real {};
   /* plans of 2^11 ... 2^15 (hilbert_small_kernel); the sweeps of the composed route, which = HILBERT_EXPAND / HILBERT_ABS */ \
   bool get_hilbert_small_kernel(Real<T>, int k, bool envelope, KernelInfo& info);                                      \
   HilbertKernel get_hilbert_kernel(Real<T>, int which);                                                                \
+  /* kernels_czt.cpp: the chirp-z transform of complex or real rows in one launch on the same shapes (czt_small_kernel); the end */ \
+  /* sweeps of the composed route, which = CZT_IN / CZT_OUT */                                                          \
+  bool get_czt_small_kernel(Real<T>, int k, bool real_input, KernelInfo& info);                                        \
+  CztKernel get_czt_kernel(Real<T>, int which);                                                                        \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

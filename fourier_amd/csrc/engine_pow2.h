@@ -291,6 +291,34 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
   }
 
+  // The chirp-z transform in one launch (czt_small_kernel; the chirp-z handle): conv_small_kernel's shapes and tables; one kernel for
+  // complex input rows, one for real ones.
+  bool enable_czt_small(bool real_input) {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    KernelInfo& k = czt_small_[real_input ? 1 : 0];
+    if (k.fn) return true;
+    if (!get_czt_small_kernel(Real<T>{}, ilog2(n_), real_input, k)) return false;
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    set_smem_attribute(k);
+    return true;
+  }
+  // in: `batch` rows of n values (complex, or reals); out: rows of m complex values, apart from the input; n + m - 1 <= n_.  atab: n
+  // entries, btab: m entries, htab: n_ entries in spectrum order with the inverse's 1 / n_ folded in
+  void run_czt_small(const void* in, void* out, size_t batch, uint32_t n, uint32_t m, const void* atab, const void* btab, const void* htab,
+                     bool real_input, hipStream_t stream, unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    const KernelInfo& k = czt_small_[real_input ? 1 : 0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.mul = htab; a.cz_a = atab; a.cz_b = btab; a.cz_n = n; a.cz_m = m;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
+  }
+
   // The fused frame routes of the STFT, MDCT, spectrogram and cross-spectrum handles (stft_rows_kernel, mdct_rows_kernel,
   // spectrogram_rows_kernel, csd_rows_kernel; stft_plan.h, mdct_plan.h, spectrogram_plan.h, csd_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
   // is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
@@ -714,6 +742,7 @@ template <typename T> class Pow2Engine {
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
+  KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
   std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel> frame_rows_;
   FusedInfo fused_;

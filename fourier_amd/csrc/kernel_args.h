@@ -67,6 +67,11 @@ struct PassArgs {
   uint32_t lc_nb;           // blocks per row
   uint32_t lc_wpr;          // workgroups per row: lc_nb, real data (lc_nb + 1) / 2
   uint32_t lc_m, lc_l;      // w / lc_wpr = (umulhi(w, lc_m) + w) >> lc_l
+  // czt_small_kernel (CztPlan, czt_plan.h): rows of cz_n values in (complex, or reals), rows of cz_m complex values out; the input is
+  // multiplied by cz_a (cz_n entries), the result by cz_b (cz_m entries); `mul` is the one table H of n entries
+  const void* cz_a;
+  const void* cz_b;
+  uint32_t cz_n, cz_m;
 };
 
 
@@ -344,6 +349,22 @@ struct HilbertArgs {
   uint32_t div_m, div_l;      // idx / n = (umulhi(idx, div_m) + idx) >> div_l
   uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
   double scale;               // the inverse's 1 / n, computed in T
+};
+
+// ---- chirp-z transform (kernels_czt.h; CztPlan, czt_plan.h): the end sweeps of the composed route, one lane per element of the
+// output side over a flat index; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of the work array per launch).
+// czt_in_kernel: rows of n values x (complex, or reals where `real`) -> rows of L = 2^l_shift complex values x[j] A[j], zeros from n on.
+// czt_out_kernel: rows of L complex values y -> rows of m complex values y[k] B[k].
+enum { CZT_IN = 0, CZT_OUT = 1 };
+struct CztArgs {
+  const void* in; void* out;
+  const void* tab;            // A (n entries) or B (m entries)
+  uint32_t n, m;              // values per user row: in, out
+  uint32_t l_shift;           // log2 of the work row
+  uint32_t total;             // rows * L (in) or rows * m (out)
+  uint32_t div_m, div_l;      // out: idx / m = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  int real;                   // in: the user rows are reals
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -598,6 +598,21 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_hilbert_small(d_in, d_out, batch, envelope, stream, nxcd_);
   }
 
+  // ---- the hook of the chirp-z handle (CztPlan, czt_plan.h); exec() is not affected.  A one-launch two-level plan of L points
+  // (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n values (complex, or reals) in one launch of czt_small_kernel: rows of m complex
+  // values out, apart from the input, n + m - 1 <= L.  The tables are the caller's: A (n entries), B (m entries), H (L entries, spectrum
+  // order, 1 / L folded in).  The caller keeps `batch` below 2^31.
+  bool enable_czt(bool real_input) {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_czt_small(real_input);
+  }
+  void exec_czt(const void* d_in, void* d_out, size_t batch, size_t n, size_t m, const void* atab, const void* btab, const void* htab,
+                bool real_input, hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_czt_small(d_in, d_out, batch, (uint32_t)n, (uint32_t)m, atab, btab, htab, real_input, stream, nxcd_);
+  }
+
   // ---- the hooks of the frame handles (StftPlan, MdctPlan, SpectrogramPlan), selected by the kernels' argument block (StftArgs,
   // MdctArgs, SpectrogramArgs); exec() is not affected.  A plan of h points that is one whole-row pass runs the frames of n = 2h samples in
   // one launch of the family's rows kernel (kernels_frames.h): fn[which] on `groups` workgroups of frame_cols() frames, 0: those that

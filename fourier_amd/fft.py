@@ -1265,6 +1265,135 @@ def envelope(x, dim=-1, out=None):
     return _hilbert(x, None, dim, out, False)
 
 
+class Czt(_Handle):
+    """Batched chirp-z transform (include/fourier.h, fourier_hip_czt_*) on device memory: of rows of n values x (complex, or reals with
+    real_input=True) the m values X[k] = sum_j x[j] a**-j w**(j k), with w = w_abs exp(2 pi i w_turns) and a = a_abs exp(2 pi i a_turns)
+    -- scipy.signal.czt(x, m, w, a) along the last axis.  The angles are in TURNS; w_turns=None means -1/m (with n == m, a = 1: the DFT)."""
+
+    _prefix = "fourier_hip_czt_"
+    _destroy = "fourier_hip_czt_destroy"
+
+    def __init__(self, n, m, w_abs=1.0, w_turns=None, a_abs=1.0, a_turns=0.0, real="f32", real_input=False, device=-1):
+        if int(n) < 1 or int(m) < 1:
+            raise ValueError(f"need n >= 1 and m >= 1, got {n}, {m}")
+        if w_turns is None:
+            w_turns = -1.0 / int(m)
+        pars = tuple(float(v) for v in (w_abs, w_turns, a_abs, a_turns))
+        if not all(np.isfinite(pars)) or pars[0] <= 0 or pars[2] <= 0:
+            raise ValueError(f"need finite parameters and positive magnitudes, got w_abs, w_turns, a_abs, a_turns = {pars}")
+        self._create(real, f"chirp-z plan of {n} samples and {m} points", int(n), int(m), *pars, int(bool(real_input)), int(device))
+        self._n, self._m, self.real_input = int(n), int(m), bool(real_input)
+
+    def size(self):
+        return self._n
+
+    def points(self):
+        return self._m
+
+    def set_option(self, key, value):
+        """"fusion": 1 = the one-launch kernel where max(2048, next_pow2(n + m - 1)) is at most 2^15 (f64: 2^14), 0 = the composed route
+        (chirp sweep, convolution of next_pow2(n + m - 1) points, chirp sweep).  Default: 1 where next_pow2(n + m - 1) >= 2048 and the
+        kernel exists, else 0."""
+        self._call("set_option", key.encode(), int(value))
+
+    def transform_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of n values at d_in -> `batch` rows of m complex values at d_out (no overlap), enqueued on `stream`."""
+        self._call("transform", d_in, d_out, int(batch), stream)
+
+    def transform(self, x, out=None):
+        """Contiguous (..., n) CUDA tensor, complex (real_input: float) of the handle's precision -> a new complex (..., m) tensor, or
+        `out` (which may not overlap `x`), on the current stream."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(x, rdt if self.real_input else cdt)
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        shape = tuple(x.shape[:-1]) + (self._m,)
+        if out is None:
+            out = torch.empty(shape, dtype=cdt, device=x.device)
+        else:
+            _require_out(out, shape, cdt, x.device)
+        batch = x.numel() // self._n
+        if batch:
+            self.transform_ptr(x.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+
+def create_czt_f32(n, m, w_abs=1.0, w_turns=None, a_abs=1.0, a_turns=0.0, real_input=False, device=-1):
+    return Czt(n, m, w_abs, w_turns, a_abs, a_turns, "f32", real_input, device)
+
+
+def create_czt_f64(n, m, w_abs=1.0, w_turns=None, a_abs=1.0, a_turns=0.0, real_input=False, device=-1):
+    return Czt(n, m, w_abs, w_turns, a_abs, a_turns, "f64", real_input, device)
+
+
+def _czt(x, m, w_abs, w_turns, a_abs, a_turns, dim, out):
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None):
+        raise TypeError("expected a CUDA float32 / float64 / complex64 / complex128 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    d = _normalise_dims(x.dim(), (dim,))[0]
+    n = int(x.shape[d])
+    m = n if m is None else int(m)
+    if n < 1 or m < 1:
+        raise ValueError(f"need n >= 1 and m >= 1, got {n}, {m}")
+    real, real_input = _precision(x.dtype)
+    shape = tuple(x.shape[:d]) + (m,) + tuple(x.shape[d + 1:])
+    cdt = _torch_dtypes(real)[1]
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == cdt and tuple(out.shape) == shape and out.device == x.device):
+        raise TypeError(f"out must be a CUDA {_names((cdt,))} tensor of shape {shape} on the input's device")
+    if w_turns is None:
+        w_turns = -1.0 / m
+    plan = _cached_plan(Czt, n, m, float(w_abs), float(w_turns), float(a_abs), float(a_turns), real, real_input, int(_device_index(x)))
+    if d == x.dim() - 1 and x.is_contiguous() and (out is None or out.is_contiguous()):
+        return plan.transform(x, out)
+    # any other dim or layout: a torch copy that makes the axis last and contiguous
+    res = plan.transform(x.movedim(d, -1).contiguous()).movedim(-1, d)
+    if out is None:
+        return res.contiguous()
+    out.copy_(res)
+    return out
+
+
+def _polar_turns(z):
+    """a complex (or real) number as (magnitude, angle in turns)"""
+    z = complex(z)
+    return abs(z), np.angle(z) / (2.0 * np.pi)
+
+
+def czt(x, m=None, w=None, a=1 + 0j, dim=-1, out=None):
+    """scipy.signal.czt(x, m, w, a, axis=dim) of a float or complex CUDA tensor on the current stream: m points (default: the axis'
+    length) of the z-transform at z = a w**-k; w=None means exp(-2 pi i / m), with a = 1 the DFT.  Complex `w` and `a` are converted with
+    abs and angle / (2 pi); a caller who has the angles in turns keeps their precision with the Czt handle or zoom_fft.  Returns a new
+    complex tensor or `out`.  Only the last dimension of a contiguous tensor is native (one cached Czt handle per parameter tuple); any
+    other `dim` is moved last with a torch copy."""
+    w_abs, w_turns = (1.0, None) if w is None else _polar_turns(w)
+    a_abs, a_turns = _polar_turns(a)
+    return _czt(x, m, w_abs, w_turns, a_abs, a_turns, dim, out)
+
+
+def zoom_fft(x, fn, m=None, fs=2, endpoint=False, dim=-1, out=None):
+    """scipy.signal.zoom_fft(x, fn, m, fs=fs, endpoint=endpoint, axis=dim): m points (default: the axis' length) of the DFT between the
+    frequencies f1 and f2 at sample rate fs -- fn = f2 (f1 = 0) or the pair (f1, f2); endpoint=True includes f2.  The angles go to the
+    handle in turns, -(f2 - f1) / (fs m) and f1 / fs, without passing through exp and atan2."""
+    f1, f2 = (0.0, float(fn)) if np.ndim(fn) == 0 else (float(fn[0]), float(fn[1]))
+    if np.ndim(fn) != 0 and len(fn) != 2:
+        raise ValueError("fn must be a scalar or a pair (f1, f2)")
+    if not _is_torch(x):
+        raise TypeError("expected a CUDA float32 / float64 / complex64 / complex128 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    points = int(x.shape[_normalise_dims(x.dim(), (dim,))[0]]) if m is None else int(m)
+    if points < 1 or (endpoint and points < 2):
+        raise ValueError(f"need m >= 1 (with endpoint: m >= 2), got {points}")
+    fs = float(fs)
+    w_turns = -(f2 - f1) / (fs * ((points - 1) if endpoint else points))
+    return _czt(x, points, 1.0, w_turns, 1.0, f1 / fs, dim, out)
+
+
 class Mdct(_Handle):
     """Batched modified discrete cosine transform and its inverse (include/fourier.h, fourier_hip_mdct_*) on device memory: rows of
     `length` reals <-> frames x n reals per row, FRAME-MAJOR (frame f of row b at element offset (b * frames + f) * n).  A frame is 2n

@@ -1002,6 +1002,68 @@ const char *fourier_hip_hilbert_describe_double(const FOURIER_STRUCT fourier_hil
 int fourier_hip_hilbert_last_status_float(const FOURIER_STRUCT fourier_hilbert_float *);
 int fourier_hip_hilbert_last_status_double(const FOURIER_STRUCT fourier_hilbert_double *);
 
+/* ---------------- chirp-z transform and zoom FFT (extension; the reference has only the DFT special case) ----------
+ * Of `batch` rows of n >= 1 values on DEVICE memory, row b at element offset b*n -- interleaved COMPLEX values, or REALS T where the
+ * handle was created with real_input = 1 --, with w = w_abs exp(2 pi i w_turns) and a = a_abs exp(2 pi i a_turns):
+ *   X[b][k] = sum_{j=0}^{n-1} x[b][j] a^(-j) w^(j k),   k = 0 .. m-1,
+ * `batch` rows of m interleaved complex values out, row b at element offset b*m: scipy.signal.czt(x, m, w, a) along the last axis.
+ * The four parameters are doubles in polar form, the angles in TURNS, fixed at create: a zoom FFT of m points from f1 to f2 at sample
+ * rate fs passes w_turns = -(f2 - f1) / (fs m), a_turns = f1 / fs, w_abs = a_abs = 1; the DFT of n points is m = n, w_turns = -1/n.
+ * Algorithm: Bluestein's identity j k = (j^2 + k^2 - (k - j)^2) / 2, a circular convolution of L >= n + m - 1 points, L a power of
+ * two.  Host tables, evaluated in double and cast to T, every phase reduced to one turn first, every magnitude as exp(log(.) * .):
+ *   c(q) = w_abs^(q/2) exp(2 pi i frac(w_turns q / 2));  A[j] = a_abs^-j exp(-2 pi i frac(a_turns j)) c(j^2), j < n;  B[k] = c(k^2), k < m;
+ *   v[i] = 1 / c(i^2), i = -(n-1) .. m-1, stored at i mod L;  H = FFT_L(v) / L;   X = B (.) ifft_L(fft_L(x (.) A, zero-padded) (.) H)[0..m).
+ * create gives NULL for n == 0, m == 0, a parameter that is not finite, w_abs <= 0 or a_abs <= 0 (invalid), for n + m - 1 > 2^26, and
+ * for a spiral so tight that an entry of A, B or H is not finite or is zero after the cast to T (unsupported).  On a spiral the error
+ * of the result grows with R, the largest over the smallest magnitude among A and B; R = 1 on the unit circle.
+ * A NULL pointer, an input not aligned to one input value (complex rows: 2*sizeof(T), real rows: sizeof(T)), an output not aligned
+ * to 2*sizeof(T), or ANY overlap of input and output give FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.
+ * Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_czt_describe_* begins with the route's name):
+ *   "czt one-launch"  L = max(2048, next_pow2(n + m - 1)) <= 2^15 (double: 2^14): load n, (.) A, FFT, (.) H, inverse FFT, (.) B, store m
+ *                     in ONE launch on register-resident data; no scratch.
+ *   "czt composed"    every n, m, L = next_pow2(n + m - 1): one sweep x (.) A -> rows of L in the plan's scratch, the convolution with H
+ *                     in place there (the convolution handle's one-launch or fused-pass route where the L-point plan has one, else
+ *                     forward transform, product, inverse), one sweep (.) B -> the first m of each row into the caller's output.
+ * Option "fusion" (fourier_hip_czt_set_option_*): 1 = the one-launch route where the lengths have one, 0 = the composed route.  The
+ * DEFAULT is 1 where next_pow2(n + m - 1) >= 2048, so that both routes run the same L (there the one-launch route was measured at about
+ * half the composed route's time), and 0 below, where the composed route convolves fewer points and nothing is measured.  The plan owns a scratch of at most 1 GiB (never less than one
+ * row) and walks larger batches in chunks of it; the first call with a batch larger than any before allocates it unless
+ * fourier_hip_czt_reserve_* was called for at least that batch.  A NULL handle gives FOURIER_HIP_INVALID_ARGUMENT, 0 from
+ * fourier_hip_czt_size_* / _points_* and "" from fourier_hip_czt_describe_*.  Handles are Send, not Sync, like the complex ones;
+ * status of the last call: fourier_hip_czt_last_status_*. */
+struct fourier_czt_float;
+struct fourier_czt_double;
+
+/* NULL on failure. */
+struct fourier_czt_float *fourier_hip_czt_create_float(FOURIER_SIZE_TYPE n, FOURIER_SIZE_TYPE m, double w_abs, double w_turns,
+                                                       double a_abs, double a_turns, int real_input, int device);
+struct fourier_czt_double *fourier_hip_czt_create_double(FOURIER_SIZE_TYPE n, FOURIER_SIZE_TYPE m, double w_abs, double w_turns,
+                                                         double a_abs, double a_turns, int real_input, int device);
+/* NULL is a no-op. */
+void fourier_hip_czt_destroy_float(FOURIER_STRUCT fourier_czt_float *);
+void fourier_hip_czt_destroy_double(FOURIER_STRUCT fourier_czt_double *);
+/* n, the values of an input row; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_czt_size_float(const FOURIER_STRUCT fourier_czt_float *);
+FOURIER_SIZE_TYPE fourier_hip_czt_size_double(const FOURIER_STRUCT fourier_czt_double *);
+/* m, the values of an output row; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_czt_points_float(const FOURIER_STRUCT fourier_czt_float *);
+FOURIER_SIZE_TYPE fourier_hip_czt_points_double(const FOURIER_STRUCT fourier_czt_double *);
+int fourier_hip_czt_transform_float(const FOURIER_STRUCT fourier_czt_float *, const void *d_in, void *d_out,
+                                    FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_czt_transform_double(const FOURIER_STRUCT fourier_czt_double *, const void *d_in, void *d_out,
+                                     FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_czt_reserve_float(const FOURIER_STRUCT fourier_czt_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_czt_reserve_double(const FOURIER_STRUCT fourier_czt_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed route, 1 = the one-launch route where it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_czt_set_option_float(FOURIER_STRUCT fourier_czt_float *, const char *key, long long value);
+int fourier_hip_czt_set_option_double(FOURIER_STRUCT fourier_czt_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_czt_describe_float(const FOURIER_STRUCT fourier_czt_float *);
+const char *fourier_hip_czt_describe_double(const FOURIER_STRUCT fourier_czt_double *);
+int fourier_hip_czt_last_status_float(const FOURIER_STRUCT fourier_czt_float *);
+int fourier_hip_czt_last_status_double(const FOURIER_STRUCT fourier_czt_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1412,6 +1474,47 @@ template <typename T> struct hilbert;
 FOURIER_DEFINE_CXX_HILBERT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_HILBERT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_HILBERT_WRAPPER
+
+/* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
+template <typename T> struct czt;
+
+#define FOURIER_DEFINE_CXX_CZT_WRAPPER(T, SUFFIX)                                                  \
+  template <> struct czt<T> {                                                                      \
+    /* w = w_abs exp(2 pi i w_turns), a = a_abs exp(2 pi i a_turns) */                             \
+    czt(std::size_t n, std::size_t m, double w_abs, double w_turns, double a_abs = 1.0,            \
+        double a_turns = 0.0, bool real_input = false, int device = -1)                            \
+        : impl(::fourier::c::fourier_hip_czt_create_##SUFFIX(n, m, w_abs, w_turns, a_abs, a_turns, \
+                                                             real_input ? 1 : 0, device),         \
+               ::fourier::c::fourier_hip_czt_destroy_##SUFFIX) {}                                  \
+    czt() = delete;                                                                                \
+    czt(const czt &) = delete;                                                                     \
+    czt(czt &&) = default;                                                                         \
+    czt &operator=(const czt &) = delete;                                                          \
+    czt &operator=(czt &&) = default;                                                              \
+    ~czt() = default;                                                                              \
+    std::size_t size() const { return ::fourier::c::fourier_hip_czt_size_##SUFFIX(impl.get()); }   \
+    std::size_t points() const { return ::fourier::c::fourier_hip_czt_points_##SUFFIX(impl.get()); }\
+    /* `batch` rows of n values -> rows of m complex values (no overlap) */                        \
+    int transform_device(const void *d_in, void *d_out, std::size_t batch, void *stream = nullptr) const {\
+      return ::fourier::c::fourier_hip_czt_transform_##SUFFIX(impl.get(), d_in, d_out, batch, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_czt_reserve_##SUFFIX(impl.get(), batch);                    \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_czt_set_option_##SUFFIX(impl.get(), key, value);            \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_czt_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_czt_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_czt_##SUFFIX,                                          \
+                      void (*)(::fourier::c::fourier_czt_##SUFFIX *)> impl;                        \
+  };
+FOURIER_DEFINE_CXX_CZT_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_CZT_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_CZT_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
