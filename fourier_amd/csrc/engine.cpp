@@ -24,6 +24,7 @@
 #include "csd_plan.h"
 #include "hilbert_plan.h"
 #include "czt_plan.h"
+#include "pfb_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -495,6 +496,49 @@ FOURIER_DEFINE_HILBERT_ABI(double, double)
 
 FOURIER_DEFINE_CZT_ABI(float, float)
 FOURIER_DEFINE_CZT_ABI(double, double)
+
+// polyphase filter bank channelizer (fourier_hip_pfb_*)
+#define FOURIER_DEFINE_PFB_ABI(T, SUFFIX)                                                                        \
+  extern "C" fc::fourier_pfb_##SUFFIX* fourier_hip_pfb_create_##SUFFIX(size_t channels, size_t taps, size_t hop, int real_input, int device) { \
+    return (fc::fourier_pfb_##SUFFIX*)create_handle<PfbPlan<T>>(channels, taps, hop, real_input, device);        \
+  }                                                                                                              \
+  extern "C" void fourier_hip_pfb_destroy_##SUFFIX(fc::fourier_pfb_##SUFFIX* h) { destroy_handle<PfbPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_pfb_describe_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) { return describe_handle<PfbPlan<T>>(h); } \
+  extern "C" int fourier_hip_pfb_last_status_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) { return last_status_of<PfbPlan<T>>(h); } \
+  extern "C" int fourier_hip_pfb_set_option_##SUFFIX(fc::fourier_pfb_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<PfbPlan<T>>(h, key, v);                                                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_pfb_channels_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) {                       \
+    return h ? ((const PfbPlan<T>*)h)->channels() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_pfb_taps_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) {                           \
+    return h ? ((const PfbPlan<T>*)h)->taps() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_pfb_hop_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) {                            \
+    return h ? ((const PfbPlan<T>*)h)->hop() : 0;                                                                \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_pfb_bins_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h) {                           \
+    return h ? ((const PfbPlan<T>*)h)->bins() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_pfb_frames_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h, size_t length) {          \
+    return h ? ((const PfbPlan<T>*)h)->frames(length) : 0;                                                       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_pfb_set_filter_##SUFFIX(fc::fourier_pfb_##SUFFIX* h, const void* d_filter, void* stream) { \
+    PfbPlan<T>* p = (PfbPlan<T>*)h;                                                                              \
+    return guarded_handle(p, [&] { p->set_filter(d_filter, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_pfb_reserve_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h, size_t length, size_t batch) { \
+    const PfbPlan<T>* p = (const PfbPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_pfb_forward_##SUFFIX(const fc::fourier_pfb_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                  size_t batch, void* stream) {                                  \
+    const PfbPlan<T>* p = (const PfbPlan<T>*)h;                                                                  \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, length, batch, (hipStream_t)stream); });              \
+  }
+
+FOURIER_DEFINE_PFB_ABI(float, float)
+FOURIER_DEFINE_PFB_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -175,9 +175,10 @@ typedef void (*StftKernel)(StftArgs);
 typedef void (*MdctKernel)(MdctArgs);
 typedef void (*SpectrogramKernel)(SpectrogramArgs);
 typedef void (*CsdKernel)(CsdArgs);
-// The fused frame route of a frame handle (STFT, MDCT, spectrogram, cross spectrum) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
+typedef void (*PfbKernel)(PfbArgs);
+// The fused frame route of a frame handle (STFT, MDCT, spectrogram, cross spectrum, polyphase filter bank) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
 // one shape.  STFT and MDCT have fn[0]; the spectrogram one per epilogue, fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL].
-// The cross spectrum has fn[0].  L == 0: none for that length
+// The cross spectrum has fn[0]; the filter bank fn[0] for complex rows (P = L channels) and fn[1] for real rows (P = 2 L).  L == 0: none for that length
 template <typename Args> struct FrameRowsKernel {
   void (*fn[4])(Args) = {nullptr, nullptr, nullptr, nullptr};
   int L = 0, CG = 0, NT = 0, COLS = 0;
@@ -187,11 +188,13 @@ typedef FrameRowsKernel<StftArgs> StftRowsKernel;
 typedef FrameRowsKernel<MdctArgs> MdctRowsKernel;
 typedef FrameRowsKernel<SpectrogramArgs> SpectrogramRowsKernel;
 typedef FrameRowsKernel<CsdArgs> CsdRowsKernel;
+typedef FrameRowsKernel<PfbArgs> PfbRowsKernel;
 // the part of a frame kernel's argument block that holds the frame geometry and the row core's stage tables
 static inline StftArgs& frame_block(StftArgs& a) { return a; }
 static inline MdctArgs& frame_block(MdctArgs& a) { return a; }
 static inline StftArgs& frame_block(SpectrogramArgs& a) { return a.f; }
 static inline StftArgs& frame_block(CsdArgs& a) { return a.f; }
+static inline PfbArgs& frame_block(PfbArgs& a) { return a; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*HilbertKernel)(HilbertArgs);
@@ -293,6 +296,10 @@ template <typename T> struct Real {};
   /* frame route for n_fft = 2 L on the whole-row kernel of length L                                                   */ \
   CsdKernel get_csd_kernel(Real<T>, int which);                                                                        \
   CsdRowsKernel get_csd_rows_kernel(Real<T>, int L);                                                                   \
+  /* kernels_pfb.cpp: the fold sweep of the polyphase filter bank handle's composed route; its fused frame routes on the */ \
+  /* whole-row kernel of length L: complex rows of P = L channels, real rows of P = 2 L                                */ \
+  PfbKernel get_pfb_kernel(Real<T>);                                                                                   \
+  PfbRowsKernel get_pfb_rows_kernel(Real<T>, int L);                                                                   \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_hilbert.cpp: the analytic signal or the envelope of real rows in one launch on the shapes of the two-level */ \
@@ -344,5 +351,6 @@ template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L,
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, MdctRowsKernel& k) { k = get_mdct_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, SpectrogramRowsKernel& k) { k = get_spectrogram_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, CsdRowsKernel& k) { k = get_csd_rows_kernel(r, L); }
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, PfbRowsKernel& k) { k = get_pfb_rows_kernel(r, L); }
 
 }  // namespace fourier_hip

@@ -319,9 +319,9 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
   }
 
-  // The fused frame routes of the STFT, MDCT, spectrogram and cross-spectrum handles (stft_rows_kernel, mdct_rows_kernel,
-  // spectrogram_rows_kernel, csd_rows_kernel; stft_plan.h, mdct_plan.h, spectrogram_plan.h, csd_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points,
-  // is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
+  // The fused frame routes of the STFT, MDCT, spectrogram, cross-spectrum and polyphase filter bank handles (stft_rows_kernel, mdct_rows_kernel,
+  // spectrogram_rows_kernel, csd_rows_kernel, pfb_rows_kernel / pfb_real_rows_kernel; stft_plan.h, mdct_plan.h, spectrogram_plan.h, csd_plan.h, pfb_plan.h), selected by the kernels' argument block: available when this plan, of h = n / 2 points
+  // (the filter bank's complex rows: of P points), is ONE whole-row pass and the family's translation unit holds its kernels on that pass's tile shape; they run on this plan's stage tables.
   template <typename Args> bool enable_frame_rows() {
     if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_ROWS) return false;
     FrameRowsKernel<Args>& slot = std::get<FrameRowsKernel<Args>>(frame_rows_);
@@ -744,7 +744,7 @@ template <typename T> class Pow2Engine {
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
   KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
-  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel> frame_rows_;
+  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel> frame_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

@@ -367,6 +367,26 @@ struct CztArgs {
   int real;                   // in: the user rows are reals
 };
 
+// ---- polyphase filter bank (kernels_pfb.h; PfbPlan, pfb_plan.h)
+// A frame is channels * taps values of a row (complex values, or reals where `real`), frame f of a row starts at value f * hop; there is
+// no padding, every frame lies inside its row.  The flat frame index, `first`, `total` and the multiply-high division are StftArgs'.
+// pfb_fold_kernel writes the `channels` folded values u[n] = sum_t filt[t * channels + n] x[f hop + t channels + n] of frame i of the
+// launch at out + i * channels (values of the input's kind); the fused kernels write frame i's bins at out + i * bins complex values.
+struct PfbArgs {
+  const void* in; void* out;
+  const void* filt;           // the prototype filter, channels * taps reals
+  const void* tw;             // fused, real rows: W_P^j, j <= P / 4 (real_untangle_twiddles)
+  const void* tw1; const void* tw2;  // fused: the row core's stage tables
+  uint64_t length;            // values per signal row
+  uint64_t total;             // frames of this launch
+  uint32_t frames;            // frames per signal row
+  uint32_t first;             // frame index (within row 0 of the launch) of item 0
+  uint32_t fr_m, fr_l;        // x / frames = (umulhi(x, fr_m) + x) >> fr_l
+  uint32_t channels, taps, hop;
+  int real;                   // fold sweep: the rows are reals
+  int pairs;                  // fused, real rows: every frame starts on an even element of a 2 * sizeof(T)-aligned row
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

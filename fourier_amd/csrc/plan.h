@@ -613,10 +613,10 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_czt_small(d_in, d_out, batch, (uint32_t)n, (uint32_t)m, atab, btab, htab, real_input, stream, nxcd_);
   }
 
-  // ---- the hooks of the frame handles (StftPlan, MdctPlan, SpectrogramPlan), selected by the kernels' argument block (StftArgs,
-  // MdctArgs, SpectrogramArgs); exec() is not affected.  A plan of h points that is one whole-row pass runs the frames of n = 2h samples in
-  // one launch of the family's rows kernel (kernels_frames.h): fn[which] on `groups` workgroups of frame_cols() frames, 0: those that
-  // cover the `total` frames of the block.
+  // ---- the hooks of the frame handles (StftPlan, MdctPlan, SpectrogramPlan, CsdPlan, PfbPlan), selected by the kernels' argument block
+  // (StftArgs, MdctArgs, SpectrogramArgs, CsdArgs, PfbArgs); exec() is not affected.  A plan of h points that is one whole-row pass runs the
+  // frames of n = 2h samples (PfbArgs: of P = 2h real or P = h complex channels, fn[1] / fn[0]) in one launch of the family's rows kernel
+  // (kernels_frames.h): fn[which] on `groups` workgroups of frame_cols() frames, 0: those that cover the `total` frames of the block.
   template <typename Args> bool enable_frames() {
     if (blu_ || !eng_) return false;
     DeviceGuard g(device_);

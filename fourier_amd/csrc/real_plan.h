@@ -41,7 +41,8 @@ template <typename T> class RealPlan : public HandleBase {
   bool even() const { return even_; }
   const Plan<T>& inner() const { return *inner_; }
   const void* twiddles() const { return tw_.p; }
-  // the fused frame route of the STFT / spectrogram handle (Args = StftArgs / SpectrogramArgs; stft_plan.h, spectrogram_plan.h): even N
+  // the fused frame route of the STFT / spectrogram / filter bank handle (Args = StftArgs / SpectrogramArgs / PfbArgs; stft_plan.h,
+  // spectrogram_plan.h, pfb_plan.h): even N
   // whose inner plan is one whole-row pass with a kernel for it
   template <typename Args> bool enable_frames() { return even_ && inner_->template enable_frames<Args>(); }
 

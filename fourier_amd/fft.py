@@ -1394,6 +1394,142 @@ def zoom_fft(x, fn, m=None, fs=2, endpoint=False, dim=-1, out=None):
     return _czt(x, points, 1.0, w_turns, 1.0, f1 / fs, dim, out)
 
 
+class Pfb(_Handle):
+    """Batched polyphase filter bank channelizer (include/fourier.h, fourier_hip_pfb_*) on device memory: of rows of `length` values
+    (complex, or reals with real_input=True), frames of channels * taps values every `hop` values are folded under a prototype filter onto
+    `channels` points and transformed: X[f, k] = sum_n (sum_t h[t P + n] x[f D + t P + n]) exp(-2 pi i k n / P).  Output frames x bins
+    complex per row, FRAME-MAJOR; bins = channels (complex rows) or channels // 2 + 1 (real rows).  No padding, no per-frame phase
+    rotation, no scale.  hop=None means channels (critically sampled).  The filter is set afterwards (set_filter; default all ones)."""
+
+    _prefix = "fourier_hip_pfb_"
+    _destroy = "fourier_hip_pfb_destroy"
+
+    def __init__(self, channels, taps, real="f32", hop=None, real_input=False, device=-1):
+        channels, taps = int(channels), int(taps)
+        hop = channels if hop is None else int(hop)
+        if channels < 1 or taps < 1 or hop < 1:
+            raise ValueError(f"need channels >= 1, taps >= 1 and hop >= 1, got {channels}, {taps}, {hop}")
+        self._create(real, f"filter bank plan of {channels} channels, {taps} taps, hop {hop}", channels, taps, hop, int(bool(real_input)),
+                     int(device))
+        self._p, self._t, self._hop, self.real_input = channels, taps, hop, bool(real_input)
+
+    def channels(self):
+        return self._p
+
+    def taps(self):
+        return self._t
+
+    def hop(self):
+        return self._hop
+
+    def bins(self):
+        return self._p // 2 + 1 if self.real_input else self._p
+
+    def frames(self, length):
+        """Frames of a row of `length` values; 0 where the length is invalid."""
+        return int(self._fn("frames")(self._h, int(length)))
+
+    def set_option(self, key, value):
+        """"fusion": 0 = the composed route, 1 = the fused one-launch route wherever it exists (the default)."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def reserve(self, length, batch):
+        """Later forward calls of at most `batch` rows of `length` values never allocate."""
+        self._call("reserve", int(length), int(batch))
+
+    def set_filter_ptr(self, d_filter, stream=0):
+        """channels() * taps() reals of the handle's precision at d_filter (0 / None: all ones).  Waits for `stream`."""
+        self._call("set_filter", d_filter or None, stream)
+
+    def forward_ptr(self, d_in, d_out, length, batch, stream=0):
+        """`batch` rows of `length` values at d_in -> batch x frames(length) x bins() complex at d_out, enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(length), int(batch), stream)
+
+    def set_filter(self, filter):
+        """A contiguous CUDA tensor of channels() * taps() reals of the handle's precision, shape (channels * taps,) or (taps, channels),
+        or None for all ones; on the current stream."""
+        if filter is None:
+            return self.set_filter_ptr(None)
+        _require_cuda(filter, _torch_dtypes(self.real)[0])
+        if tuple(filter.shape) not in ((self._p * self._t,), (self._t, self._p)):
+            raise ValueError(f"filter must have shape ({self._p * self._t},) or ({self._t}, {self._p}), got {tuple(filter.shape)}")
+        self.set_filter_ptr(filter.data_ptr(), _stream(filter))
+
+    def forward(self, x, out=None):
+        """Contiguous (..., length) CUDA tensor, complex (real_input: float) of the handle's precision -> a new (..., frames, bins)
+        complex tensor (frame-major), or `out` (which may not overlap `x`), on the current stream."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(x, rdt if self.real_input else cdt)
+        if x.dim() == 0:
+            raise ValueError("expected at least one dimension")
+        length = int(x.shape[-1])
+        fr = self.frames(length)
+        if fr == 0:
+            raise ValueError(f"a row of {length} values is too short for {self._p} channels x {self._t} taps")
+        shape = tuple(x.shape[:-1]) + (fr, self.bins())
+        if out is None:
+            out = torch.empty(shape, dtype=cdt, device=x.device)
+        else:
+            _require_out(out, shape, cdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), length, batch, _stream(x))
+        return out
+
+
+def create_pfb_f32(channels, taps, hop=None, real_input=False, device=-1):
+    return Pfb(channels, taps, "f32", hop, real_input, device)
+
+
+def create_pfb_f64(channels, taps, hop=None, real_input=False, device=-1):
+    return Pfb(channels, taps, "f64", hop, real_input, device)
+
+
+def pfb_channelize(x, filter, channels, hop=None, out=None):
+    """The polyphase filter bank of a CUDA tensor of shape (..., length) on the current stream: float32 / float64 rows (real input,
+    channels // 2 + 1 bins) or complex64 / complex128 rows (`channels` bins); `filter` holds channels * taps reals of the same
+    precision on the same device, shape (channels * taps,) or (taps, channels), or is None for all ones of one tap.  Returns
+    (..., frames, bins) complex, or `out`.  Leading dimensions fold into the batch.  Handles are cached per (channels, taps, hop, dtype,
+    device) and the filter is set on EVERY call; keep a Pfb to reuse one."""
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None):
+        raise TypeError("expected a CUDA float32 / float64 / complex64 / complex128 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    real, real_input = _precision(x.dtype)
+    channels = int(channels)
+    if channels < 1:
+        raise ValueError(f"need channels >= 1, got {channels}")
+    taps = 1
+    if filter is not None:
+        if not (_is_torch(filter) and filter.is_cuda and filter.dtype == _torch_dtypes(real)[0] and filter.device == x.device):
+            raise TypeError(f"filter must be a CUDA {_names((_torch_dtypes(real)[0],))} tensor on the input's device")
+        if filter.numel() == 0 or filter.numel() % channels or (filter.dim() == 2 and filter.shape[1] != channels) or filter.dim() not in (1, 2):
+            raise ValueError(f"filter must hold channels * taps values as (channels * taps,) or (taps, {channels}), got {tuple(filter.shape)}")
+        taps = filter.numel() // channels
+        filter = filter.contiguous()
+    p = _cached_plan(Pfb, channels, taps, real, channels if hop is None else int(hop), real_input, int(_device_index(x)))
+    p.set_filter(filter)
+    return p.forward(x.contiguous(), out)
+
+
+def pfb_prototype(channels, taps, dtype=None):
+    """The usual windowed-sinc prototype filter of a `channels`-channel bank with `taps` taps: sinc((n - (P T - 1) / 2) / P) *
+    hamming(P T)[n], n < P T, computed in float64 and rounded to `dtype` (a numpy dtype: a numpy array; a torch dtype: a CPU tensor;
+    default numpy float64)."""
+    P, T = int(channels), int(taps)
+    if P < 1 or T < 1:
+        raise ValueError(f"need channels >= 1 and taps >= 1, got {channels}, {taps}")
+    n = np.arange(P * T, dtype=np.float64)
+    h = np.sinc((n - (P * T - 1) / 2.0) / P) * np.hamming(P * T)
+    if dtype is not None and type(dtype).__module__.startswith("torch"):
+        import torch
+
+        return torch.from_numpy(h).to(dtype)
+    return h.astype(np.float64 if dtype is None else dtype)
+
+
 class Mdct(_Handle):
     """Batched modified discrete cosine transform and its inverse (include/fourier.h, fourier_hip_mdct_*) on device memory: rows of
     `length` reals <-> frames x n reals per row, FRAME-MAJOR (frame f of row b at element offset (b * frames + f) * n).  A frame is 2n

@@ -1064,6 +1064,75 @@ const char *fourier_hip_czt_describe_double(const FOURIER_STRUCT fourier_czt_dou
 int fourier_hip_czt_last_status_float(const FOURIER_STRUCT fourier_czt_float *);
 int fourier_hip_czt_last_status_double(const FOURIER_STRUCT fourier_czt_double *);
 
+/* ---------------- polyphase filter bank channelizer (extension; the reference has none) ----------
+ * The weighted-overlap-add analysis bank on DEVICE memory: P = channels >= 1, T = taps >= 1, D = hop >= 1 (D = P critically sampled,
+ * D < P oversampled, D > P leaves gaps) and a prototype filter h of P * T reals of the handle's precision.  Of `batch` contiguous rows of
+ * `length` values -- interleaved COMPLEX values, or REALS where the handle was created with real_input = 1 --
+ *   frames(length) = 1 + (length - P T) / D   for length >= P T, else 0 (an invalid length; fourier_hip_pfb_frames_*),
+ *   u[b, f, n] = sum_{t < T} h[t P + n] x[b, f D + t P + n],   n < P,   the taps summed in the order t = 0, 1, ...,
+ *   X[b, f, k] = sum_{n < P} u[b, f, n] exp(-2 pi i k n / P),
+ * batch x frames x bins interleaved complex values out, FRAME-MAJOR like every frame handle: frame f of row b at complex offset
+ * (b * frames + f) * bins; bins = P for complex rows, P / 2 + 1 (onesided) for real rows.  There is no padding.  There is NO per-frame
+ * phase rotation for D != P: a frame's time origin is its first sample, as in the STFT handle; a caller who wants the bins referred to
+ * the row's origin multiplies bin k of frame f by exp(-2 pi i k f D / P).  There is no `normalized` flag: the prototype filter carries
+ * the gain.  Analysis only.
+ * Filter: fourier_hip_pfb_set_filter_* takes P * T reals T on the device; NULL restores the default of all ones.  A set-up call: it
+ * waits for `stream`.
+ * create gives NULL for channels, taps or hop of 0 or a real_input flag outside {0, 1} (invalid), and for P * T or D above 2^31 - 1
+ * (unsupported).  Frames per row stay below 2^31.
+ * A NULL handle or pointer, reals not aligned to sizeof(T) or complex values -- a complex input included -- not aligned to 2 * sizeof(T),
+ * any overlap of d_in and d_out or an invalid length give FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.
+ * Stream-ordered on `stream` like fourier_hip_transform_batch_*.  Routes (fourier_hip_pfb_describe_*: "<route>: <the inner plan's describe>"):
+ *   "pfb composed"    every P: a fold sweep writes u of a chunk of frames into a handle-owned scratch (at most 1 GiB, never less than one
+ *                     frame), the inner plan -- the complex plan of P points, or the real-input plan of P points -- transforms them
+ *                     into the output.
+ *   "pfb fused rows"  the inner transform is one whole-row kernel (complex rows: P 64 ... 512, f32 also 1024; real rows: P 128 ... 1024,
+ *                     f32 also 2048): fold, transform and (real rows) untangle in ONE launch, no scratch.  Option "fusion" = 0 forces
+ *                     the composed route, 1 takes the fused one wherever it exists.  The DEFAULT is 1: the fused route was measured
+ *                     at 0.46 - 0.88 of the composed route's time at every shape tried.
+ * fourier_hip_pfb_reserve_*(h, length, batch) sizes everything forward calls of at most `batch` rows of `length` values need: they then
+ * never allocate.  NULL-handle calls return 0 from the getters, "" from describe and FOURIER_HIP_INVALID_ARGUMENT from the rest.
+ * Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_pfb_last_status_*. */
+struct fourier_pfb_float;
+struct fourier_pfb_double;
+
+/* NULL on failure (parameters outside the ranges above included). */
+struct fourier_pfb_float *fourier_hip_pfb_create_float(FOURIER_SIZE_TYPE channels, FOURIER_SIZE_TYPE taps, FOURIER_SIZE_TYPE hop,
+                                                       int real_input, int device);
+struct fourier_pfb_double *fourier_hip_pfb_create_double(FOURIER_SIZE_TYPE channels, FOURIER_SIZE_TYPE taps, FOURIER_SIZE_TYPE hop,
+                                                         int real_input, int device);
+/* NULL is a no-op. */
+void fourier_hip_pfb_destroy_float(FOURIER_STRUCT fourier_pfb_float *);
+void fourier_hip_pfb_destroy_double(FOURIER_STRUCT fourier_pfb_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_pfb_channels_float(const FOURIER_STRUCT fourier_pfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_channels_double(const FOURIER_STRUCT fourier_pfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_taps_float(const FOURIER_STRUCT fourier_pfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_taps_double(const FOURIER_STRUCT fourier_pfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_hop_float(const FOURIER_STRUCT fourier_pfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_hop_double(const FOURIER_STRUCT fourier_pfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_bins_float(const FOURIER_STRUCT fourier_pfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_pfb_bins_double(const FOURIER_STRUCT fourier_pfb_double *);
+/* frames of a row of `length` values; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_pfb_frames_float(const FOURIER_STRUCT fourier_pfb_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_pfb_frames_double(const FOURIER_STRUCT fourier_pfb_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_pfb_set_filter_float(FOURIER_STRUCT fourier_pfb_float *, const void *d_filter, void *stream);
+int fourier_hip_pfb_set_filter_double(FOURIER_STRUCT fourier_pfb_double *, const void *d_filter, void *stream);
+int fourier_hip_pfb_forward_float(const FOURIER_STRUCT fourier_pfb_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                  FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_pfb_forward_double(const FOURIER_STRUCT fourier_pfb_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                   FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_pfb_reserve_float(const FOURIER_STRUCT fourier_pfb_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_pfb_reserve_double(const FOURIER_STRUCT fourier_pfb_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed route, 1 = the fused one wherever it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_pfb_set_option_float(FOURIER_STRUCT fourier_pfb_float *, const char *key, long long value);
+int fourier_hip_pfb_set_option_double(FOURIER_STRUCT fourier_pfb_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_pfb_describe_float(const FOURIER_STRUCT fourier_pfb_float *);
+const char *fourier_hip_pfb_describe_double(const FOURIER_STRUCT fourier_pfb_double *);
+int fourier_hip_pfb_last_status_float(const FOURIER_STRUCT fourier_pfb_float *);
+int fourier_hip_pfb_last_status_double(const FOURIER_STRUCT fourier_pfb_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1515,6 +1584,58 @@ template <typename T> struct czt;
 FOURIER_DEFINE_CXX_CZT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CZT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CZT_WRAPPER
+
+/* polyphase filter bank channelizer on device memory (extension): fourier::pfb<float> / <double> */
+template <typename T> struct pfb;
+
+#define FOURIER_DEFINE_CXX_PFB_WRAPPER(T, SUFFIX)                                                  \
+  template <> struct pfb<T> {                                                                      \
+    /* hop = 0: critically sampled, hop = channels */                                              \
+    pfb(std::size_t channels, std::size_t taps, std::size_t hop = 0, bool real_input = false,      \
+        int device = -1)                                                                           \
+        : impl(::fourier::c::fourier_hip_pfb_create_##SUFFIX(channels, taps, hop ? hop : channels, \
+                                                             real_input ? 1 : 0, device),          \
+               ::fourier::c::fourier_hip_pfb_destroy_##SUFFIX) {}                                  \
+    pfb() = delete;                                                                                \
+    pfb(const pfb &) = delete;                                                                     \
+    pfb(pfb &&) = default;                                                                         \
+    pfb &operator=(const pfb &) = delete;                                                          \
+    pfb &operator=(pfb &&) = default;                                                              \
+    ~pfb() = default;                                                                              \
+    std::size_t channels() const { return ::fourier::c::fourier_hip_pfb_channels_##SUFFIX(impl.get()); } \
+    std::size_t taps() const { return ::fourier::c::fourier_hip_pfb_taps_##SUFFIX(impl.get()); }   \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_pfb_hop_##SUFFIX(impl.get()); }     \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_pfb_bins_##SUFFIX(impl.get()); }   \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_pfb_frames_##SUFFIX(impl.get(), length);                    \
+    }                                                                                              \
+    /* channels * taps reals on the device, nullptr: all ones; waits for `stream` */               \
+    int set_filter(const void *d_filter, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_pfb_set_filter_##SUFFIX(impl.get(), d_filter, stream);      \
+    }                                                                                              \
+    /* `batch` rows of `length` values -> batch x frames x bins complex values (no overlap) */     \
+    int forward_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch,       \
+                       void *stream = nullptr) const {                                             \
+      return ::fourier::c::fourier_hip_pfb_forward_##SUFFIX(impl.get(), d_in, d_out, length, batch, \
+                                                            stream);                               \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_pfb_reserve_##SUFFIX(impl.get(), length, batch);            \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_pfb_set_option_##SUFFIX(impl.get(), key, value);            \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_pfb_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_pfb_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_pfb_##SUFFIX,                                          \
+                      void (*)(::fourier::c::fourier_pfb_##SUFFIX *)> impl;                        \
+  };
+FOURIER_DEFINE_CXX_PFB_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_PFB_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_PFB_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
