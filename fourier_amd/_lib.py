@@ -82,6 +82,12 @@ _PFB = ("fourier_hip_pfb_", {  # polyphase filter bank channelizer
     "set_filter": (ci, [vp, vp, vp]),
     "forward": (ci, [vp, vp, vp, sz, sz, vp]),  # handle, d_in, d_out, length, batch, stream
     "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_IPFB = ("fourier_hip_ipfb_", {  # polyphase synthesis filter bank
+    "create": (vp, [sz, sz, sz, ci, ci]),  # channels, taps, hop, real_output, device
+    "destroy": (None, [vp]), "channels": (sz, [vp]), "taps": (sz, [vp]), "hop": (sz, [vp]), "bins": (sz, [vp]), "length": (sz, [vp, sz]),
+    "set_filter": (ci, [vp, vp, vp]),
+    "inverse": (ci, [vp, vp, vp, sz, sz, sz, vp]),  # handle, d_in, d_out, frames, length, batch, stream
+    "reserve": (ci, [vp, sz, sz]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -106,8 +112,9 @@ CSD_SYMBOLS = list(_signatures(_CSD))
 HILBERT_SYMBOLS = list(_signatures(_HILBERT))
 CZT_SYMBOLS = list(_signatures(_CZT))
 PFB_SYMBOLS = list(_signatures(_PFB))
+IPFB_SYMBOLS = list(_signatures(_IPFB))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -117,7 +124,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT, _PFB):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT, _PFB, _IPFB):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -25,6 +25,7 @@
 #include "hilbert_plan.h"
 #include "czt_plan.h"
 #include "pfb_plan.h"
+#include "ipfb_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -539,6 +540,46 @@ FOURIER_DEFINE_CZT_ABI(double, double)
 
 FOURIER_DEFINE_PFB_ABI(float, float)
 FOURIER_DEFINE_PFB_ABI(double, double)
+
+// polyphase synthesis filter bank (fourier_hip_ipfb_*)
+#define FOURIER_DEFINE_IPFB_ABI(T, SUFFIX)                                                                       \
+  extern "C" fc::fourier_ipfb_##SUFFIX* fourier_hip_ipfb_create_##SUFFIX(size_t channels, size_t taps, size_t hop, int real_output, int device) { \
+    return (fc::fourier_ipfb_##SUFFIX*)create_handle<IpfbPlan<T>>(channels, taps, hop, real_output, device);     \
+  }                                                                                                              \
+  extern "C" void fourier_hip_ipfb_destroy_##SUFFIX(fc::fourier_ipfb_##SUFFIX* h) { destroy_handle<IpfbPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_ipfb_describe_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) { return describe_handle<IpfbPlan<T>>(h); } \
+  extern "C" int fourier_hip_ipfb_last_status_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) { return last_status_of<IpfbPlan<T>>(h); } \
+  extern "C" size_t fourier_hip_ipfb_channels_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) {                     \
+    return h ? ((const IpfbPlan<T>*)h)->channels() : 0;                                                          \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_ipfb_taps_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) {                         \
+    return h ? ((const IpfbPlan<T>*)h)->taps() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_ipfb_hop_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) {                          \
+    return h ? ((const IpfbPlan<T>*)h)->hop() : 0;                                                               \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_ipfb_bins_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h) {                         \
+    return h ? ((const IpfbPlan<T>*)h)->bins() : 0;                                                              \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_ipfb_length_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h, size_t frames) {        \
+    return h ? ((const IpfbPlan<T>*)h)->length(frames) : 0;                                                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_ipfb_set_filter_##SUFFIX(fc::fourier_ipfb_##SUFFIX* h, const void* d_filter, void* stream) { \
+    IpfbPlan<T>* p = (IpfbPlan<T>*)h;                                                                            \
+    return guarded_handle(p, [&] { p->set_filter(d_filter, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_ipfb_reserve_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h, size_t frames, size_t batch) { \
+    const IpfbPlan<T>* p = (const IpfbPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->reserve(frames, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_ipfb_inverse_##SUFFIX(const fc::fourier_ipfb_##SUFFIX* h, const void* d_in, void* d_out, size_t frames, \
+                                                   size_t length, size_t batch, void* stream) {                  \
+    const IpfbPlan<T>* p = (const IpfbPlan<T>*)h;                                                                \
+    return guarded_handle(p, [&] { p->inverse(d_in, d_out, frames, length, batch, (hipStream_t)stream); });      \
+  }
+
+FOURIER_DEFINE_IPFB_ABI(float, float)
+FOURIER_DEFINE_IPFB_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

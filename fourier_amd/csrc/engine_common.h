@@ -176,6 +176,7 @@ typedef void (*MdctKernel)(MdctArgs);
 typedef void (*SpectrogramKernel)(SpectrogramArgs);
 typedef void (*CsdKernel)(CsdArgs);
 typedef void (*PfbKernel)(PfbArgs);
+typedef void (*IpfbKernel)(IpfbArgs);
 // The fused frame route of a frame handle (STFT, MDCT, spectrogram, cross spectrum, polyphase filter bank) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
 // one shape.  STFT and MDCT have fn[0]; the spectrogram one per epilogue, fn[SPEC_MAGNITUDE], fn[SPEC_POWER], fn[SPEC_PARTIAL].
 // The cross spectrum has fn[0]; the filter bank fn[0] for complex rows (P = L channels) and fn[1] for real rows (P = 2 L).  L == 0: none for that length
@@ -300,6 +301,8 @@ template <typename T> struct Real {};
   /* whole-row kernel of length L: complex rows of P = L channels, real rows of P = 2 L                                */ \
   PfbKernel get_pfb_kernel(Real<T>);                                                                                   \
   PfbRowsKernel get_pfb_rows_kernel(Real<T>, int L);                                                                   \
+  /* ... and the overlap-add gather of the synthesis filter bank handle (ipfb_gather_kernel; IpfbPlan, ipfb_plan.h)    */ \
+  IpfbKernel get_ipfb_kernel(Real<T>);                                                                                 \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
   /* kernels_hilbert.cpp: the analytic signal or the envelope of real rows in one launch on the shapes of the two-level */ \

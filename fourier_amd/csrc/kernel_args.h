@@ -387,6 +387,37 @@ struct PfbArgs {
   int pairs;                  // fused, real rows: every frame starts on an even element of a 2 * sizeof(T)-aligned row
 };
 
+// ---- polyphase synthesis filter bank (kernels_pfb.h; IpfbPlan, ipfb_plan.h)
+// ipfb_gather_kernel: the weighted overlap-add as a gather.  Frames q < nfr of each of the launch's rows lie in `in` as rows of `channels`
+// values of the output's kind (complex values, or reals where `real`), frame q of row r at (r * nfr + q) * channels.  The launch writes
+// samples t0 ... t0 + span - 1 of every row (row r at out + r * length), one lane per sample, or per pair of samples where `pairs`:
+// `items` lanes a row, lane index = r * items + j by multiply-high.  Everything inside a row is 32-bit and relative to frame fb, the first
+// frame of the row that does not end before t0: sample t0 + i lies u = e0 + i values behind the start of frame fb (e0 = t0 - fb * hop,
+// negative inside a gap between frames), frame fb + k covers it where 0 <= u - k * hop < span_pt, and
+//   y[t0 + i] = scale * sum over those k < kcount, ascending, of filt[u - k hop] * frame_{q0 + k}[(u - k hop) mod channels],
+// 0 where there is none.  The plan keeps span <= 2^30, so u < 2^32.
+struct IpfbArgs {
+  const void* in; void* out;
+  const void* filt;           // the synthesis filter, channels * taps reals
+  uint64_t length;            // values per output row
+  uint64_t t0;                // first sample of the launch within a row
+  uint64_t nfr;               // frames per row in `in`
+  long long e0;               // t0 - fb * hop (signed; spelled without a stdint name: the run-time compiler has no int64_t)
+  uint32_t span;              // samples per row in this launch
+  uint32_t items;             // lanes per row: span, with `pairs` (span + 1) / 2
+  uint32_t total;             // rows * items
+  uint32_t it_m, it_l;        // idx / items = (umulhi(idx, it_m) + idx) >> it_l
+  uint32_t q0;                // the frame fb's index within `in`
+  uint32_t kcount;            // frames of `in` from fb on: nfr - q0
+  uint32_t channels, span_pt, hop;  // P, P * T, D
+  uint32_t hop_mod;           // D mod P: what the index within a frame moves by per frame
+  uint32_t hop_m, hop_l;      // the same divider for hop
+  uint32_t ch_m, ch_l;        // ... and for channels
+  int real;                   // the rows are reals
+  int pairs;                  // real rows: every row of the launch starts on a 2 * sizeof(T)-aligned address, two reals per store
+  double scale;               // 1 / channels (the inner inverse runs unscaled), applied to the finished sum
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

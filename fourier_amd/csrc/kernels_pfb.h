@@ -12,7 +12,10 @@
 //   pfb_real_rows_kernel  fused route for real rows, P = 2L: the complex value m is (x[2m], x[2m+1]) under the coefficient pair
 //                         (h[2m], h[2m+1]), as stft_rows_kernel packs its window; after the row core it untangles through LDS half a tile at
 //                         a time (real_post_kernel's formula, kernels_real.h; stft_rows_kernel's epilogue with scale = 1).
-// One launch, no scratch: the T-fold re-read of every sample comes from the L2 (consecutive frames stay on one XCD), the filter table
+//   ipfb_gather_kernel    the synthesis bank (IpfbPlan, ipfb_plan.h): the weighted overlap-add of the inverse-transformed frames of a
+//                         chunk as a gather, y[t] = 1/P sum_f g[t - f D] v[f, (t - f D) mod P] in ascending f, one lane per output
+//                         sample (or pair of reals), no atomics; as istft_ola_kernel lives beside the STFT's forward kernels.
+// The fused routes take one launch, no scratch: the T-fold re-read of every sample comes from the L2 (consecutive frames stay on one XCD), the filter table
 // is shared by every frame and stays there too; the bins are written once.  The accumulators are the register tile itself, so the tap
 // loop costs address registers only.  The gather and the epilogue stay spelled out, as kernels_frames.h says of the siblings.
 #pragma once
@@ -50,6 +53,71 @@ __global__ void __launch_bounds__(PFB_THREADS) pfb_fold_kernel(PfbArgs a) {
       }
       dst[n] = acc;
     }
+  }
+}
+
+// ---- the synthesis bank's overlap-add (IpfbPlan, ipfb_plan.h; the argument block's comment in kernel_args.h has the geometry)
+// One value of the output's kind times a filter coefficient, and the running sum: the same two expressions for every sample, whichever
+// store width its lane has, so that a sample's bits do not depend on the launch it falls into.
+template <typename T> __device__ __forceinline__ T ipfb_mul(T g, T v) { return g * v; }
+template <typename T> __device__ __forceinline__ cpx<T> ipfb_mul(T g, cpx<T> v) { return cpx<T>{g * v.re, g * v.im}; }
+template <typename T> __device__ __forceinline__ T ipfb_acc(T acc, T g, T v) { return acc + g * v; }
+template <typename T> __device__ __forceinline__ cpx<T> ipfb_acc(cpx<T> acc, T g, cpx<T> v) { return cpx<T>{acc.re + g * v.re, acc.im + g * v.im}; }
+template <typename T> __device__ __forceinline__ T ipfb_scaled(T acc, T s) { return acc * s; }
+template <typename T> __device__ __forceinline__ cpx<T> ipfb_scaled(cpx<T> acc, T s) { return cpx<T>{acc.re * s, acc.im * s}; }
+
+// the sample u values behind the start of frame fb: `fr` points at that frame of the sample's row.  Three multiply-high divisions in
+// front of the frame loop (the last and the first covering frame, the first index within a frame), none inside: m moves by D per frame,
+// n = m mod P by D mod P with a conditional add.  Ascending frames, starting from the first term.
+template <typename T, typename V> __device__ __forceinline__ V ipfb_sample(const IpfbArgs& a, const V* __restrict__ fr, const T* __restrict__ filt, int64_t u) {
+  V zero{};
+  if (u < 0 || a.kcount == 0) return zero;  // inside a gap in front of frame fb: no frame covers it
+  const uint32_t x = (uint32_t)u, P = a.channels, D = a.hop, dm = a.hop_mod;
+  uint32_t k_hi = real_div(x, a.hop_m, a.hop_l);
+  const uint32_t k_lo = x >= a.span_pt ? real_div(x - a.span_pt, a.hop_m, a.hop_l) + 1u : 0u;
+  if (k_hi > a.kcount - 1u) k_hi = a.kcount - 1u;
+  if (k_lo > k_hi) return zero;  // a gap behind frame k_lo - 1, or behind the last frame
+  uint32_t m = x - k_lo * D;     // < P T
+  uint32_t n = m - real_div(m, a.ch_m, a.ch_l) * P;
+  const V* p = fr + (uint64_t)k_lo * P;
+  V acc = ipfb_mul(filt[m], p[n]);
+  for (uint32_t k = k_lo; k < k_hi; ++k) {
+    m -= D;
+    n = n >= dm ? n - dm : n + (P - dm);
+    p += P;
+    acc = ipfb_acc(acc, filt[m], p[n]);
+  }
+  return ipfb_scaled(acc, (T)a.scale);
+}
+
+// One lane per output sample of the launch's range, consecutive lanes consecutive samples: g[m] and the frames' values are read in runs
+// (up to the wrap at P), every sample of the range is written once, zeros included, nothing else.  With `pairs` a lane owns two
+// neighbouring reals and stores them together; the last lane of an odd range stores one.
+template <typename T>
+__global__ void __launch_bounds__(PFB_THREADS) ipfb_gather_kernel(IpfbArgs a) {
+  const uint32_t idx = blockIdx.x * (uint32_t)PFB_THREADS + threadIdx.x;
+  if (idx >= a.total) return;
+  const uint32_t row = real_div(idx, a.it_m, a.it_l), j = idx - row * a.items;
+  const T* __restrict__ filt = (const T*)a.filt;
+  const uint64_t fr0 = ((uint64_t)row * a.nfr + a.q0) * a.channels, o0 = (uint64_t)row * a.length + a.t0;
+  if (!a.real) {
+    const cpx<T>* fr = (const cpx<T>*)a.in + fr0;
+    ((cpx<T>*)a.out)[o0 + j] = ipfb_sample<T, cpx<T>>(a, fr, filt, a.e0 + (int64_t)j);
+    return;
+  }
+  const T* fr = (const T*)a.in + fr0;
+  T* out = (T*)a.out + o0;
+  if (!a.pairs) {
+    out[j] = ipfb_sample<T, T>(a, fr, filt, a.e0 + (int64_t)j);
+    return;
+  }
+  const uint32_t i = 2u * j;
+  const T y0 = ipfb_sample<T, T>(a, fr, filt, a.e0 + (int64_t)i);
+  if (i + 1u < a.span) {
+    const T y1 = ipfb_sample<T, T>(a, fr, filt, a.e0 + (int64_t)i + 1);
+    *(cpx<T>*)(out + i) = cpx<T>{y0, y1};
+  } else {
+    out[i] = y0;
   }
 }
 

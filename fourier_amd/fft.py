@@ -1514,6 +1514,151 @@ def pfb_channelize(x, filter, channels, hop=None, out=None):
     return p.forward(x.contiguous(), out)
 
 
+class Ipfb(_Handle):
+    """Batched polyphase synthesis filter bank (include/fourier.h, fourier_hip_ipfb_*) on device memory, the mirror of Pfb: frames x
+    bins complex values per row, FRAME-MAJOR (what Pfb.forward writes), are inverse-transformed to `channels` values each and
+    overlap-added under a synthesis filter g: y[t] = sum_f g[t - f D] v[f, (t - f D) mod P] over the frames that cover t, in ascending f.
+    Rows of 1 <= length <= length(frames) values out, complex, or reals with real_output=True (bins = channels // 2 + 1).  No envelope
+    division, no phase rotation: reconstruction is a property of the filter pair (pfb_reconstruction_terms).  hop=None means channels.
+    The filter is set afterwards (set_filter; default all ones)."""
+
+    _prefix = "fourier_hip_ipfb_"
+    _destroy = "fourier_hip_ipfb_destroy"
+
+    def __init__(self, channels, taps, real="f32", hop=None, real_output=False, device=-1):
+        channels, taps = int(channels), int(taps)
+        hop = channels if hop is None else int(hop)
+        if channels < 1 or taps < 1 or hop < 1:
+            raise ValueError(f"need channels >= 1, taps >= 1 and hop >= 1, got {channels}, {taps}, {hop}")
+        self._create(real, f"synthesis filter bank plan of {channels} channels, {taps} taps, hop {hop}", channels, taps, hop,
+                     int(bool(real_output)), int(device))
+        self._p, self._t, self._hop, self.real_output = channels, taps, hop, bool(real_output)
+
+    def channels(self):
+        return self._p
+
+    def taps(self):
+        return self._t
+
+    def hop(self):
+        return self._hop
+
+    def bins(self):
+        return self._p // 2 + 1 if self.real_output else self._p
+
+    def length(self, frames):
+        """(frames - 1) * hop + channels * taps, the longest row `frames` frames give; 0 where the frame count is invalid."""
+        return int(self._fn("length")(self._h, int(frames)))
+
+    def reserve(self, frames, batch):
+        """Later inverse calls from at most `frames` frames and `batch` rows never allocate."""
+        self._call("reserve", int(frames), int(batch))
+
+    def set_filter_ptr(self, d_filter, stream=0):
+        """channels() * taps() reals of the handle's precision at d_filter (0 / None: all ones).  Waits for `stream`."""
+        self._call("set_filter", d_filter or None, stream)
+
+    def inverse_ptr(self, d_in, d_out, frames, length, batch, stream=0):
+        """batch x frames x bins() complex at d_in -> `batch` rows of `length` values at d_out, enqueued on `stream`."""
+        self._call("inverse", d_in, d_out, int(frames), int(length), int(batch), stream)
+
+    def set_filter(self, filter):
+        """A contiguous CUDA tensor of channels() * taps() reals of the handle's precision, shape (channels * taps,) or (taps, channels),
+        or None for all ones; on the current stream."""
+        if filter is None:
+            return self.set_filter_ptr(None)
+        _require_cuda(filter, _torch_dtypes(self.real)[0])
+        if tuple(filter.shape) not in ((self._p * self._t,), (self._t, self._p)):
+            raise ValueError(f"filter must have shape ({self._p * self._t},) or ({self._t}, {self._p}), got {tuple(filter.shape)}")
+        self.set_filter_ptr(filter.data_ptr(), _stream(filter))
+
+    def inverse(self, Y, length=None, out=None):
+        """Contiguous (..., frames, bins) complex CUDA tensor of the handle's precision -> a new (..., length) tensor, float where
+        real_output, else complex, or `out` (which may not overlap `Y`), on the current stream.  length=None: length(frames)."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        _require_cuda(Y, cdt)
+        if Y.dim() < 2 or int(Y.shape[-1]) != self.bins():
+            raise ValueError(f"expected (..., frames, {self.bins()}), got {tuple(Y.shape)}")
+        frames = int(Y.shape[-2])
+        full = self.length(frames)
+        if full == 0:
+            raise ValueError(f"{frames} frames are not a valid frame count")
+        length = full if length is None else int(length)
+        if not 1 <= length <= full:
+            raise ValueError(f"length must be 1 ... {full} for {frames} frames, got {length}")
+        shape = tuple(Y.shape[:-2]) + (length,)
+        odt = rdt if self.real_output else cdt
+        if out is None:
+            out = torch.empty(shape, dtype=odt, device=Y.device)
+        else:
+            _require_out(out, shape, odt, Y.device)
+        batch = Y.numel() // (frames * self.bins())
+        if batch:
+            self.inverse_ptr(Y.data_ptr(), out.data_ptr(), frames, length, batch, _stream(Y))
+        return out
+
+
+def create_ipfb_f32(channels, taps, hop=None, real_output=False, device=-1):
+    return Ipfb(channels, taps, "f32", hop, real_output, device)
+
+
+def create_ipfb_f64(channels, taps, hop=None, real_output=False, device=-1):
+    return Ipfb(channels, taps, "f64", hop, real_output, device)
+
+
+def pfb_synthesize(Y, filter, channels, hop=None, length=None, real_output=False, out=None):
+    """The polyphase synthesis bank of a complex64 / complex128 CUDA tensor of shape (..., frames, bins) on the current stream, the
+    mirror of pfb_channelize: bins = `channels`, or channels // 2 + 1 with real_output=True (explicit: the bins cannot tell the two
+    kinds apart at channels <= 2); `filter` holds channels * taps reals of the same precision on the same device, shape
+    (channels * taps,) or (taps, channels), or is None for all ones of one tap.  Returns (..., length) float (real_output) or complex,
+    or `out`; length=None means (frames - 1) * hop + channels * taps.  Leading dimensions fold into the batch.  Handles are cached per
+    (channels, taps, hop, dtype, kind, device) and the filter is set on EVERY call; keep an Ipfb to reuse one."""
+    if not (_is_torch(Y) and Y.is_cuda and _precision(Y.dtype) is not None and not _precision(Y.dtype)[1]):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor")
+    real = _precision(Y.dtype)[0]
+    channels = int(channels)
+    if channels < 1:
+        raise ValueError(f"need channels >= 1, got {channels}")
+    bins = channels // 2 + 1 if real_output else channels
+    if Y.dim() < 2 or int(Y.shape[-1]) != bins:
+        raise ValueError(f"expected (..., frames, {bins}) for {channels} channels, real_output={bool(real_output)}, got {tuple(Y.shape)}")
+    taps = 1
+    if filter is not None:
+        if not (_is_torch(filter) and filter.is_cuda and filter.dtype == _torch_dtypes(real)[0] and filter.device == Y.device):
+            raise TypeError(f"filter must be a CUDA {_names((_torch_dtypes(real)[0],))} tensor on the input's device")
+        if filter.numel() == 0 or filter.numel() % channels or (filter.dim() == 2 and filter.shape[1] != channels) or filter.dim() not in (1, 2):
+            raise ValueError(f"filter must hold channels * taps values as (channels * taps,) or (taps, {channels}), got {tuple(filter.shape)}")
+        taps = filter.numel() // channels
+        filter = filter.contiguous()
+    p = _cached_plan(Ipfb, channels, taps, real, channels if hop is None else int(hop), bool(real_output), int(_device_index(Y)))
+    p.set_filter(filter)
+    return p.inverse(Y.contiguous(), length, out)
+
+
+def pfb_reconstruction_terms(h, g, channels, hop):
+    """What an analysis filter h and a synthesis filter g (channels * taps reals each, any shape) make of a signal that goes through
+    Pfb and Ipfb, in the interior where every covering frame exists: y[t] = sum_{|s| < T} c_s(t mod D) x[t + s P] with
+    c_s(r) = sum_j g[r + j D] h[r + j D + s P] over the j that keep both indices inside [0, P T).  Host-side numpy in float64; returns
+    c of shape (2 T - 1, D), row s + T - 1 holding c_s.  Perfect reconstruction with zero delay: row T - 1 all ones, every other row zero."""
+    P, D = int(channels), int(hop)
+    hv = np.asarray(h.cpu() if _is_torch(h) else h, dtype=np.float64).reshape(-1)
+    gv = np.asarray(g.cpu() if _is_torch(g) else g, dtype=np.float64).reshape(-1)
+    if P < 1 or D < 1:
+        raise ValueError(f"need channels >= 1 and hop >= 1, got {channels}, {hop}")
+    if hv.size == 0 or hv.size % P or gv.size != hv.size:
+        raise ValueError(f"h and g must hold the same multiple of {P} values, got {hv.size} and {gv.size}")
+    span = hv.size
+    T = span // P
+    c = np.zeros((2 * T - 1, D))
+    for s in range(-(T - 1), T):
+        lo, hi = max(0, -s * P), min(span, span - s * P)  # the m with m and m + s P inside [0, P T)
+        m = np.arange(lo, hi)
+        np.add.at(c[s + T - 1], m % D, gv[m] * hv[m + s * P])
+    return c
+
+
 def pfb_prototype(channels, taps, dtype=None):
     """The usual windowed-sinc prototype filter of a `channels`-channel bank with `taps` taps: sinc((n - (P T - 1) / 2) / P) *
     hamming(P T)[n], n < P T, computed in float64 and rounded to `dtype` (a numpy dtype: a numpy array; a torch dtype: a CPU tensor;

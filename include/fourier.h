@@ -1075,7 +1075,7 @@ int fourier_hip_czt_last_status_double(const FOURIER_STRUCT fourier_czt_double *
  * (b * frames + f) * bins; bins = P for complex rows, P / 2 + 1 (onesided) for real rows.  There is no padding.  There is NO per-frame
  * phase rotation for D != P: a frame's time origin is its first sample, as in the STFT handle; a caller who wants the bins referred to
  * the row's origin multiplies bin k of frame f by exp(-2 pi i k f D / P).  There is no `normalized` flag: the prototype filter carries
- * the gain.  Analysis only.
+ * the gain.  The synthesis bank that takes these frames back to rows is the fourier_hip_ipfb_* family below.
  * Filter: fourier_hip_pfb_set_filter_* takes P * T reals T on the device; NULL restores the default of all ones.  A set-up call: it
  * waits for `stream`.
  * create gives NULL for channels, taps or hop of 0 or a real_input flag outside {0, 1} (invalid), and for P * T or D above 2^31 - 1
@@ -1132,6 +1132,73 @@ const char *fourier_hip_pfb_describe_float(const FOURIER_STRUCT fourier_pfb_floa
 const char *fourier_hip_pfb_describe_double(const FOURIER_STRUCT fourier_pfb_double *);
 int fourier_hip_pfb_last_status_float(const FOURIER_STRUCT fourier_pfb_float *);
 int fourier_hip_pfb_last_status_double(const FOURIER_STRUCT fourier_pfb_double *);
+
+/* ---------------- polyphase synthesis filter bank (extension; the reference has none) ----------
+ * The weighted-overlap-add synthesis bank on DEVICE memory, the mirror of the channelizer above with its parameterisation: P = channels,
+ * T = taps, D = hop and a synthesis filter g of P * T reals of the handle's precision.  Of batch x frames x bins interleaved complex
+ * values, FRAME-MAJOR, exactly what fourier_hip_pfb_forward_* writes (bins = P for complex output rows, P / 2 + 1 for REAL output rows,
+ * real_output = 1),
+ *   full(frames)  = (frames - 1) D + P T                                       (fourier_hip_ipfb_length_*),
+ *   v[b, f, n]    = (1/P) sum_k Y[b, f, k] exp(+2 pi i k n / P),  n < P        (real rows: numpy's irfft(Y, n = P): the imaginary parts
+ *                                                                               of bin 0 and, for even P, of bin P / 2 are ignored),
+ *   y[b, t]       = sum over the frames f with 0 <= t - f D < P T, in ASCENDING f, of  g[t - f D] * v[b, f, (t - f D) mod P],  t < length,
+ * `batch` contiguous rows of `length` values out, 1 <= length <= full(frames).  The sum starts from its first term; a sample that no
+ * frame covers (D > P T) is written as 0.  No atomics: repeated calls give the same bits.  There is no envelope division and no NOLA
+ * check, and no per-frame phase rotation (the mirror of the analysis convention): reconstruction is a property of the pair (h, g).
+ * For frames made by the analysis handle with filter h, in the interior where every covering frame exists,
+ *   y[t] = sum_{|s| < T} c_s(t mod D) x[t + s P],     c_s(r) = sum_j g[r + j D] h[r + j D + s P]   (both indices inside [0, P T)),
+ * so the pair reconstructs perfectly with zero delay iff c_0 == 1 and c_s == 0 for s != 0 -- for instance T = 1, D = P / 2,
+ * h = g = the periodic sqrt-Hann window, or D = P, h = g = ones on the first P coefficients and zeros after.
+ * Filter: fourier_hip_ipfb_set_filter_* takes P * T reals T on the device; NULL restores the default of all ones.  A set-up call: it
+ * waits for `stream`.
+ * create gives NULL for channels, taps or hop of 0 or a real_output flag outside {0, 1} (invalid), and for P * T or D above 2^31 - 1
+ * (unsupported).  Frames per row stay below 2^31.
+ * A NULL handle or pointer, frames = 0 or >= 2^31, length = 0 or > full(frames), d_in not aligned to 2 * sizeof(T), d_out not aligned
+ * to its element (sizeof(T) for real rows, 2 * sizeof(T) for complex rows) or any overlap of d_in and d_out give
+ * FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  The input is not modified.
+ * Stream-ordered on `stream` like fourier_hip_transform_batch_*.  One route (fourier_hip_ipfb_describe_*: "ipfb composed: <the inner
+ * plan's describe>"): the inner plan -- the complex plan of P points, or the real-input plan of P points -- takes a chunk of frames,
+ * unscaled, into a handle-owned scratch of rows of P values (at most 1 GiB, never fewer frames than cover one sample, ceil(P T / D)),
+ * one gather launch writes the chunk's samples with the 1/P folded in.  The output does not depend on the chunking.
+ * fourier_hip_ipfb_reserve_*(h, frames, batch) sizes everything inverse calls from at most `frames` frames and `batch` rows need: they
+ * then never allocate.  NULL-handle calls return 0 from the getters, "" from describe and FOURIER_HIP_INVALID_ARGUMENT from the rest.
+ * Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_ipfb_last_status_*. */
+struct fourier_ipfb_float;
+struct fourier_ipfb_double;
+
+/* NULL on failure (parameters outside the ranges above included). */
+struct fourier_ipfb_float *fourier_hip_ipfb_create_float(FOURIER_SIZE_TYPE channels, FOURIER_SIZE_TYPE taps, FOURIER_SIZE_TYPE hop,
+                                                         int real_output, int device);
+struct fourier_ipfb_double *fourier_hip_ipfb_create_double(FOURIER_SIZE_TYPE channels, FOURIER_SIZE_TYPE taps, FOURIER_SIZE_TYPE hop,
+                                                           int real_output, int device);
+/* NULL is a no-op. */
+void fourier_hip_ipfb_destroy_float(FOURIER_STRUCT fourier_ipfb_float *);
+void fourier_hip_ipfb_destroy_double(FOURIER_STRUCT fourier_ipfb_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_ipfb_channels_float(const FOURIER_STRUCT fourier_ipfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_channels_double(const FOURIER_STRUCT fourier_ipfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_taps_float(const FOURIER_STRUCT fourier_ipfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_taps_double(const FOURIER_STRUCT fourier_ipfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_hop_float(const FOURIER_STRUCT fourier_ipfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_hop_double(const FOURIER_STRUCT fourier_ipfb_double *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_bins_float(const FOURIER_STRUCT fourier_ipfb_float *);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_bins_double(const FOURIER_STRUCT fourier_ipfb_double *);
+/* full(frames), the longest row `frames` frames give; 0 for frames = 0 or >= 2^31 or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_ipfb_length_float(const FOURIER_STRUCT fourier_ipfb_float *, FOURIER_SIZE_TYPE frames);
+FOURIER_SIZE_TYPE fourier_hip_ipfb_length_double(const FOURIER_STRUCT fourier_ipfb_double *, FOURIER_SIZE_TYPE frames);
+int fourier_hip_ipfb_set_filter_float(FOURIER_STRUCT fourier_ipfb_float *, const void *d_filter, void *stream);
+int fourier_hip_ipfb_set_filter_double(FOURIER_STRUCT fourier_ipfb_double *, const void *d_filter, void *stream);
+int fourier_hip_ipfb_inverse_float(const FOURIER_STRUCT fourier_ipfb_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                   FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_ipfb_inverse_double(const FOURIER_STRUCT fourier_ipfb_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE frames,
+                                    FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_ipfb_reserve_float(const FOURIER_STRUCT fourier_ipfb_float *, FOURIER_SIZE_TYPE frames, FOURIER_SIZE_TYPE batch);
+int fourier_hip_ipfb_reserve_double(const FOURIER_STRUCT fourier_ipfb_double *, FOURIER_SIZE_TYPE frames, FOURIER_SIZE_TYPE batch);
+/* "" for a NULL handle. */
+const char *fourier_hip_ipfb_describe_float(const FOURIER_STRUCT fourier_ipfb_float *);
+const char *fourier_hip_ipfb_describe_double(const FOURIER_STRUCT fourier_ipfb_double *);
+int fourier_hip_ipfb_last_status_float(const FOURIER_STRUCT fourier_ipfb_float *);
+int fourier_hip_ipfb_last_status_double(const FOURIER_STRUCT fourier_ipfb_double *);
 
 #ifdef __cplusplus
 } /* extern "C" */
@@ -1636,6 +1703,56 @@ template <typename T> struct pfb;
 FOURIER_DEFINE_CXX_PFB_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_PFB_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_PFB_WRAPPER
+
+/* polyphase synthesis filter bank on device memory (extension): fourier::ipfb<float> / <double> */
+template <typename T> struct ipfb;
+
+#define FOURIER_DEFINE_CXX_IPFB_WRAPPER(T, SUFFIX)                                                 \
+  template <> struct ipfb<T> {                                                                     \
+    /* hop = 0: critically sampled, hop = channels */                                              \
+    ipfb(std::size_t channels, std::size_t taps, std::size_t hop = 0, bool real_output = false,    \
+         int device = -1)                                                                          \
+        : impl(::fourier::c::fourier_hip_ipfb_create_##SUFFIX(channels, taps, hop ? hop : channels, \
+                                                              real_output ? 1 : 0, device),        \
+               ::fourier::c::fourier_hip_ipfb_destroy_##SUFFIX) {}                                 \
+    ipfb() = delete;                                                                               \
+    ipfb(const ipfb &) = delete;                                                                   \
+    ipfb(ipfb &&) = default;                                                                       \
+    ipfb &operator=(const ipfb &) = delete;                                                        \
+    ipfb &operator=(ipfb &&) = default;                                                            \
+    ~ipfb() = default;                                                                             \
+    std::size_t channels() const { return ::fourier::c::fourier_hip_ipfb_channels_##SUFFIX(impl.get()); } \
+    std::size_t taps() const { return ::fourier::c::fourier_hip_ipfb_taps_##SUFFIX(impl.get()); }  \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_ipfb_hop_##SUFFIX(impl.get()); }    \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_ipfb_bins_##SUFFIX(impl.get()); }  \
+    /* (frames - 1) * hop + channels * taps */                                                     \
+    std::size_t length(std::size_t frames) const {                                                 \
+      return ::fourier::c::fourier_hip_ipfb_length_##SUFFIX(impl.get(), frames);                   \
+    }                                                                                              \
+    /* channels * taps reals on the device, nullptr: all ones; waits for `stream` */               \
+    int set_filter(const void *d_filter, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_ipfb_set_filter_##SUFFIX(impl.get(), d_filter, stream);     \
+    }                                                                                              \
+    /* batch x frames x bins complex values -> `batch` rows of `length` values (no overlap) */     \
+    int inverse_device(const void *d_in, void *d_out, std::size_t frames, std::size_t length,      \
+                       std::size_t batch, void *stream = nullptr) const {                          \
+      return ::fourier::c::fourier_hip_ipfb_inverse_##SUFFIX(impl.get(), d_in, d_out, frames, length, \
+                                                             batch, stream);                       \
+    }                                                                                              \
+    int reserve(std::size_t frames, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_ipfb_reserve_##SUFFIX(impl.get(), frames, batch);           \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_ipfb_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_ipfb_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_ipfb_##SUFFIX,                                         \
+                      void (*)(::fourier::c::fourier_ipfb_##SUFFIX *)> impl;                       \
+  };
+FOURIER_DEFINE_CXX_IPFB_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_IPFB_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_IPFB_WRAPPER
 
 /* convolution with a prepared filter bank on device memory (extension): fourier::conv<float> / <double> */
 template <typename T> struct conv;
