@@ -88,6 +88,12 @@ _IPFB = ("fourier_hip_ipfb_", {  # polyphase synthesis filter bank
     "set_filter": (ci, [vp, vp, vp]),
     "inverse": (ci, [vp, vp, vp, sz, sz, sz, vp]),  # handle, d_in, d_out, frames, length, batch, stream
     "reserve": (ci, [vp, sz, sz]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_RESAMPLE = ("fourier_hip_resample_", {  # Fourier-domain resampling of complex or real rows
+    "create": (vp, [sz, sz, ci, ci]),  # n_in, n_out, real_input, device
+    "destroy": (None, [vp]), "size_in": (sz, [vp]), "size_out": (sz, [vp]), "real_input": (ci, [vp]),
+    "forward": (ci, [vp, vp, vp, sz, vp]),  # handle, d_in, d_out, batch, stream
+    "set_window": (ci, [vp, vp, vp]),
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -113,8 +119,9 @@ HILBERT_SYMBOLS = list(_signatures(_HILBERT))
 CZT_SYMBOLS = list(_signatures(_CZT))
 PFB_SYMBOLS = list(_signatures(_PFB))
 IPFB_SYMBOLS = list(_signatures(_IPFB))
+RESAMPLE_SYMBOLS = list(_signatures(_RESAMPLE))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -124,7 +131,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT, _PFB, _IPFB):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -26,6 +26,7 @@
 #include "czt_plan.h"
 #include "pfb_plan.h"
 #include "ipfb_plan.h"
+#include "resample_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -580,6 +581,37 @@ FOURIER_DEFINE_PFB_ABI(double, double)
 
 FOURIER_DEFINE_IPFB_ABI(float, float)
 FOURIER_DEFINE_IPFB_ABI(double, double)
+
+// Fourier-domain resampling of complex or real rows (fourier_hip_resample_*)
+#define FOURIER_DEFINE_RESAMPLE_ABI(T, SUFFIX)                                                                   \
+  FOURIER_DEFINE_HANDLE_ABI(resample, fourier_resample_##SUFFIX, ResamplePlan<T>, SUFFIX)                        \
+  extern "C" fc::fourier_resample_##SUFFIX* fourier_hip_resample_create_##SUFFIX(size_t n_in, size_t n_out, int real_input, int device) { \
+    return (fc::fourier_resample_##SUFFIX*)create_handle<ResamplePlan<T>>(n_in, n_out, real_input, device);      \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_resample_size_in_##SUFFIX(const fc::fourier_resample_##SUFFIX* h) {              \
+    return h ? ((const ResamplePlan<T>*)h)->size_in() : 0;                                                       \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_resample_size_out_##SUFFIX(const fc::fourier_resample_##SUFFIX* h) {             \
+    return h ? ((const ResamplePlan<T>*)h)->size_out() : 0;                                                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_resample_real_input_##SUFFIX(const fc::fourier_resample_##SUFFIX* h) {              \
+    return h ? (int)((const ResamplePlan<T>*)h)->real_input() : 0;                                               \
+  }                                                                                                              \
+  extern "C" int fourier_hip_resample_forward_##SUFFIX(const fc::fourier_resample_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                       size_t batch, void* stream) {                             \
+    const ResamplePlan<T>* p = (const ResamplePlan<T>*)h;                                                        \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, batch, (hipStream_t)stream); });                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_resample_set_window_##SUFFIX(fc::fourier_resample_##SUFFIX* h, const void* d_window, void* stream) { \
+    ResamplePlan<T>* p = (ResamplePlan<T>*)h;                                                                    \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_resample_set_option_##SUFFIX(fc::fourier_resample_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<ResamplePlan<T>>(h, key, v);                                                        \
+  }
+
+FOURIER_DEFINE_RESAMPLE_ABI(float, float)
+FOURIER_DEFINE_RESAMPLE_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -200,6 +200,7 @@ typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
 typedef void (*HilbertKernel)(HilbertArgs);
 typedef void (*CztKernel)(CztArgs);
+typedef void (*ResampleKernel)(ResampleArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -313,6 +314,8 @@ template <typename T> struct Real {};
   /* sweeps of the composed route, which = CZT_IN / CZT_OUT */                                                          \
   bool get_czt_small_kernel(Real<T>, int k, bool real_input, KernelInfo& info);                                        \
   CztKernel get_czt_kernel(Real<T>, int which);                                                                        \
+  /* kernels_resample.cpp: the sweeps of the resampling handle, which = RESAMPLE_REMAP / RESAMPLE_UNTANGLE */                 \
+  ResampleKernel get_resample_kernel(Real<T>, int which);                                                              \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

@@ -418,6 +418,35 @@ struct IpfbArgs {
   double scale;               // 1 / channels (the inner inverse runs unscaled), applied to the finished sum
 };
 
+// ---- Fourier-domain resampling (kernels_resample.h; ResamplePlan, resample_plan.h): rows of n values -> rows of m values, K = min(n, m),
+// kh = K / 2.  Byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of either side per launch); `win` is NULL for no window.
+// resample_remap_kernel: one lane per output bin over a flat index of rows x orow.  Complex rows (half = 0): spectra of n values ->
+// spectra of m values, Y[f mod m] = X[f mod n] win[f mod n] * scale for 2 |f| < K and the rule of include/fourier.h for an even K's bin
+// kh, zeros elsewhere.  Half spectra (half = 1): rows of n / 2 + 1 -> rows of m / 2 + 1, Y[k] = X[k] win[k] * scale for 2 k < K,
+// Y[kh] = X[kh] win[kh] * scale * nyq for an even K, zeros above; win is the folded window of n / 2 + 1 reals.
+// resample_untangle_kernel (n = 2 hn, m = 2 hm): the hn values Z of the forward inner transform of a row -> the hm values the inverse
+// inner transform takes, one lane per pair (j, hm - j), j <= hm / 2: `pairs` lanes a row.
+enum { RESAMPLE_REMAP = 0, RESAMPLE_UNTANGLE = 1 };
+enum { RESAMPLE_SAME = 0, RESAMPLE_DOWN = 1, RESAMPLE_UP = 2 };  // m == n, m < n, n < m
+struct ResampleArgs {
+  const void* in; void* out;
+  const void* win;            // remap, complex rows: n reals; remap, half spectra, and untangle: n / 2 + 1 reals (folded); or NULL
+  const void* tw_in;          // untangle: W_n^j, j <= n / 4 (real_untangle_twiddles)
+  const void* tw_out;         // untangle: W_m^j, j <= m / 4
+  uint32_t n, m;              // values per row of the signal: in, out
+  uint32_t irow, orow;        // remap: values per row of the two spectra; untangle: hn, hm
+  uint32_t kh;                // K / 2
+  uint32_t even;              // K is even: the bin kh takes the Nyquist rule
+  uint32_t mode;              // RESAMPLE_SAME / DOWN / UP
+  uint32_t half;              // remap: the rows are half spectra
+  uint32_t pairs;             // untangle: hm / 2 + 1
+  uint32_t total;             // remap: rows * orow; untangle: rows * pairs
+  uint32_t div_m, div_l;      // idx / orow (remap) or idx / pairs (untangle) = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  double nyq;                 // half spectra and untangle: the factor of the bin kh -- 1, 2 (m < n) or 1/2 (n < m)
+  double scale;               // 1 / n, computed in T: m / n times the inverse's 1 / m
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

@@ -1265,6 +1265,119 @@ def envelope(x, dim=-1, out=None):
     return _hilbert(x, None, dim, out, False)
 
 
+class Resample(_Handle):
+    """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
+    n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an
+    array of n_in reals in FFT order, or no window.  Real rows (real_input=True, the default) or complex rows of the handle's precision.
+    ONE exception to scipy 1.15: complex rows with n_out == 2 < n_in add X[n_in - 1] into bin 1 as every other even length does (scipy's
+    slice is empty there), so that complex rows with zero imaginary part agree with real rows.  scipy's `t`, domain="freq" and window
+    names or callables are not offered."""
+
+    _prefix = "fourier_hip_resample_"
+    _destroy = "fourier_hip_resample_destroy"
+
+    def __init__(self, n_in, n_out, real="f32", device=-1, real_input=True):
+        n_in, n_out = int(n_in), int(n_out)
+        if n_in < 1 or n_out < 1:
+            raise ValueError(f"need n_in >= 1 and n_out >= 1, got {n_in}, {n_out}")
+        self._create(real, f"resampling plan of {n_in} -> {n_out} values", n_in, n_out, int(bool(real_input)), int(device))
+        self._n, self._m, self.real_input = n_in, n_out, bool(real_input)
+
+    def size_in(self):
+        return self._n
+
+    def size_out(self):
+        return self._m
+
+    def set_option(self, key, value):
+        """"fusion": 1 (default) = the fused untangle route (real rows, n_in and n_out both even: one sweep between the two inner
+        transforms), 0 = the composed route.  Accepted without effect where there is no fused route."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def set_window_ptr(self, d_window, stream=0):
+        """size_in() reals of the handle's precision at d_window, FFT order (0 / None: no window).  Waits for `stream`."""
+        self._call("set_window", d_window or None, stream)
+
+    def forward_ptr(self, d_in, d_out, batch, stream=0):
+        """`batch` rows of size_in() values at d_in -> `batch` rows of size_out() values at d_out (no overlap), enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(batch), stream)
+
+    def set_window(self, window):
+        """A contiguous CUDA tensor of size_in() reals of the handle's precision in FFT order (DC first), or None for no window; on the
+        current stream.  The handle keeps a copy."""
+        if window is None:
+            return self.set_window_ptr(None)
+        _require_cuda(window, _torch_dtypes(self.real)[0])
+        if tuple(window.shape) != (self._n,):
+            raise ValueError(f"window must have shape ({self._n},), got {tuple(window.shape)}")
+        self.set_window_ptr(window.data_ptr(), _stream(window))
+
+    def forward(self, x, out=None):
+        """Contiguous (..., n_in) CUDA tensor, float (real_input) or complex of the handle's precision -> a new (..., n_out) tensor of
+        the same dtype, or `out` (which may not overlap `x`), on the current stream."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        dt = rdt if self.real_input else cdt
+        _require_cuda(x, dt)
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        shape = tuple(x.shape[:-1]) + (self._m,)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=x.device)
+        else:
+            _require_out(out, shape, dt, x.device)
+        batch = x.numel() // self._n
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+
+def create_resample_f32(n_in, n_out, real_input=True, device=-1):
+    return Resample(n_in, n_out, "f32", device, real_input)
+
+
+def create_resample_f64(n_in, n_out, real_input=True, device=-1):
+    return Resample(n_in, n_out, "f64", device, real_input)
+
+
+def resample(x, num, window=None, dim=-1, out=None):
+    """scipy.signal.resample(x, num, axis=dim, window=window) of a CUDA tensor on the current stream: float32 / float64 (real rows) or
+    complex64 / complex128 (complex rows); `window` is None or a CUDA tensor of x.shape[dim] reals of the same precision in FFT order.
+    Returns a new tensor of the input's dtype with `num` values along `dim`, or `out`.  Only the last dimension of a contiguous tensor
+    is native; any other `dim` or layout is moved last with a torch copy.  One cached Resample handle per (n_in, num, dtype, device);
+    a call with a window uses a handle of its own that is not cached.  One exception to scipy 1.15: complex rows with num == 2 <
+    x.shape[dim] add the bin N - 1 into bin 1, as real rows do (include/fourier.h)."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None):
+        raise TypeError("expected a CUDA float32 / float64 / complex64 / complex128 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    d = _normalise_dims(x.dim(), (dim,))[0]
+    n, num = int(x.shape[d]), int(num)
+    if n < 1 or num < 1:
+        raise ValueError(f"the resampled dimension must have length >= 1 and num >= 1, got {n}, {num}")
+    real, real_input = _precision(x.dtype)
+    shape = tuple(x.shape[:d]) + (num,) + tuple(x.shape[d + 1:])
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == shape and out.device == x.device):
+        raise TypeError(f"out must be a CUDA {_names((x.dtype,))} tensor of shape {shape} on the input's device")
+    if window is None:
+        plan = _cached_plan(Resample, n, num, real, int(_device_index(x)), real_input)
+    else:
+        if not (_is_torch(window) and window.is_cuda and window.dtype == _torch_dtypes(real)[0] and window.device == x.device):
+            raise TypeError(f"window must be a CUDA {_names((_torch_dtypes(real)[0],))} tensor on the input's device")
+        plan = Resample(n, num, real, int(_device_index(x)), real_input)
+        plan.set_window(window.contiguous())
+    if d == x.dim() - 1 and x.is_contiguous() and (out is None or out.is_contiguous()):
+        return plan.forward(x, out)
+    res = plan.forward(x.movedim(d, -1).contiguous()).movedim(-1, d)
+    if out is None:
+        return res.contiguous()
+    out.copy_(res)
+    return out
+
+
 class Czt(_Handle):
     """Batched chirp-z transform (include/fourier.h, fourier_hip_czt_*) on device memory: of rows of n values x (complex, or reals with
     real_input=True) the m values X[k] = sum_j x[j] a**-j w**(j k), with w = w_abs exp(2 pi i w_turns) and a = a_abs exp(2 pi i a_turns)

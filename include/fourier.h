@@ -1200,6 +1200,77 @@ const char *fourier_hip_ipfb_describe_double(const FOURIER_STRUCT fourier_ipfb_d
 int fourier_hip_ipfb_last_status_float(const FOURIER_STRUCT fourier_ipfb_float *);
 int fourier_hip_ipfb_last_status_double(const FOURIER_STRUCT fourier_ipfb_double *);
 
+/* ---------------- Fourier-domain resampling (extension; the reference has none) ----------------
+ * `batch` contiguous rows of N = n_in values x on DEVICE memory -> `batch` contiguous rows of M = n_out values y: the row's spectrum
+ * cut or zero-padded to M bins and transformed back.  K = min(N, M).  W is an optional window of N reals in FFT order (DC first);
+ * absent (the default) means all ones.
+ * Complex rows (real_input = 0, interleaved complex values):
+ *   X = fft_N(x) * W, Y = M zeros;  Y[f mod M] = X[f mod N] for every signed frequency f with 2 |f| < K;  for an even K, h = K / 2:
+ *   M < N: Y[h] = X[h] + X[N-h];   N < M: Y[h] = Y[M-h] = X[h] / 2;   N == M: Y[h] = X[h];   y = ifft_M(Y) * M / N.
+ * Real rows (real_input = 1):
+ *   X = rfft_N(x) * Wr, Wr[0] = W[0], Wr[k] = (W[k] + W[N-k]) / 2;  Y = M / 2 + 1 zeros;  Y[k] = X[k] for 2 k < K;  for an even K,
+ *   Y[K/2] = X[K/2] * c with c = 2 for M < N, 1/2 for N < M, 1 for N == M;  y = irfft_M(Y) * M / N (the imaginary parts of bin 0 and of
+ *   an even M's bin M / 2 are dropped, as irfft does).
+ * This is scipy.signal.resample(x, M, axis=-1, window=W) with W given as an array, with ONE exception: for complex rows with
+ * M == 2 < N scipy 1.15 does not add X[N-1] into Y[1] (a slice expression in its source is empty there); the rule above does, so that
+ * complex rows whose imaginary part is zero agree with real rows.  scipy's `t`, domain='freq' and window names or callables have no
+ * counterpart here.
+ * Window: fourier_hip_resample_set_window_*(h, d_window, stream) takes n_in reals T on the device; NULL clears the window.  The handle
+ * keeps a copy of its own (real rows: the folded Wr).  A set-up call: it waits for `stream`.
+ * Routes (fourier_hip_resample_describe_*), chosen at create:
+ *   "resample complex: ..."              complex rows: the N-point plan into a handle-owned scratch, one remap sweep into the output
+ *                                        with the window, the rule of the bin K/2 and 1/N folded in, the M-point unscaled inverse in place
+ *   "resample real composed: ..."        real rows: the real-input plan of N points, the remap sweep on half spectra, the real-input
+ *                                        plan of M points
+ *   "resample real fused untangle: ..."  real rows, N and M both even: the N/2-point inner plan, ONE sweep that does the work of the
+ *                                        forward untangle, the remap and the inverse untangle, the M/2-point inner plan
+ * Option "fusion" (fourier_hip_resample_set_option_*): 1 (the default: it measured faster at every shape) selects
+ * the fused untangle route where it exists, 0 the composed one; on the other routes it is accepted and changes nothing.  Any other
+ * key or value: FOURIER_HIP_INVALID_ARGUMENT.
+ * create gives NULL for a length of 0 or a real_input flag outside {0, 1} (invalid) and for lengths beyond what the inner plans or
+ * one sweep launch serve (2^31 - 1 bytes of a row's spectrum: unsupported).
+ * A NULL handle or pointer, a buffer not aligned to its element (sizeof(T) for real rows, which may start on any T; 2 * sizeof(T) for
+ * complex rows), or any overlap of d_in and d_out (in place included) give FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful
+ * no-op.  The input is not modified.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.  The batch is walked in chunks
+ * of a handle-owned scratch of at most 1 GiB (never less than one row); there are no atomics, so the result does not depend on the
+ * chunking and repeated calls give the same bits.  fourier_hip_resample_reserve_*(h, batch) sizes everything calls of at most `batch`
+ * rows need on the current route: they then never allocate.  NULL-handle calls return 0 from the getters, "" from describe and
+ * FOURIER_HIP_INVALID_ARGUMENT from the rest.  Handles are Send, not Sync, like the complex ones; status of the last call:
+ * fourier_hip_resample_last_status_*. */
+struct fourier_resample_float;
+struct fourier_resample_double;
+
+/* NULL on failure (parameters outside the ranges above included). */
+struct fourier_resample_float *fourier_hip_resample_create_float(FOURIER_SIZE_TYPE n_in, FOURIER_SIZE_TYPE n_out, int real_input,
+                                                                 int device);
+struct fourier_resample_double *fourier_hip_resample_create_double(FOURIER_SIZE_TYPE n_in, FOURIER_SIZE_TYPE n_out, int real_input,
+                                                                   int device);
+/* NULL is a no-op. */
+void fourier_hip_resample_destroy_float(FOURIER_STRUCT fourier_resample_float *);
+void fourier_hip_resample_destroy_double(FOURIER_STRUCT fourier_resample_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_resample_size_in_float(const FOURIER_STRUCT fourier_resample_float *);
+FOURIER_SIZE_TYPE fourier_hip_resample_size_in_double(const FOURIER_STRUCT fourier_resample_double *);
+FOURIER_SIZE_TYPE fourier_hip_resample_size_out_float(const FOURIER_STRUCT fourier_resample_float *);
+FOURIER_SIZE_TYPE fourier_hip_resample_size_out_double(const FOURIER_STRUCT fourier_resample_double *);
+int fourier_hip_resample_real_input_float(const FOURIER_STRUCT fourier_resample_float *);
+int fourier_hip_resample_real_input_double(const FOURIER_STRUCT fourier_resample_double *);
+int fourier_hip_resample_forward_float(const FOURIER_STRUCT fourier_resample_float *, const void *d_in, void *d_out,
+                                       FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_resample_forward_double(const FOURIER_STRUCT fourier_resample_double *, const void *d_in, void *d_out,
+                                        FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_resample_set_window_float(FOURIER_STRUCT fourier_resample_float *, const void *d_window, void *stream);
+int fourier_hip_resample_set_window_double(FOURIER_STRUCT fourier_resample_double *, const void *d_window, void *stream);
+int fourier_hip_resample_reserve_float(const FOURIER_STRUCT fourier_resample_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_resample_reserve_double(const FOURIER_STRUCT fourier_resample_double *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_resample_set_option_float(FOURIER_STRUCT fourier_resample_float *, const char *key, long long value);
+int fourier_hip_resample_set_option_double(FOURIER_STRUCT fourier_resample_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_resample_describe_float(const FOURIER_STRUCT fourier_resample_float *);
+const char *fourier_hip_resample_describe_double(const FOURIER_STRUCT fourier_resample_double *);
+int fourier_hip_resample_last_status_float(const FOURIER_STRUCT fourier_resample_float *);
+int fourier_hip_resample_last_status_double(const FOURIER_STRUCT fourier_resample_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
