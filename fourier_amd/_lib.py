@@ -67,6 +67,13 @@ _CSD = ("fourier_hip_csd_", {  # cross-spectral density and coherence of two sig
     "csd": (ci, [vp, vp, vp, vp, sz, sz, ci, ctypes.c_double, vp]),  # handle, d_x, d_y, d_out, length, batch, onesided_fold, scale, stream
     "coherence": (ci, [vp, vp, vp, vp, sz, sz, vp]),                 # handle, d_x, d_y, d_out, length, batch, stream
     "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_BANDSPEC = ("fourier_hip_bandspec_", {  # band-energy (mel) spectrogram: a sparse-row projection of |X|^p on the STFT's frames
+    "create": (vp, [sz, sz, sz, ci, sz, ci]),  # n_fft, hop, win_length, pad_mode, bands, device
+    "destroy": (None, [vp]), "n_fft": (sz, [vp]), "hop": (sz, [vp]), "win_length": (sz, [vp]), "bins": (sz, [vp]), "bands": (sz, [vp]),
+    "frames": (sz, [vp, sz]), "set_window": (ci, [vp, vp, vp]),
+    "set_bands": (ci, [vp, vp, vp]),  # handle, h_matrix (HOST, bands x bins reals), stream
+    "forward": (ci, [vp, vp, vp, sz, sz, ci, ci, ctypes.c_double, ctypes.c_double, vp]),  # handle, d_in, d_out, length, batch, power, normalized, log_mult, log_floor, stream
+    "reserve": (ci, [vp, sz, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _HILBERT = ("fourier_hip_hilbert_", {  # analytic signal and envelope of real rows
     "create": (vp, [sz, ci]), "destroy": (None, [vp]), "size": (sz, [vp]),
     "analytic": (ci, [vp, vp, vp, sz, vp]), "envelope": (ci, [vp, vp, vp, sz, vp]),  # handle, d_in, d_out, batch, stream
@@ -115,13 +122,14 @@ STFT_SYMBOLS = list(_signatures(_STFT))
 MDCT_SYMBOLS = list(_signatures(_MDCT))
 SPECTROGRAM_SYMBOLS = list(_signatures(_SPECTROGRAM))
 CSD_SYMBOLS = list(_signatures(_CSD))
+BANDSPEC_SYMBOLS = list(_signatures(_BANDSPEC))
 HILBERT_SYMBOLS = list(_signatures(_HILBERT))
 CZT_SYMBOLS = list(_signatures(_CZT))
 PFB_SYMBOLS = list(_signatures(_PFB))
 IPFB_SYMBOLS = list(_signatures(_IPFB))
 RESAMPLE_SYMBOLS = list(_signatures(_RESAMPLE))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -131,7 +139,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

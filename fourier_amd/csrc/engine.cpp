@@ -22,6 +22,7 @@
 #include "mdct_plan.h"
 #include "spectrogram_plan.h"
 #include "csd_plan.h"
+#include "bandspec_plan.h"
 #include "hilbert_plan.h"
 #include "czt_plan.h"
 #include "pfb_plan.h"
@@ -447,6 +448,50 @@ FOURIER_DEFINE_SPECTROGRAM_ABI(double, double)
 
 FOURIER_DEFINE_CSD_ABI(float, float)
 FOURIER_DEFINE_CSD_ABI(double, double)
+
+// band-energy (mel) spectrogram on the STFT's frames (fourier_hip_bandspec_*)
+#define FOURIER_DEFINE_BANDSPEC_ABI(T, SUFFIX)                                                                   \
+  extern "C" fc::fourier_bandspec_##SUFFIX* fourier_hip_bandspec_create_##SUFFIX(size_t n_fft, size_t hop, size_t win_length, int pad_mode, \
+                                                                                size_t bands, int device) {      \
+    return (fc::fourier_bandspec_##SUFFIX*)create_handle<BandSpecPlan<T>>(n_fft, hop, win_length, pad_mode, bands, device); \
+  }                                                                                                              \
+  extern "C" void fourier_hip_bandspec_destroy_##SUFFIX(fc::fourier_bandspec_##SUFFIX* h) { destroy_handle<BandSpecPlan<T>>(h); } \
+  extern "C" const char* fourier_hip_bandspec_describe_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return describe_handle<BandSpecPlan<T>>(h); } \
+  extern "C" int fourier_hip_bandspec_last_status_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return last_status_of<BandSpecPlan<T>>(h); } \
+  extern "C" int fourier_hip_bandspec_set_option_##SUFFIX(fc::fourier_bandspec_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<BandSpecPlan<T>>(h, key, v);                                                        \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_bandspec_n_fft_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return h ? ((const BandSpecPlan<T>*)h)->n_fft() : 0; } \
+  extern "C" size_t fourier_hip_bandspec_hop_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return h ? ((const BandSpecPlan<T>*)h)->hop() : 0; } \
+  extern "C" size_t fourier_hip_bandspec_win_length_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) {           \
+    return h ? ((const BandSpecPlan<T>*)h)->win_length() : 0;                                                    \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_bandspec_bins_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return h ? ((const BandSpecPlan<T>*)h)->bins() : 0; } \
+  extern "C" size_t fourier_hip_bandspec_bands_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h) { return h ? ((const BandSpecPlan<T>*)h)->bands() : 0; } \
+  extern "C" size_t fourier_hip_bandspec_frames_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h, size_t length) { \
+    return h ? ((const BandSpecPlan<T>*)h)->frames(length) : 0;                                                  \
+  }                                                                                                              \
+  extern "C" int fourier_hip_bandspec_set_window_##SUFFIX(fc::fourier_bandspec_##SUFFIX* h, const void* d_window, void* stream) { \
+    BandSpecPlan<T>* p = (BandSpecPlan<T>*)h;                                                                    \
+    return guarded_handle(p, [&] { p->set_window(d_window, (hipStream_t)stream); });                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_bandspec_set_bands_##SUFFIX(fc::fourier_bandspec_##SUFFIX* h, const void* h_matrix, void* stream) { \
+    BandSpecPlan<T>* p = (BandSpecPlan<T>*)h;                                                                    \
+    return guarded_handle(p, [&] { p->set_bands(h_matrix, (hipStream_t)stream); });                              \
+  }                                                                                                              \
+  extern "C" int fourier_hip_bandspec_reserve_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h, size_t length, size_t batch) { \
+    const BandSpecPlan<T>* p = (const BandSpecPlan<T>*)h;                                                        \
+    return guarded_handle(p, [&] { p->reserve(length, batch); });                                                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_bandspec_forward_##SUFFIX(const fc::fourier_bandspec_##SUFFIX* h, const void* d_in, void* d_out, size_t length, \
+                                                       size_t batch, int power, int normalized, double log_mult, double log_floor, \
+                                                       void* stream) {                                           \
+    const BandSpecPlan<T>* p = (const BandSpecPlan<T>*)h;                                                        \
+    return guarded_handle(p, [&] { p->forward(d_in, d_out, length, batch, power, normalized != 0, log_mult, log_floor, (hipStream_t)stream); }); \
+  }
+
+FOURIER_DEFINE_BANDSPEC_ABI(float, float)
+FOURIER_DEFINE_BANDSPEC_ABI(double, double)
 
 // analytic signal and envelope of real rows (fourier_hip_hilbert_*)
 #define FOURIER_DEFINE_HILBERT_ABI(T, SUFFIX)                                                                    \

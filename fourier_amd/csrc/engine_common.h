@@ -175,6 +175,7 @@ typedef void (*StftKernel)(StftArgs);
 typedef void (*MdctKernel)(MdctArgs);
 typedef void (*SpectrogramKernel)(SpectrogramArgs);
 typedef void (*CsdKernel)(CsdArgs);
+typedef void (*BandSpecKernel)(BandSpecArgs);
 typedef void (*PfbKernel)(PfbArgs);
 typedef void (*IpfbKernel)(IpfbArgs);
 // The fused frame route of a frame handle (STFT, MDCT, spectrogram, cross spectrum, polyphase filter bank) on a whole-row kernel's tile shape (kernels_frames.h): the kernels of
@@ -189,12 +190,14 @@ typedef FrameRowsKernel<StftArgs> StftRowsKernel;
 typedef FrameRowsKernel<MdctArgs> MdctRowsKernel;
 typedef FrameRowsKernel<SpectrogramArgs> SpectrogramRowsKernel;
 typedef FrameRowsKernel<CsdArgs> CsdRowsKernel;
+typedef FrameRowsKernel<BandSpecArgs> BandSpecRowsKernel;  // fn[SPEC_MAGNITUDE], fn[SPEC_POWER]
 typedef FrameRowsKernel<PfbArgs> PfbRowsKernel;
 // the part of a frame kernel's argument block that holds the frame geometry and the row core's stage tables
 static inline StftArgs& frame_block(StftArgs& a) { return a; }
 static inline MdctArgs& frame_block(MdctArgs& a) { return a; }
 static inline StftArgs& frame_block(SpectrogramArgs& a) { return a.f; }
 static inline StftArgs& frame_block(CsdArgs& a) { return a.f; }
+static inline StftArgs& frame_block(BandSpecArgs& a) { return a.f; }
 static inline PfbArgs& frame_block(PfbArgs& a) { return a; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
@@ -298,6 +301,10 @@ template <typename T> struct Real {};
   /* frame route for n_fft = 2 L on the whole-row kernel of length L                                                   */ \
   CsdKernel get_csd_kernel(Real<T>, int which);                                                                        \
   CsdRowsKernel get_csd_rows_kernel(Real<T>, int L);                                                                   \
+  /* kernels_bandspec.cpp: the band sweep of the band-spectrogram handle's composed route; its fused frame route for     */ \
+  /* n_fft = 2 L on the whole-row kernel of length L, one kernel per power                                             */ \
+  BandSpecKernel get_bandspec_kernel(Real<T>);                                                                         \
+  BandSpecRowsKernel get_bandspec_rows_kernel(Real<T>, int L);                                                         \
   /* kernels_pfb.cpp: the fold sweep of the polyphase filter bank handle's composed route; its fused frame routes on the */ \
   /* whole-row kernel of length L: complex rows of P = L channels, real rows of P = 2 L                                */ \
   PfbKernel get_pfb_kernel(Real<T>);                                                                                   \
@@ -357,6 +364,7 @@ template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L,
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, MdctRowsKernel& k) { k = get_mdct_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, SpectrogramRowsKernel& k) { k = get_spectrogram_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, CsdRowsKernel& k) { k = get_csd_rows_kernel(r, L); }
+template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, BandSpecRowsKernel& k) { k = get_bandspec_rows_kernel(r, L); }
 template <typename T> static inline void get_frame_rows_kernel(Real<T> r, int L, PfbRowsKernel& k) { k = get_pfb_rows_kernel(r, L); }
 
 }  // namespace fourier_hip

@@ -744,7 +744,7 @@ template <typename T> class Pow2Engine {
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
   KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
-  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel> frame_rows_;
+  std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel, BandSpecRowsKernel> frame_rows_;
   FusedInfo fused_;
   bool fused_on_ = false;
   bool prefetch_last_ = false;

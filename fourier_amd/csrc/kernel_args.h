@@ -279,6 +279,23 @@ struct CsdArgs {
   double scale;               // reduce: the caller's scale over frames
 };
 
+// ---- band-energy (mel) spectrogram (kernels_bandspec.h; BandSpecPlan, bandspec_plan.h)
+// `f` is the STFT's argument block.  The bank is a sparse-row matrix of `bands` x `bins` reals: row j has its support at the columns
+// lo[j] ... lo[j] + (off[j + 1] - off[j]) - 1 and its weights, zeros inside the support included, at w + off[j].  Item i of a launch
+// writes `bands` reals at f.out + i * bands: y_j = sum_k w_j[k] |X[k]|^power in ascending k in one accumulator, then, log_mult != 0,
+// log_mult * ln(max(y_j, log_floor)).  bandspec_rows_kernel reads f as stft_rows_kernel does; bandspec_sweep_kernel has one lane per
+// (frame, band) of `count` = frames * bands over the transformed frames at f.in (frame i at i * bins complex values).
+struct BandSpecArgs {
+  StftArgs f;
+  const void* lo;             // uint32_t[bands]: first column of a row's support
+  const void* off;            // uint32_t[bands + 1]: start of a row's weights in w
+  const void* w;              // the packed weights, reals T
+  uint32_t bins, bands;
+  uint32_t power;             // sweep: SPEC_MAGNITUDE / SPEC_POWER
+  uint64_t count;             // sweep: lanes
+  double log_mult, log_floor;
+};
+
 // ---- modified discrete cosine transform (kernels_mdct.h; MdctPlan, mdct_plan.h)
 // A frame is 2n samples, the hop n; frame f of a row covers xpad[f n - pad ... f n - pad + 2n), zero outside the row.  The flat frame
 // index, `first`, `total` and the multiply-high division are StftArgs'.  Even n = 2h: a frame is h complex values in the scratch

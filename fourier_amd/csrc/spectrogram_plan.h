@@ -15,7 +15,7 @@
 // one frame; the partials are a buffer of their own under the same bound, never less than one row's, the rows walked in groups that fit.
 // No atomics: the order of every sum is fixed by (route, shape, chunking), so equal calls give bit-equal results.
 #pragma once
-#include "stft_plan.h"
+#include "frame_scratch.h"
 
 namespace fourier_hip {
 
@@ -29,7 +29,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     stft_.reset(new StftPlan<T>(n_fft, hop, win_length, pad_mode, device));
     device_ = stft_->real().inner().device();
     DeviceGuard g(device_);
-    scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    scratch_cap_ = frames_.cap = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     // Where the fused route is the default: nowhere yet.  The project's rule is that a default follows a measurement (the STFT's fused
     // route became one after tools/stft_bench.py), and tools/spectrogram_bench.py has not run on an MI355X -- DESIGN.md section 4, "Power
     // spectrogram and Welch average".  Option "fusion" = 1 selects the fused kernels wherever they exist.
@@ -91,7 +91,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     const int code = normalized ? ::fourier::c::FOURIER_TRANSFORM_SQRT_SCALED_FFT : ::fourier::c::FOURIER_TRANSFORM_FFT;
     for_chunks(total, chunk, [&](size_t g0, size_t ng) {
       transform_chunk(a, in, length, fr, g0, ng, chunk, code, stream);
-      a.f.in = spectra(chunk);
+      a.f.in = frames_.spectra();
       a.f.out = out + g0 * bins;
       a.count = ng * bins;
       FOURIER_LAUNCH(get_spectrogram_kernel(Real<T>{}, SPECTROGRAM_POWER_SWEEP), elementwise_grid(a.count), 256, 0, stream, a);
@@ -127,7 +127,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
         for_chunks(nb * fr, chunk, [&](size_t g0, size_t ng) {
           transform_chunk(a, in + b0 * length, length, fr, g0, ng, chunk, ::fourier::c::FOURIER_TRANSFORM_FFT, stream);
           const size_t g_last = g0 + ng - 1, r0 = g0 / fr, r1 = g_last / fr;
-          a.f.in = spectra(chunk);
+          a.f.in = frames_.spectra();
           a.g0 = g0; a.g1 = g0 + ng;
           a.slot0 = r0 * tiles + (g0 - r0 * fr) / WELCH_TILE;
           a.count = (r1 * tiles + (g_last - r1 * fr) / WELCH_TILE - a.slot0 + 1) * bins;
@@ -157,29 +157,18 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     return rows_per;
   }
   // frames per chunk of the composed routes; sizes the scratch (bins complex + n_fft reals per frame) and RealPlan's buffers
-  size_t prepare_frames(size_t total) const {
-    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, bins() * ELEM + n_fft() * sizeof(T)), LAUNCH_ITEMS);
-    scratch_.ensure(chunk * (bins() * ELEM + n_fft() * sizeof(T)));
-    stft_->real().reserve(chunk);
-    return chunk;
-  }
-  // the scratch of a chunk: the transformed frames first (aligned as complex values), the windowed frames behind them
-  cpx<T>* spectra(size_t) const { return (cpx<T>*)scratch_.p; }
-  T* gathered(size_t chunk) const { return (T*)((cpx<T>*)scratch_.p + chunk * bins()); }
-  // frames g0 ... g0 + ng - 1 of the flat frame index counted from the row at `in`: gathered, windowed, transformed into spectra()
+  size_t prepare_frames(size_t total) const { return frames_.prepare(*stft_, total); }
+  // frames g0 ... g0 + ng - 1 of the flat frame index counted from the row at `in`: gathered, windowed, transformed into frames_.spectra()
   void transform_chunk(SpectrogramArgs& a, const T* in, size_t length, size_t fr, size_t g0, size_t ng, size_t chunk, int code,
                        hipStream_t stream) const {
-    StftArgs f = a.f;
-    frame_launch_at(f, in, length, fr, g0, ng);
-    f.out = gathered(chunk);
-    FOURIER_LAUNCH(get_stft_kernel(Real<T>{}, STFT_FRAME), ng, 256, 0, stream, f);
-    stft_->real().run_forward(gathered(chunk), spectra(chunk), ng, code, stream);
+    frames_.transform_chunk(*stft_, a.f, in, length, fr, g0, ng, chunk, code, stream);
   }
 
   std::unique_ptr<StftPlan<T>> stft_;
   int device_ = 0;
   FusionSwitch fusion_;
-  mutable DevBuf scratch_, part_;
+  FrameScratch<T> frames_;  // the composed routes' scratch (frame_scratch.h)
+  mutable DevBuf part_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
 };
 

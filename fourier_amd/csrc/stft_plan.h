@@ -61,6 +61,7 @@ template <typename T> class StftPlan : public HandleBase {
   const RealPlan<T>& real() const { return *real_; }
   bool enable_spectrogram() { return real_->template enable_frames<SpectrogramArgs>(); }
   bool enable_csd() { return real_->template enable_frames<CsdArgs>(); }  // ... and the cross-spectrum handle (csd_plan.h)
+  bool enable_bandspec() { return real_->template enable_frames<BandSpecArgs>(); }  // ... and the band-spectrogram handle (bandspec_plan.h)
   // the argument block of a forward launch, all but in, out, first, total (and the fused route's tw, scale, pairs)
   StftArgs frame_args(size_t length, size_t fr) const {
     StftArgs a{};

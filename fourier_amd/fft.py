@@ -1154,6 +1154,253 @@ def coherence(x, y, fs=1.0, window=None, nperseg=256, noverlap=None):
     return freqs, p.coherence(x.contiguous(), y.contiguous())
 
 
+class BandSpectrogram(_Handle):
+    """Batched band-energy spectrogram (include/fourier.h, fourier_hip_bandspec_*) on device memory: the |X|^p of the frames X an Stft of
+    the same parameters gives, projected onto the rows of a real `bands` x bins matrix W -- a mel bank (mel_filterbank), or any matrix
+    whose rows have short supports; negative weights are allowed -- Y[b, f, j] = sum_k W[j, k] |X[b, f, k]|^p, optionally
+    log_mult * ln(max(Y, log_floor)), FRAME-MAJOR reals (frame f of row b at element offset (b * frames + f) * bands).  |X|^p is never
+    written anywhere the caller sees.  n_fft, hop, win_length, the padding and the number of bands are fixed at create; the window
+    (set_window; default all ones) and the bank (set_bands; forward raises without one) are set afterwards."""
+
+    _prefix = "fourier_hip_bandspec_"
+    _destroy = "fourier_hip_bandspec_destroy"
+
+    def __init__(self, n_fft, bands, real="f32", hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+        n_fft, bands = int(n_fft), int(bands)
+        hop = n_fft // 4 if hop_length is None else int(hop_length)
+        wl = n_fft if win_length is None else int(win_length)
+        self.pad_mode = _stft_pad_mode(center, pad_mode)
+        if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+            raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+        if not 1 <= bands <= 65535:
+            raise ValueError(f"need 1 <= bands <= 65535, got {bands}")
+        self._create(real, f"band-spectrogram plan of n_fft {n_fft}, hop {hop}, win_length {wl}, padding {self.pad_mode}, {bands} bands",
+                     n_fft, hop, wl, STFT_PAD_MODES[self.pad_mode], bands, int(device))
+        self._n, self._hop, self._wl, self._bands = n_fft, hop, wl, bands
+
+    # the framing, the window and the options are the spectrogram handle's
+    n_fft, hop, win_length, bins, frames = Spectrogram.n_fft, Spectrogram.hop, Spectrogram.win_length, Spectrogram.bins, Spectrogram.frames
+    set_window_ptr, set_window, _rows = Spectrogram.set_window_ptr, Spectrogram.set_window, Spectrogram._rows
+
+    def bands(self):
+        return self._bands
+
+    def set_option(self, key, value):
+        """"fusion": 0 = the composed route, 1 = the fused one-launch route wherever it exists (bands <= bins; the default there)."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def reserve(self, length, batch):
+        """Later forward calls of at most `batch` rows of `length` reals never allocate (on the route selected now)."""
+        self._call("reserve", int(length), int(batch))
+
+    def set_bands_ptr(self, h_matrix, stream=0):
+        """bands() x bins() reals of the handle's precision, row-major, at the HOST address h_matrix.  Waits for `stream`."""
+        self._call("set_bands", h_matrix, stream)
+
+    def set_bands(self, matrix):
+        """A numpy array or a torch tensor (any device) of shape (bands, bins): moved to the host and cast to the handle's precision.
+        Every weight must be finite.  Replaces the bank in use; waits for the current stream."""
+        import numpy as np
+
+        if _is_torch(matrix):
+            matrix = matrix.detach().cpu().numpy()
+        elif not isinstance(matrix, np.ndarray):
+            raise TypeError("matrix must be a numpy array or a torch tensor")
+        if matrix.dtype.kind not in "fiu":
+            raise TypeError(f"matrix must be real, got {matrix.dtype}")
+        if tuple(matrix.shape) != (self._bands, self.bins()):
+            raise ValueError(f"matrix must have shape ({self._bands}, {self.bins()}), got {tuple(matrix.shape)}")
+        host = np.ascontiguousarray(matrix, dtype=np.float32 if self.real == "f32" else np.float64)
+        if not np.isfinite(host).all():
+            raise ValueError("every band weight must be finite")
+        stream = 0
+        try:
+            import torch
+
+            if torch.cuda.is_available():
+                stream = torch.cuda.current_stream().cuda_stream
+        except Exception:
+            pass
+        self.set_bands_ptr(host.ctypes.data, stream)
+
+    def forward_ptr(self, d_in, d_out, length, batch, power=2, normalized=False, log_mult=0.0, log_floor=0.0, stream=0):
+        """`batch` rows of `length` reals at d_in -> batch x frames(length) x bands() reals at d_out, enqueued on `stream`."""
+        self._call("forward", d_in, d_out, int(length), int(batch), int(power), int(bool(normalized)), float(log_mult), float(log_floor), stream)
+
+    def forward(self, x, power=2, normalized=False, log_mult=0.0, log_floor=0.0, out=None):
+        """Contiguous (..., length) real CUDA tensor -> a new (..., frames, bands) real tensor (frame-major), or `out`, on the current
+        stream.  log_mult 0: the band energies; else log_mult * ln(max(energy, log_floor)) with log_floor > 0."""
+        import math
+
+        import torch
+
+        power = _spectrogram_power(power)
+        log_mult, log_floor = float(log_mult), float(log_floor)
+        if not math.isfinite(log_mult):
+            raise ValueError(f"log_mult must be finite, got {log_mult}")
+        if log_mult != 0.0 and not (math.isfinite(log_floor) and log_floor > 0.0):
+            raise ValueError(f"log_floor must be finite and > 0 when log_mult != 0, got {log_floor}")
+        rdt, length, fr = self._rows(x)
+        shape = tuple(x.shape[:-1]) + (fr, self._bands)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=x.device)
+        else:
+            _require_out(out, shape, rdt, x.device)
+        batch = x.numel() // length
+        if batch:
+            self.forward_ptr(x.data_ptr(), out.data_ptr(), length, batch, power, normalized, log_mult, log_floor, _stream(x))
+        return out
+
+
+def create_bandspec_f32(n_fft, bands, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return BandSpectrogram(n_fft, bands, "f32", hop_length, win_length, center, pad_mode, device)
+
+
+def create_bandspec_f64(n_fft, bands, hop_length=None, win_length=None, center=True, pad_mode="reflect", device=-1):
+    return BandSpectrogram(n_fft, bands, "f64", hop_length, win_length, center, pad_mode, device)
+
+
+MEL_SCALES = ("htk", "slaney")
+MEL_LOGS = (None, "ln", "log10", "db")
+
+
+def _hz_to_mel(f, mel_scale):
+    import numpy as np
+
+    f = np.asarray(f, dtype=np.float64)
+    if mel_scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    lin = f / (200.0 / 3.0)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0), lin)
+
+
+def _mel_to_hz(m, mel_scale):
+    import numpy as np
+
+    m = np.asarray(m, dtype=np.float64)
+    if mel_scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filterbank(n_freqs, f_min, f_max, n_mels, sample_rate, norm=None, mel_scale="htk"):
+    """The triangular mel bank as a numpy float64 (n_mels, n_freqs) matrix: the transpose of
+    torchaudio.functional.melscale_fbanks(n_freqs, f_min, f_max, n_mels, sample_rate, norm, mel_scale).  Column k stands for the
+    frequency k * (sample_rate / 2) / (n_freqs - 1); n_mels + 2 points equally spaced in mel between f_min and f_max give the corners
+    f_pts of the triangles, W[j, k] = max(0, min((f_k - f_pts[j]) / (f_pts[j+1] - f_pts[j]), (f_pts[j+2] - f_k) / (f_pts[j+2] - f_pts[j+1]))).
+    norm "slaney" scales row j by 2 / (f_pts[j+2] - f_pts[j]) (unit area); mel_scale "htk": mel = 2595 log10(1 + f / 700), "slaney":
+    f / (200 / 3) below 1000 Hz and 15 + ln(f / 1000) / (ln(6.4) / 27) from there on."""
+    import numpy as np
+
+    n_freqs, n_mels = int(n_freqs), int(n_mels)
+    f_min, f_max, sample_rate = float(f_min), float(f_max), float(sample_rate)
+    if norm not in (None, "slaney"):
+        raise ValueError(f"norm must be None or 'slaney', got {norm!r}")
+    if mel_scale not in MEL_SCALES:
+        raise ValueError(f"mel_scale must be 'htk' or 'slaney', got {mel_scale!r}")
+    if n_freqs < 2 or n_mels < 1:
+        raise ValueError(f"need n_freqs >= 2 and n_mels >= 1, got {n_freqs}, {n_mels}")
+    if not (sample_rate > 0 and 0 <= f_min < f_max):
+        raise ValueError(f"need sample_rate > 0 and 0 <= f_min < f_max, got {sample_rate}, {f_min}, {f_max}")
+    all_freqs = np.linspace(0.0, sample_rate / 2.0, n_freqs)
+    m_pts = np.linspace(float(_hz_to_mel(f_min, mel_scale)), float(_hz_to_mel(f_max, mel_scale)), n_mels + 2)
+    f_pts = _mel_to_hz(m_pts, mel_scale)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[:, None] - all_freqs[None, :]  # (n_mels + 2, n_freqs)
+    up = -slopes[:-2] / f_diff[:-1, None]
+    down = slopes[2:] / f_diff[1:, None]
+    W = np.maximum(0.0, np.minimum(up, down))
+    if norm == "slaney":
+        W *= (2.0 / (f_pts[2:] - f_pts[:-2]))[:, None]
+    return W
+
+
+def _bandspec_plan(x, matrix, n_fft, hop_length, win_length, window, center, pad_mode, real):
+    """The cached handle of these parameters with `window` and the bank set (on every call, like fftconv's filters)."""
+    import numpy as np
+
+    if not (_is_torch(matrix) or isinstance(matrix, np.ndarray)):
+        raise TypeError("matrix must be a numpy array or a torch tensor")
+    if matrix.ndim != 2 or matrix.shape[1] != int(n_fft) // 2 + 1 or matrix.shape[0] < 1:
+        raise ValueError(f"matrix must have shape (bands >= 1, {int(n_fft) // 2 + 1}), got {tuple(matrix.shape)}")
+    bands = int(matrix.shape[0])
+    n_fft = int(n_fft)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    mode = _stft_pad_mode(center, pad_mode)
+    if n_fft < 1 or hop < 1 or not 1 <= wl <= n_fft:
+        raise ValueError(f"need n_fft >= 1, hop_length >= 1 and 1 <= win_length <= n_fft, got {n_fft}, {hop}, {wl}")
+    if window is not None:
+        if not (_is_torch(window) and window.is_cuda and window.dtype == _torch_dtypes(real)[0] and window.device == x.device):
+            raise TypeError(f"window must be a CUDA {_names((_torch_dtypes(real)[0],))} tensor on the input's device")
+        if tuple(window.shape) != (wl,):
+            raise ValueError(f"window must have shape ({wl},), got {tuple(window.shape)}")
+        window = window.contiguous()
+    p = _cached_plan(BandSpectrogram, n_fft, bands, real, hop, wl, mode != "none", "reflect" if mode == "none" else mode, int(_device_index(x)))
+    p.set_window(window)
+    p.set_bands(matrix)
+    return p
+
+
+def band_spectrogram(x, matrix, n_fft, hop_length=None, win_length=None, window=None, center=True, pad_mode="reflect", power=2.0,
+                     normalized=False, log_mult=0.0, log_floor=0.0):
+    """spectrogram(x, ...) projected onto the rows of `matrix`, a numpy array or torch tensor of shape (bands, n_fft // 2 + 1), without
+    the spectrogram being written: a float32 / float64 CUDA tensor of shape (..., length) -> (..., frames, bands), FRAME-MAJOR and
+    contiguous, on the current stream; log_mult != 0 gives log_mult * ln(max(., log_floor)).  Leading dimensions fold into the batch.
+    Handles are cached per (n_fft, bands, hop, win_length, padding, dtype, device); the window and the bank are set on EVERY call, and
+    setting a bank waits for the stream -- keep a BandSpectrogram to reuse one."""
+    real = _real_rows(x)
+    power = _spectrogram_power(power)
+    p = _bandspec_plan(x, matrix, n_fft, hop_length, win_length, window, center, pad_mode, real)
+    return p.forward(x.contiguous(), power, normalized, log_mult, log_floor)
+
+
+def mel_spectrogram(x, sample_rate, n_fft, n_mels=128, f_min=0.0, f_max=None, hop_length=None, win_length=None, window=None, center=True,
+                    pad_mode="reflect", power=2.0, normalized=False, norm=None, mel_scale="htk", log=None, amin=1e-10, ref=1.0, top_db=None):
+    """torchaudio.transforms.MelSpectrogram of a float32 / float64 CUDA tensor of shape (..., length) on the current stream, with the
+    defaults of spectrogram() (hop_length n_fft // 4, window of ones) -> (..., frames, n_mels), FRAME-MAJOR (torchaudio's
+    (..., n_mels, frames) is its transpose(-1, -2)).  f_max defaults to sample_rate / 2.  log: None = the mel energies Y; "ln" =
+    ln(max(Y, amin)); "log10" = log10(max(Y, amin)); "db" = (10 if power == 2 else 20) * log10(max(Y, amin) / ref), librosa's
+    power_to_db / amplitude_to_db with a scalar ref.  The logarithm of the floored value runs in the kernel; the `ref` offset and the
+    `top_db` clamp ("db" only: nothing below the maximum of each leading item's (frames, n_mels) block minus top_db) are torch
+    operations on the small output."""
+    import math
+
+    real = _real_rows(x)
+    power = _spectrogram_power(power)
+    if log not in MEL_LOGS:
+        raise ValueError(f"log must be None, 'ln', 'log10' or 'db', got {log!r}")
+    if log is not None and not (math.isfinite(float(amin)) and float(amin) > 0):
+        raise ValueError(f"amin must be finite and > 0, got {amin}")
+    if not (math.isfinite(float(ref)) and float(ref) > 0):
+        raise ValueError(f"ref must be finite and > 0, got {ref}")
+    if top_db is not None and (log != "db" or not float(top_db) >= 0):
+        raise ValueError("top_db needs log='db' and a value >= 0")
+    W = mel_filterbank(int(n_fft) // 2 + 1, f_min, float(sample_rate) / 2 if f_max is None else f_max, n_mels, sample_rate, norm, mel_scale)
+    mult = {None: 0.0, "ln": 1.0, "log10": 1.0 / math.log(10.0), "db": (10.0 if power == 2 else 20.0) / math.log(10.0)}[log]
+    p = _bandspec_plan(x, W, n_fft, hop_length, win_length, window, center, pad_mode, real)
+    y = p.forward(x.contiguous(), power, normalized, mult, float(amin) if log is not None else 0.0)
+    if log == "db":
+        if float(ref) != 1.0:
+            y -= mult * math.log(float(ref))
+        if top_db is not None and y.numel():
+            y = y.maximum(y.amax(dim=(-2, -1), keepdim=True) - float(top_db))
+    return y
+
+
+def mfcc(x, sample_rate, n_mfcc=40, n_fft=400, n_mels=128, f_min=0.0, f_max=None, hop_length=None, win_length=None, window=None,
+         center=True, pad_mode="reflect", mel_scale="htk", mel_norm=None, amin=1e-10, ref=1.0, top_db=80.0, norm="ortho"):
+    """torchaudio.transforms.MFCC: the dB mel power spectrogram (mel_spectrogram(..., power=2, log="db", amin, ref, top_db); mel_norm is
+    its `norm`) followed by dct(type=2, norm=norm) along the band axis, truncated to n_mfcc coefficients -> (..., frames, n_mfcc).  A
+    composition of the two calls: no kernel of its own."""
+    n_mfcc = int(n_mfcc)
+    if not 1 <= n_mfcc <= int(n_mels):
+        raise ValueError(f"need 1 <= n_mfcc <= n_mels, got {n_mfcc}, {n_mels}")
+    y = mel_spectrogram(x, sample_rate, n_fft, n_mels, f_min, f_max, hop_length, win_length, window, center, pad_mode, 2.0, False, mel_norm,
+                        mel_scale, "db", amin, ref, top_db)
+    return dct(y, 2, norm, -1)[..., :n_mfcc].contiguous()
+
+
 class Hilbert(_Handle):
     """Batched analytic signal and envelope (include/fourier.h, fourier_hip_hilbert_*) on device memory: of rows of N reals x,
     z = ifft(fft(x) * m) with m = 1 at bin 0 and (N even) N/2, 2 between them and 0 above -- scipy.signal.hilbert(x), N complex values a

@@ -946,6 +946,80 @@ const char *fourier_hip_csd_describe_double(const FOURIER_STRUCT fourier_csd_dou
 int fourier_hip_csd_last_status_float(const FOURIER_STRUCT fourier_csd_float *);
 int fourier_hip_csd_last_status_double(const FOURIER_STRUCT fourier_csd_double *);
 
+/* ---------------- band-energy (mel) spectrogram (extension; the reference has none) ----------
+ * Of `batch` rows of `length` reals T on DEVICE memory, the energies of every STFT frame in `bands` bands: with X[b, f, k] exactly what
+ * fourier_hip_stft_forward_* produces (framing, window, padding and `normalized` as fourier_hip_spectrogram_*), S = |X|^p, p = 1
+ * (FOURIER_SPECTROGRAM_MAGNITUDE) or 2 (FOURIER_SPECTROGRAM_POWER), and a real matrix W of bands x bins,
+ *   Y[b, f, j] = sum_k W[j, k] * S[b, f, k],   and with log_mult != 0   Y <- log_mult * ln(max(Y, log_floor)),
+ * frame-major batch x frames x bands REALS out; S never reaches memory the caller sees.  bins = n_fft / 2 + 1, 1 <= bands <= 65535.
+ * torchaudio's MelSpectrogram is W = melscale_fbanks(...)^T; any sparse-row matrix works, negative weights included.
+ * The sum over k runs in ascending k over the row's support [lo_j, hi_j) -- first non-zero column to last non-zero column + 1, zeros
+ * inside kept -- in ONE accumulator of type T; an all-zero row gives 0 (log_mult * ln(log_floor) under the log).  The logarithm is the
+ * library's logf / log.  log_mult == 0 means linear and log_floor is ignored; otherwise log_floor must be finite and > 0 (in T too).
+ * fourier_hip_bandspec_set_bands_*: h_matrix points to bands x bins reals T, row-major, on the HOST.  A set-up call like
+ * fourier_hip_bandspec_set_window_*: the supports are found and packed, uploaded, and the call waits for `stream`.  A NaN or infinite
+ * weight gives FOURIER_HIP_INVALID_ARGUMENT and keeps the bank that was there.  A later call replaces the bank; forward before any
+ * set_bands gives FOURIER_HIP_INVALID_ARGUMENT.
+ * Determinism: no atomics, and no sum crosses a frame: two calls with equal arguments give bit-equal results on a route, whatever the
+ * scratch bound.
+ * A NULL handle or pointer, reals not aligned to sizeof(T), any overlap of d_out with d_in, an invalid length or power give
+ * FOURIER_HIP_INVALID_ARGUMENT; batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_bandspec_describe_*: "bandspec <route>: <the real plan's describe>"):
+ *   "fused rows"  n_fft = 2h whose h-point plan is one whole-row kernel (n_fft 128 ... 1024, f32 also 2048) and bands <= bins: gather,
+ *                 window, transform, untangle, |.|^p, the band sums and the log in ONE launch; the |X|^p of a tile of frames live in
+ *                 LDS only.  No scratch.
+ *   "composed"    any n_fft and any bands: per chunk of the flat frame index the spectrogram's gather sweep and the real-input plan
+ *                 into a handle-owned scratch (n_fft reals + bins complex per frame, at most 1 GiB, never less than one frame), then a
+ *                 sweep with one lane per (frame, band).
+ * Option "fusion" = 1 takes the fused route wherever it exists (the default: it measured 0.18 - 0.20 of the composed route's time,
+ * DESIGN.md section 4, "Band-energy (mel) spectrogram"), 0 the composed one.  fourier_hip_bandspec_reserve_*(h, length, batch) sizes what forward needs
+ * for at most `batch` rows of `length` reals on the route selected at that time: it then never allocates (the bank's buffers belong
+ * to set_bands).  Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_bandspec_last_status_*. */
+struct fourier_bandspec_float;
+struct fourier_bandspec_double;
+
+/* NULL on failure (parameters outside the STFT handle's ranges, bands == 0 or bands > 65535 included). */
+struct fourier_bandspec_float *fourier_hip_bandspec_create_float(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                                 int pad_mode, FOURIER_SIZE_TYPE bands, int device);
+struct fourier_bandspec_double *fourier_hip_bandspec_create_double(FOURIER_SIZE_TYPE n_fft, FOURIER_SIZE_TYPE hop, FOURIER_SIZE_TYPE win_length,
+                                                                   int pad_mode, FOURIER_SIZE_TYPE bands, int device);
+/* NULL is a no-op. */
+void fourier_hip_bandspec_destroy_float(FOURIER_STRUCT fourier_bandspec_float *);
+void fourier_hip_bandspec_destroy_double(FOURIER_STRUCT fourier_bandspec_double *);
+/* 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_bandspec_n_fft_float(const FOURIER_STRUCT fourier_bandspec_float *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_n_fft_double(const FOURIER_STRUCT fourier_bandspec_double *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_hop_float(const FOURIER_STRUCT fourier_bandspec_float *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_hop_double(const FOURIER_STRUCT fourier_bandspec_double *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_win_length_float(const FOURIER_STRUCT fourier_bandspec_float *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_win_length_double(const FOURIER_STRUCT fourier_bandspec_double *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_bins_float(const FOURIER_STRUCT fourier_bandspec_float *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_bins_double(const FOURIER_STRUCT fourier_bandspec_double *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_bands_float(const FOURIER_STRUCT fourier_bandspec_float *);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_bands_double(const FOURIER_STRUCT fourier_bandspec_double *);
+/* frames of a row of `length` reals; 0 for an invalid length or a NULL handle */
+FOURIER_SIZE_TYPE fourier_hip_bandspec_frames_float(const FOURIER_STRUCT fourier_bandspec_float *, FOURIER_SIZE_TYPE length);
+FOURIER_SIZE_TYPE fourier_hip_bandspec_frames_double(const FOURIER_STRUCT fourier_bandspec_double *, FOURIER_SIZE_TYPE length);
+int fourier_hip_bandspec_set_window_float(FOURIER_STRUCT fourier_bandspec_float *, const void *d_window, void *stream);
+int fourier_hip_bandspec_set_window_double(FOURIER_STRUCT fourier_bandspec_double *, const void *d_window, void *stream);
+/* h_matrix: bands x bins reals on the HOST */
+int fourier_hip_bandspec_set_bands_float(FOURIER_STRUCT fourier_bandspec_float *, const void *h_matrix, void *stream);
+int fourier_hip_bandspec_set_bands_double(FOURIER_STRUCT fourier_bandspec_double *, const void *h_matrix, void *stream);
+int fourier_hip_bandspec_forward_float(const FOURIER_STRUCT fourier_bandspec_float *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                       FOURIER_SIZE_TYPE batch, int power, int normalized, double log_mult, double log_floor, void *stream);
+int fourier_hip_bandspec_forward_double(const FOURIER_STRUCT fourier_bandspec_double *, const void *d_in, void *d_out, FOURIER_SIZE_TYPE length,
+                                        FOURIER_SIZE_TYPE batch, int power, int normalized, double log_mult, double log_floor, void *stream);
+int fourier_hip_bandspec_reserve_float(const FOURIER_STRUCT fourier_bandspec_float *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+int fourier_hip_bandspec_reserve_double(const FOURIER_STRUCT fourier_bandspec_double *, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 = the composed route, 1 = the fused one wherever it exists.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_bandspec_set_option_float(FOURIER_STRUCT fourier_bandspec_float *, const char *key, long long value);
+int fourier_hip_bandspec_set_option_double(FOURIER_STRUCT fourier_bandspec_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_bandspec_describe_float(const FOURIER_STRUCT fourier_bandspec_float *);
+const char *fourier_hip_bandspec_describe_double(const FOURIER_STRUCT fourier_bandspec_double *);
+int fourier_hip_bandspec_last_status_float(const FOURIER_STRUCT fourier_bandspec_float *);
+int fourier_hip_bandspec_last_status_double(const FOURIER_STRUCT fourier_bandspec_double *);
+
 /* ---------------- analytic signal and envelope of real rows (extension; the reference has none) ----------
  * Of `batch` rows of N >= 1 reals T on DEVICE memory, row b at element offset b*N, with X = fft(x) and
  *   m[k] = 1 for k = 0 and (N even) k = N/2,  2 for 0 < k < N/2 (odd N: k <= (N-1)/2),  0 above,
@@ -1640,6 +1714,61 @@ template <typename T> struct csd;
 FOURIER_DEFINE_CXX_CSD_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CSD_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CSD_WRAPPER
+
+/* band-energy (mel) spectrogram on device memory (extension): fourier::bandspec<float> / <double>; the pad modes are stft_pad, the powers spectrogram_power's values */
+template <typename T> struct bandspec;
+
+#define FOURIER_DEFINE_CXX_BANDSPEC_WRAPPER(T, SUFFIX)                                             \
+  template <> struct bandspec<T> {                                                                 \
+    bandspec(std::size_t n_fft, std::size_t hop, std::size_t win_length, std::size_t bands, stft_pad pad = stft_pad::reflect, \
+             int device = -1)                                                                      \
+        : impl(::fourier::c::fourier_hip_bandspec_create_##SUFFIX(n_fft, hop, win_length, static_cast<int>(pad), bands, device), \
+               ::fourier::c::fourier_hip_bandspec_destroy_##SUFFIX) {}                             \
+    bandspec() = delete;                                                                           \
+    bandspec(const bandspec &) = delete;                                                           \
+    bandspec(bandspec &&) = default;                                                               \
+    bandspec &operator=(const bandspec &) = delete;                                                \
+    bandspec &operator=(bandspec &&) = default;                                                    \
+    ~bandspec() = default;                                                                         \
+    std::size_t n_fft() const { return ::fourier::c::fourier_hip_bandspec_n_fft_##SUFFIX(impl.get()); } \
+    std::size_t hop() const { return ::fourier::c::fourier_hip_bandspec_hop_##SUFFIX(impl.get()); } \
+    std::size_t win_length() const { return ::fourier::c::fourier_hip_bandspec_win_length_##SUFFIX(impl.get()); } \
+    std::size_t bins() const { return ::fourier::c::fourier_hip_bandspec_bins_##SUFFIX(impl.get()); } \
+    std::size_t bands() const { return ::fourier::c::fourier_hip_bandspec_bands_##SUFFIX(impl.get()); } \
+    std::size_t frames(std::size_t length) const {                                                 \
+      return ::fourier::c::fourier_hip_bandspec_frames_##SUFFIX(impl.get(), length);               \
+    }                                                                                              \
+    /* win_length reals on the device; nullptr: all ones */                                        \
+    int set_window(const void *d_window, void *stream = nullptr) {                                 \
+      return ::fourier::c::fourier_hip_bandspec_set_window_##SUFFIX(impl.get(), d_window, stream); \
+    }                                                                                              \
+    /* bands x bins reals on the HOST, row-major */                                                \
+    int set_bands(const T *h_matrix, void *stream = nullptr) {                                     \
+      return ::fourier::c::fourier_hip_bandspec_set_bands_##SUFFIX(impl.get(), h_matrix, stream);  \
+    }                                                                                              \
+    /* batch rows of `length` reals -> batch x frames x bands reals; power: 1 = |X|, 2 = |X|^2; log_mult != 0: log_mult ln(max(., log_floor)) */ \
+    int forward_device(const void *d_in, void *d_out, std::size_t length, std::size_t batch, int power = 2, \
+                       bool normalized = false, double log_mult = 0.0, double log_floor = 0.0, void *stream = nullptr) const { \
+      return ::fourier::c::fourier_hip_bandspec_forward_##SUFFIX(impl.get(), d_in, d_out, length, batch, power, \
+                                                                 normalized ? 1 : 0, log_mult, log_floor, stream); \
+    }                                                                                              \
+    int reserve(std::size_t length, std::size_t batch) const {                                     \
+      return ::fourier::c::fourier_hip_bandspec_reserve_##SUFFIX(impl.get(), length, batch);       \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_bandspec_set_option_##SUFFIX(impl.get(), key, value);       \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_bandspec_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_bandspec_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_bandspec_##SUFFIX,                                     \
+                      void (*)(::fourier::c::fourier_bandspec_##SUFFIX *)> impl;                   \
+  };
+FOURIER_DEFINE_CXX_BANDSPEC_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_BANDSPEC_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_BANDSPEC_WRAPPER
 
 /* analytic signal and envelope of real rows on device memory (extension): fourier::hilbert<float> / <double> */
 template <typename T> struct hilbert;
