@@ -15,8 +15,8 @@
 //                      chunk that holds a slot's first frame writes the slot, a later chunk adds to what is there (welch_colsum_kernel's
 //                      rule): launches of one stream run in order, so the sum's order is fixed by the chunking.
 //   csd_reduce_kernel  the final sweep of both routes: a row's slots summed in ascending order, one lane per (b, k); the cross spectrum
-//                      scale * c_k * (Re, Im) (a.scale already holds the 1 / frames) or the coherence (Re^2 + Im^2) / (Pxx Pyy), a plain
-//                      IEEE division.
+//                      scale * c_k * (Re, Im) (a.scale already holds the 1 / frames) or the coherence (Re^2 + Im^2) / (Pxx Pyy) as
+//                      (Re / Pxx)(Re / Pyy) + (Im / Pxx)(Im / Pyy), plain IEEE divisions: no product of two sums is formed.
 // No atomics anywhere.
 #pragma once
 #include "kernels_stft.h"
@@ -69,7 +69,10 @@ __global__ void __launch_bounds__(STFT_THREADS) csd_reduce_kernel(CsdArgs a) {
         pxx += p[t * slot + CSD_PXX * bins];
         pyy += p[t * slot + CSD_PYY * bins];
       }
-      ((T*)a.f.out)[i] = (re * re + im * im) / (pxx * pyy);
+      // quotients first: neither Re^2 + Im^2 nor Pxx Pyy is formed at full magnitude.  |Re|, |Im| <= sqrt(Pxx Pyy), so every quotient is
+      // at most sqrt(Pyy / Pxx) or its inverse; a power-of-two scaling of x and y moves the quotients by exact powers of two that cancel
+      const T rx = re / pxx, ry = re / pyy, ix = im / pxx, iy = im / pyy;
+      ((T*)a.f.out)[i] = rx * ry + ix * iy;
     } else {
       const T c = (T)a.scale * (a.fold && k > 0 && 2 * k < a.f.n_fft ? (T)2 : (T)1);
       ((cpx<T>*)a.f.out)[i] = cpx<T>{c * re, c * im};

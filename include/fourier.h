@@ -86,6 +86,26 @@ enum {
   FOURIER_HIP_UNSUPPORTED = 4,      /* size outside the engine's range                           */
 };
 
+/* Amplitude.  No entry point has an absolute constant in its arithmetic; the dynamic range of each follows from the number format T
+ * (FLT_MAX = 2^128 (1 - 2^-24), DBL_MAX = 2^1024 (1 - 2^-53)) and is pinned by tests/amplitude_cases.py:
+ *   linear entry points  (the transforms of every handle, convolution in the signal and in the filter, STFT / MDCT / filter banks /
+ *                        resampling / chirp-z / analytic signal and their inverses): f(2^k x) = 2^k f(x) BIT FOR BIT while every input,
+ *                        intermediate and output stays a normal number of T -- a power of two changes exponents only.
+ *   power and Welch      (fourier_hip_spectrogram_* at power 2 and welch, fourier_hip_csd_csd_*, the band sums of fourier_hip_bandspec_*):
+ *                        scale by exactly 2^2k under the same condition; |X|^2 = re^2 + im^2 and every sum of it (over frames, over the
+ *                        bins of a band) must be representable: |X| < sqrt(FLT_MAX) ~ 2^64 (f64: sqrt(DBL_MAX) ~ 2^512).
+ *   magnitude, envelope  (spectrogram and band spectrogram at power 1, fourier_hip_hilbert_envelope_*) are sqrt(re^2 + im^2), NOT a hypot: the
+ *                        result is representable for every finite X, but re^2 + im^2 must be: finite and exactly scaling for
+ *                        |X| < sqrt(FLT_MAX) ~ 2^64 (f64 2^512), inf beyond although |X| itself is far from FLT_MAX; and re^2 and im^2 must
+ *                        stay normal, |re|, |im| >= 2^-63 (f64 2^-511) where not 0, below which the result loses bits and then flushes to 0.
+ *                        The tests pin finite and exactly scaled results with the largest magnitude in [2^61, 2^62) (f64 [2^509, 2^510)).
+ *   coherence            is invariant under a power-of-two scaling of x or of y (degree 0) up to the overflow of the partial sums
+ *                        themselves: sum_f |X[b, f, k]|^2 and sum_f |Y[b, f, k]|^2 must be finite (the cross sums are bounded by them:
+ *                        Cauchy-Schwarz).  |X[b, f, k]| <= max |x| * sum_j |w_j|, so frames * (max |x| * sum |w|)^2 < FLT_MAX is
+ *                        sufficient: with a Hann window of 2048 samples and 1000 frames, max |x| < 5.7e14 in f32 -- neither their
+ *                        product nor the square of a cross sum is formed (see fourier_hip_csd_coherence_*).
+ * Subnormal values may be flushed to zero by the device; nothing above holds where one appears. */
+
 /* Create a plan on a specific device (-1 = current device).  Same plan factory as `create_fft_f32/f64`
  * (fourier/src/lib.rs:31-60): Stockham autosort for 2^a * 3^b as in the reference (`Autosort::new`, autosort/mod.rs:104-134),
  * Bluestein chirp-z (fourier-algorithms/src/bluesteins.rs) otherwise -- with one extension: SOME lengths that the reference
@@ -882,8 +902,10 @@ int fourier_hip_spectrogram_last_status_double(const FOURIER_STRUCT fourier_spec
  * scale = 1 / (fs sum w^2) for a density and 1 / (sum w)^2 for a spectrum.
  * fourier_hip_csd_coherence_*: batch x bins REALS out,
  *   out[b, k] = |sum_f conj(X) Y|^2 / (sum_f |X|^2 * sum_f |Y|^2)
- * (scale and fold cancel): scipy.signal.coherence(detrend = False).  A plain IEEE division: a bin whose denominator is 0 gives what the
- * division gives.  There is NO detrending: scipy's default removes each segment's mean first, this does not.
+ * (scale and fold cancel): scipy.signal.coherence(detrend = False).  Computed quotients first, with S = sum_f conj(X) Y, Pxx and Pyy as
+ * (Re S / Pxx) (Re S / Pyy) + (Im S / Pxx) (Im S / Pyy) in plain IEEE divisions, so that neither |S|^2 nor Pxx Pyy is formed: the result is
+ * finite and scale-invariant wherever the sums themselves are finite ("Amplitude" above).  A bin whose denominator is 0 gives what the
+ * divisions give.  There is NO detrending: scipy's default removes each segment's mean first, this does not.
  * Determinism: no atomics.  Every sum over frames runs in an order fixed by the route, the shape and the scratch bound -- ascending
  * frames inside a tile, then ascending tiles -- so two calls with equal arguments on one handle give bit-equal results.
  * A NULL handle or pointer, reals not aligned to sizeof(T), a cross spectrum not aligned to 2 sizeof(T), any overlap of d_out with d_x or

@@ -1,0 +1,843 @@
+"""The library across the amplitude range: one table of cases, stated once and run twice -- on the CPU emulation
+(tests/test_amplitude_emu.py) and on the MI355X (tests/test_gpu_amplitude.py).  Every other accuracy test feeds unit-variance noise and
+measures a relative L2 error, which says nothing about scale; these cases feed the same kernels 2^k x and integer-valued samples.
+
+The two callers hand in an adapter (`api`):
+  api.fa, api.device          fourier_amd bound to the library under test, the device index the handles are created on
+  api.put(array), api.ptr(b)  a numpy array as memory of the library's side, and its address
+  api.run(call, shape, dtype) runs call(address of an output of `shape` between guard elements), checks the guards, returns numpy
+Everything else -- shapes, routes, inputs, assertions, tolerances -- is here.
+
+A case (Case below) is a constructor, the option settings that select each of its routes with the describe() prefix the route must
+show (a silent fall-back fails there), the degree d of the output in the input amplitude, a maker of unit-variance Gaussian inputs from
+a seeded numpy generator, a runner through the handle's *_ptr entry point and the family's f64 truth (tests/*_truth.py, numpy for the
+core).  Shapes are the smallest that reach each kernel family (a partly empty last tile, more than one workgroup), batch 3, f32 and f64.
+
+Assertions (a test prints its worst figures in one line, then asserts every one of them):
+  (a) exact scaling   with y0 = f(x): f(2^k x) is BIT-equal to 2^(k d) y0 over the whole output.  2^k x is formed in the working
+                      precision, which is exact.  k by precision and degree is K below; these k keep every input, table product and
+                      output of the cases normal with a wide margin, so a device that flushes subnormals changes nothing.
+                      d = 1: the linear entry points; d = 2: power spectrogram, Welch, cross spectrum, band sums of powers; d = 0: the
+                      coherence, whose k go past the point (2^28 in f32) where a product of two summed powers leaves the format.
+  (b) truth           at k = 0 and at the largest and the smallest k of (a): relative L2 against the truth of the scaled, rounded input
+                      within the tolerance the family's own GPU test grants (restated below from each tol(); none is new -- relative L2
+                      does not change with scale).  A band spectrogram under the log has no degree: exp(out / log_mult) against
+                      maximum(truth, floor) with the floor the median of the truth, the rule of tests/bandspec_cases.py.
+  (c) integers        f32 only: round(sigma gauss) clipped to the integer type -- sigma 2^13 as int16, 2^21 as int24, 2^28 as int32 --
+                      through the power, magnitude and Welch spectrograms, cross spectrum and coherence, the band spectrogram in dB, the
+                      envelope and the real transform, against the truth under the same tolerances; and two full-scale 24-bit tones
+                      (two_tone below), whose coherence must be finite and within tolerance in the bins that hold the tone.
+  (d) range edges     spectrogram magnitude and envelope are sqrt(re^2 + im^2): |X|^2 must be representable, |X| < sqrt(FLT_MAX) ~ 2^64
+                      (f64: 2^512).  With k chosen so that max |y0| 2^k lies in [2^61, 2^62) (f64 [2^509, 2^510)) the output is finite
+                      and exactly scaled.  The edge is derived from the format, not measured; include/fourier.h states it."""
+import math
+import re
+import types
+
+import numpy as np
+
+import bandspec_truth
+import csd_truth
+import czt_truth
+import hilbert_truth
+import ipfb_truth
+import mdct_truth
+import pfb_truth
+import r2r_truth
+import resample_truth
+import spectrogram_truth
+import stft_truth
+from helpers import rel_l2
+
+BATCH = 3
+K = {"f32": {1: (-40, 40), 2: (-24, 24), 0: (-24, 24, 28, 40)},
+     "f64": {1: (-300, 300), 2: (-150, 150), 0: (-150, 150)}}
+EDGE = {"f32": 61, "f64": 509}                       # (d): the binary exponent of the largest scaled magnitude
+INTEGERS = ((13, 16), (21, 24), (28, 32))            # (c): log2 sigma, bits of the integer type
+LOG_MULT = 10.0 / math.log(10.0)                     # dB of a power
+FFT, IFFT, SQRT_IFFT = 0, 1, 4                       # fourier_amd.Transform
+GUARD, SENTINEL = 64, 77.0
+
+
+def rdt(real):
+    return np.float32 if real == "f32" else np.float64
+
+
+def cdt(real):
+    return np.complex64 if real == "f32" else np.complex128
+
+
+# ---- tolerances, restated from the families' GPU tests the way tests/test_gpu_chunks.py restates them
+def base_tol(d, real):
+    """tests/test_gpu_real.py's tol(): one transform of the inner plan"""
+    blu = "bluestein" in d
+    return (4e-6 if blu else 2e-6) if real == "f32" else (1e-11 if blu else 1e-13)
+
+
+def times(factor):
+    return lambda d, real: factor * base_tol(d, real)
+
+
+def axis_tol(d, real):
+    """tests/test_gpu_axis.py's tol()"""
+    blu = "bluestein" in d
+    return (4e-6 if blu else 2e-6) if real == "f32" else (1e-11 if blu else 1e-12)
+
+
+def realnd_tol(d, real):
+    """tests/test_gpu_realnd.py's tol() at rank 2"""
+    return 2e-6 if real == "f32" else 1e-12
+
+
+def czt_tol(d, real):
+    """tests/czt_cases.py's bound on the unit circle (chirp ratio 1)"""
+    return 4e-6 if real == "f32" else 1e-11
+
+
+def csd_base(d, real):
+    """tests/test_gpu_csd.py's base()"""
+    blu = "bluestein" in d
+    return (4e-6 if blu else 2e-6) if real == "f32" else (2e-13 if blu else 1e-13)
+
+
+def csd_tol(d, real):
+    return 4 * csd_base(d, real)
+
+
+def coherence_tol(d, real):
+    return 12 * csd_base(d, real)
+
+
+# tests/test_gpu_r2r.py, _stft.py and _mdct.py (forward 2 x, inverse 4 x), _pfb.py, _ipfb.py, _resample.py, _hilbert.py: 2 x;
+# _conv.py and _lconv.py: 3 x; _spectrogram.py and tests/bandspec_cases.py: 2 x 2 x
+TWO, THREE, FOUR = times(2), times(3), times(4)
+
+
+# ---- scaling and comparing
+def scale(a, k):
+    """2^k a in a's own precision: exact while the result is normal"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "c":
+        return np.ldexp(a.view(a.real.dtype), k).view(a.dtype)
+    return np.ldexp(a, k)
+
+
+def differing(a, b):
+    """the number of reals of a and b whose bits differ"""
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    u = np.uint32 if a.real.dtype == np.float32 else np.uint64
+    return int(np.count_nonzero(np.ascontiguousarray(a).view(u) != np.ascontiguousarray(b).view(u)))
+
+
+class HostApi:
+    """the adapter of the CPU emulation build: `fa` is fourier_amd bound to it, the buffers are host memory"""
+    device = -1
+
+    def __init__(self, fa):
+        self.fa = fa
+
+    def put(self, a):
+        return np.ascontiguousarray(a)
+
+    def ptr(self, b):
+        return b.ctypes.data
+
+    def run(self, call, shape, dtype):
+        count = int(np.prod(shape))
+        buf = np.full(count + 2 * GUARD, SENTINEL, dtype)
+        out = buf[GUARD:GUARD + count]
+        out[:] = np.nan
+        call(out.ctypes.data)
+        assert np.all(buf[:GUARD] == SENTINEL) and np.all(buf[-GUARD:] == SENTINEL), "a guard element was written"
+        return out.reshape(shape).copy()
+
+
+class Case:
+    """name; d: the degree (None: no exact scaling, `kd` picks the k of (b)); make(api, real) -> ctx with .plan; routes(real) ->
+    ((options, describe prefix or compiled pattern), ...); inputs(ctx, rng) -> unit-variance f64 / c128 arrays; scaled: the inputs
+    that carry the amplitude; run(api, ctx, ins) -> numpy; truth(ctx, ins) -> f64; pick(ctx, out): the part of out the truth covers;
+    err(ctx, out, want): the figure held against tol(describe, real)"""
+
+    def __init__(self, name, d, make, routes, inputs, run, truth, tol, scaled=None, pick=None, err=None, kd=None, integers=False,
+                 edge=False, describe=None):
+        self.name, self.d, self.make, self.inputs, self.run, self.truth, self.tol = name, d, make, inputs, run, truth, tol
+        self.routes = routes if callable(routes) else (lambda real: routes)
+        self.scaled, self.pick, self.err = scaled, pick or (lambda ctx, out: out), err or (lambda ctx, out, want: rel_l2(out, want))
+        self.kd = d if kd is None else kd
+        self.integers, self.edge = integers, edge
+        self.describe = describe or (lambda ctx: ctx.plan.describe())
+
+    def unit_inputs(self, ctx):
+        return self.inputs(ctx, np.random.default_rng(sum(self.name.encode())))
+
+    def carries(self, i):
+        return self.scaled is None or i in self.scaled
+
+    def select(self, ctx, real, options, prefix):
+        for key, value in options.items():
+            ctx.plan.set_option(key, value)
+        d = self.describe(ctx)
+        ok = d.startswith(prefix) if isinstance(prefix, str) else prefix.match(d)
+        assert ok, (self.name, real, options, d)
+        return d
+
+
+def rounded(ins, real):
+    return [np.ascontiguousarray(a.astype(cdt(real) if np.iscomplexobj(a) else rdt(real))) for a in ins]
+
+
+class Report:
+    """the figures of one test: its worst ones are printed in ONE line, then everything is asserted"""
+
+    def __init__(self, what):
+        self.what, self.routes, self.bad, self.reals, self.notes, self.failed = what, [], 0, 0, [], []
+        self.worst = (0.0, 0.0, 1.0, "")  # ratio, figure, bound, where
+
+    def route(self, d):
+        self.routes.append(d if not self.routes else d.split(":")[0].split(",")[0])  # the first describe() whole, the others by name
+
+    def exact(self, where, got, want):
+        bad = differing(got, want)
+        self.bad, self.reals = self.bad + bad, self.reals + got.size * (2 if got.dtype.kind == "c" else 1)
+        if bad:
+            self.failed.append((where, f"{bad} reals differ from the exactly scaled result"))
+
+    def figure(self, where, value, bound):
+        ratio = value / bound if value == value else math.inf
+        if ratio >= self.worst[0]:
+            self.worst = (ratio, value, bound, where)
+        if not value <= bound:
+            self.failed.append((where, value, bound))
+
+    def print(self):
+        parts = [f"{self.bad} of {self.reals} reals differ from the exactly scaled result"] if self.reals else []
+        if self.worst[3]:
+            parts.append(f"worst error {self.worst[1]:.3g} of {self.worst[2]:.3g} ({self.worst[3]})")
+        print(f"amplitude {self.what}: " + "; ".join(parts + self.notes) + f"  [{' | '.join(self.routes)}]")
+
+    def check(self):
+        assert not self.failed, (self.what, self.failed)
+
+
+def opt(options):
+    return "".join(f"{key}={value} " for key, value in options.items())
+
+
+def figure(what, value, bound):
+    print(f"amplitude {what}: figure {value:.3g} bound {bound:.3g}")
+    assert value <= bound, (what, value, bound)
+
+
+def check_scaling(api, case, real):
+    """(a) and (b)"""
+    ctx = case.make(api, real)
+    ins = rounded(case.unit_inputs(ctx), real)
+    ks = K[real][case.kd]
+    rep = Report(f"{real} {case.name}, k = {', '.join(f'{k:+d}' for k in ks)}")
+    try:
+        for options, prefix in case.routes(real):
+            d = case.select(ctx, real, options, prefix)
+            rep.route(d)
+            t = case.tol(d, real)
+            y0 = case.run(api, ctx, ins)
+            rep.figure(f"{opt(options)}k=0", case.err(ctx, case.pick(ctx, y0), case.truth(ctx, ins)), t)
+            for k in ks:
+                sc = [scale(a, k) if case.carries(i) else a for i, a in enumerate(ins)]
+                y = case.run(api, ctx, sc)
+                if case.d is not None:
+                    rep.exact(f"{opt(options)}k={k:+d}", y, scale(y0, k * case.d))
+                if k in (min(ks), max(ks)):
+                    rep.figure(f"{opt(options)}k={k:+d}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, sc)), t)
+    finally:
+        rep.print()
+    rep.check()
+
+
+def integer_samples(ins, case, log2_sigma, bits):
+    """round(sigma g) clipped to the integer type, as f32 (the inputs that carry no amplitude: rounded to f32 as they are)"""
+    lo, hi = -2.0 ** (bits - 1), 2.0 ** (bits - 1) - 1
+    return [np.ascontiguousarray((np.clip(np.rint(2.0 ** log2_sigma * a), lo, hi) if case.carries(i) else a).astype(np.float32))
+            for i, a in enumerate(ins)]
+
+
+def check_integers(api, case):
+    """(c): f32"""
+    ctx = case.make(api, "f32")
+    unit = case.unit_inputs(ctx)
+    rep = Report(f"f32 {case.name}, int16 / int24 / int32 samples")
+    try:
+        for options, prefix in case.routes("f32"):
+            d = case.select(ctx, "f32", options, prefix)
+            rep.route(d)
+            for log2_sigma, bits in INTEGERS:
+                ins = integer_samples(unit, case, log2_sigma, bits)
+                assert all(np.array_equal(a, np.rint(a)) for i, a in enumerate(ins) if case.carries(i))
+                y = case.run(api, ctx, ins)
+                if not np.all(np.isfinite(y)):
+                    rep.failed.append((options, bits, f"{int(np.count_nonzero(~np.isfinite(y)))} non-finite"))
+                rep.figure(f"{opt(options)}int{bits}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, ins)), case.tol(d, "f32"))
+    finally:
+        rep.print()
+    rep.check()
+
+
+def check_edge(api, case, real):
+    """(d)"""
+    ctx = case.make(api, real)
+    ins = rounded(case.unit_inputs(ctx), real)
+    rep = Report(f"{real} {case.name}, range edge")
+    try:
+        for options, prefix in case.routes(real):
+            rep.route(case.select(ctx, real, options, prefix))
+            y0 = case.run(api, ctx, ins)
+            k = EDGE[real] - int(math.floor(math.log2(float(np.max(np.abs(y0))))))
+            top = math.ldexp(float(np.max(np.abs(y0))), k)
+            assert 2.0 ** EDGE[real] <= top < 2.0 ** (EDGE[real] + 1), (k, top)
+            y = case.run(api, ctx, [scale(a, k) if case.carries(i) else a for i, a in enumerate(ins)])
+            bad = int(np.count_nonzero(~np.isfinite(y)))
+            rep.notes.append(f"{opt(options)}k={k:+d}: largest 2^{math.log2(top):.2f}, {bad} non-finite")
+            if bad:
+                rep.failed.append((options, k, f"{bad} non-finite"))
+            rep.exact(f"{opt(options)}k={k:+d}", y, scale(y0, k))
+    finally:
+        rep.print()
+    rep.check()
+
+
+# ---- the two-tone case of (c)
+TONE = dict(n_fft=2048, hop=512, frames=9, bin=200, amplitude=8388607.0, phase=0.3, noise=50.0)
+
+
+def two_tone(api):
+    """Two full-scale 24-bit tones at bin 200 of n_fft 2048 (amplitudes 2^23 - 1 and half of it, phase 0.3) plus noise of sigma 50,
+    rounded to integers, 9 frames, Hann window, f32, both routes.  The coherence in bins 199 ... 201 -- the ones a caller computes it
+    for -- must be finite and within tests/test_gpu_csd.py's tol_coherence of the truth (0.964, 0.983, 0.951 in the first row, printed); no
+    bin may be non-finite where the truth is finite.  The bins that hold only noise are not compared: their f32 frames carry the
+    rounding of a tone 2^17 times larger."""
+    n, hop, nb = TONE["n_fft"], TONE["hop"], TONE["bin"]
+    length = (TONE["frames"] - 1) * hop + 2
+    rng = np.random.default_rng(2048)
+    t = np.arange(length)
+    lo, hi = -2.0 ** 23, 2.0 ** 23 - 1
+    x = TONE["amplitude"] * np.cos(2 * np.pi * nb / n * t) + TONE["noise"] * rng.standard_normal((BATCH, length))
+    y = 0.5 * TONE["amplitude"] * np.cos(2 * np.pi * nb / n * t + TONE["phase"]) + TONE["noise"] * rng.standard_normal((BATCH, length))
+    x, y = (np.ascontiguousarray(np.clip(np.rint(v), lo, hi).astype(np.float32)) for v in (x, y))
+    w = stft_truth.hann(n, np.float32)
+    plan = api.fa.CrossSpectrum(n, "f32", hop, None, True, "reflect", api.device)
+    dw, dx, dy = api.put(w), api.put(x), api.put(y)
+    plan.set_window_ptr(api.ptr(dw))
+    assert plan.frames(length) == TONE["frames"]
+    want = csd_truth.coherence(x, y, n, hop, n, w, "reflect")
+    print("amplitude two-tone truth, row 0, bins 199 ... 201:", want[0, nb - 1:nb + 2])
+    for fusion, route in ((1, "fused rows"), (0, "composed")):
+        plan.set_option("fusion", fusion)
+        d = plan.describe()
+        assert d.startswith(f"csd {route}, coherence {route}: real "), d
+        got = api.run(lambda out: plan.coherence_ptr(api.ptr(dx), api.ptr(dy), out, length, BATCH), (BATCH, plan.bins()), np.float32)
+        bad = int(np.count_nonzero(~np.isfinite(got) & np.isfinite(want)))
+        print(f"amplitude two-tone {route}: {bad} non-finite bins where the truth is finite; bins 199 ... 201 of row 0: {got[0, nb - 1:nb + 2]}")
+        assert bad == 0, (route, bad)
+        figure(f"two-tone {route} bins 199 ... 201", rel_l2(got[:, nb - 1:nb + 2], want[:, nb - 1:nb + 2]), coherence_tol(d, "f32"))
+
+
+# ---- inputs
+def gauss(rng, *shape):
+    return rng.standard_normal(shape)
+
+
+def cgauss(rng, *shape):
+    return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+
+def half_spectrum(rng, rows, n):
+    """the half spectrum of real Gaussian rows at unit variance (bin 0 and, n even, bin n / 2 are real)"""
+    return np.fft.rfft(rng.standard_normal(rows + (n,)), axis=-1) / math.sqrt(n)
+
+
+def window(rng, real, n):
+    return np.ascontiguousarray((0.5 + rng.random(n)).astype(rdt(real)))
+
+
+def ctx_of(plan, **kw):
+    return types.SimpleNamespace(plan=plan, **kw)
+
+
+def fusion_routes(fused, composed, has=lambda real: True):
+    """both "fusion" values where the fused route exists, else the composed one under "fusion" = 1 (which must stay composed)"""
+    return lambda real: (({"fusion": 1}, fused), ({"fusion": 0}, composed)) if has(real) else (({"fusion": 1}, composed),)
+
+
+CASES = []
+
+
+def add(*args, **kw):
+    CASES.append(Case(*args, **kw))
+
+
+# ---- core plans
+CORE = {64: "stockham 64 ", 4096: "stockham 64x64 one-launch ", 1000: "stockham mixed-radix 5.5.5.8 ",
+        1001: "stockham registers 13x11x7 one-launch ", 1031: re.compile(r"bluestein M=\d+ registers \S+ one-launch "),
+        255: re.compile(r"bluestein M=\d+ (inner \d+ fused|registers \S+ one-launch) "), 12288: "stockham mixed tiles 128x96 ",
+        44100: "stockham mixed tiles 210x210 ", 16411: re.compile(r"bluestein M=\d+ inner mixed tiles \d+x\d+ "),
+        65536: re.compile(r"stockham \d+x\d+(x\d+)? f")}
+TWO_PASSES = re.compile(r"stockham \d+x\d+ f(32|64)$")  # two tile passes, not in one launch
+CORE_TRUTH = {FFT: lambda x: np.fft.fft(x, axis=-1), IFFT: lambda x: np.fft.ifft(x, axis=-1),
+              SQRT_IFFT: lambda x: np.fft.ifft(x, axis=-1) * math.sqrt(x.shape[-1])}
+
+
+def smallest_two_passes(api, real):
+    """the smallest power of two whose default plan is two tile passes, by describe()"""
+    for log2n in range(6, 21):
+        plan = api.fa.Fft(1 << log2n, real, api.device)
+        if TWO_PASSES.match(plan.describe()):
+            return plan
+    raise AssertionError("no power of two up to 2^20 runs as two tile passes")
+
+
+def core(n, code, name):
+    def make(api, real):
+        return ctx_of(api.fa.Fft(n, real, api.device) if n else smallest_two_passes(api, real))
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, BATCH, code), ins[0].shape, ins[0].dtype)
+
+    add(f"fft {n or 'smallest two passes'} {name}", 1, make, (({}, CORE[n] if n else TWO_PASSES),), lambda c, rng: [cgauss(rng, BATCH, c.plan.size())],
+        run, lambda c, ins: CORE_TRUTH[code](ins[0].astype(np.complex128)), base_tol)
+
+
+for _n in (64, 4096, 1000, 1001, 1031, 255, 12288, 44100, 16411, 65536, 0):
+    for _code, _name in ((FFT, "Fft"), (IFFT, "Ifft"), (SQRT_IFFT, "SqrtScaledIfft")):
+        core(_n, _code, _name)
+
+
+# ---- real transforms, N-D, a strided axis, DCT / DST
+def rfft(n):
+    def make(api, real):
+        return ctx_of(api.fa.RealFft(n, real, api.device))
+
+    def forward(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, BATCH), (BATCH, n // 2 + 1), cdt(c.plan.real))
+
+    def inverse(api, c, ins):
+        s = api.put(ins[0])
+        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, BATCH), (BATCH, n), rdt(c.plan.real))
+
+    add(f"rfft {n}", 1, make, (({}, "real "),), lambda c, rng: [gauss(rng, BATCH, n)], forward,
+        lambda c, ins: np.fft.rfft(ins[0].astype(np.float64), axis=-1), base_tol, integers=n == 4096)
+    add(f"irfft {n}", 1, make, (({}, "real "),), lambda c, rng: [half_spectrum(rng, (BATCH,), n)], inverse,
+        lambda c, ins: np.fft.irfft(ins[0].astype(np.complex128), n=n, axis=-1), base_tol)
+
+
+for _n in (4096, 1001):
+    rfft(_n)
+
+
+def rfftn(shape):
+    half = shape[:-1] + (shape[-1] // 2 + 1,)
+    axes = tuple(range(1, len(shape) + 1))
+
+    def make(api, real):
+        return ctx_of(api.fa.RealFftN(shape, real, api.device))
+
+    def forward(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, BATCH), (BATCH,) + half, cdt(c.plan.real))
+
+    def inverse(api, c, ins):
+        s = api.put(ins[0])
+        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, BATCH), (BATCH,) + shape, rdt(c.plan.real))
+
+    add(f"rfftn {list(shape)}", 1, make, (({}, "realnd "),), lambda c, rng: [gauss(rng, BATCH, *shape)], forward,
+        lambda c, ins: np.fft.rfftn(ins[0].astype(np.float64), axes=axes), realnd_tol)
+    add(f"irfftn {list(shape)}", 1, make, (({}, "realnd "),),
+        lambda c, rng: [np.fft.rfftn(gauss(rng, BATCH, *shape), axes=axes) / math.sqrt(np.prod(shape))], inverse,
+        lambda c, ins: np.fft.irfftn(ins[0].astype(np.complex128), s=shape, axes=axes), realnd_tol)
+
+
+rfftn((16, 64))
+
+
+def axis(outer, n, inner):
+    def make(api, real):
+        return ctx_of(api.fa.Fft(n, real, api.device))
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.transform_axis_ptr(api.ptr(x), out, outer, inner, FFT), ins[0].shape, ins[0].dtype)
+
+    add(f"axis [{outer}, {n}, {inner}]", 1, make, (({}, "axis "),), lambda c, rng: [cgauss(rng, outer, n, inner)], run,
+        lambda c, ins: np.fft.fft(ins[0].astype(np.complex128), axis=1), axis_tol, describe=lambda c: c.plan.describe_axis(inner))
+
+
+axis(8, 64, 6)
+
+
+def r2r(n, kind):
+    def make(api, real):
+        return ctx_of(api.fa.R2R(n, real, api.device), idx=r2r_truth.want(kind, "ortho", np.zeros((1, n)))[0])
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, BATCH, r2r_truth.KINDS[kind], r2r_truth.NORMS["ortho"]),
+                       (BATCH, n), ins[0].dtype)
+
+    add(f"r2r {n} {kind} ortho", 1, make, (({}, "r2r "),), lambda c, rng: [gauss(rng, BATCH, n)], run,
+        lambda c, ins: r2r_truth.want(kind, "ortho", ins[0])[1], TWO, pick=lambda c, out: out[:, c.idx])
+
+
+for _n in (1000, 255):
+    for _kind in r2r_truth.KINDS:
+        r2r(_n, _kind)
+
+
+# ---- circular and linear convolution: the amplitude in the signal, and in the filter through set_filters
+FILTERS, TAPS = 2, 33
+
+
+def conv_want(x, h):
+    """numpy in f64; row b with filter b mod F (tests/test_gpu_conv.py's want)"""
+    n = x.shape[-1]
+    hb = h[np.arange(x.shape[0]) % h.shape[0]]
+    if np.iscomplexobj(x):
+        return np.fft.ifft(np.fft.fft(x.astype(np.complex128), axis=-1) * np.fft.fft(hb.astype(np.complex128), n, axis=-1), axis=-1)
+    return np.fft.irfft(np.fft.rfft(x.astype(np.float64), axis=-1) * np.fft.rfft(hb.astype(np.float64), n, axis=-1), n=n, axis=-1)
+
+
+def fftconv(n, real_data):
+    g = gauss if real_data else cgauss
+    kind = "real" if real_data else "complex"
+
+    def make(api, real):
+        return ctx_of(api.fa.FftConv(n, real, real_data, api.device))
+
+    def run(api, c, ins):
+        x, h = api.put(ins[0]), api.put(ins[1])
+        c.plan.set_filters_ptr(api.ptr(h), TAPS, FILTERS)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), ins[0].shape, ins[0].dtype)
+
+    if real_data:
+        routes = (({"fusion": 1}, "conv real fused untangle: "), ({"fusion": 0}, "conv real composed: "))
+    else:
+        routes = (({"fusion": 1}, "conv one-launch: "), ({"fusion": 0}, "conv composed: ")) if n == 4096 else (({"fusion": 1}, "conv composed: "),)
+    for what, scaled in (("signal", (0,)), ("filter", (1,))):
+        add(f"fftconv {n} {kind} scaled {what}", 1, make, routes, lambda c, rng: [g(rng, BATCH, n), g(rng, FILTERS, TAPS)], run,
+            lambda c, ins: conv_want(ins[0], ins[1]), THREE, scaled=scaled)
+
+
+for _n in (4096, 1000):
+    for _real_data in (False, True):
+        fftconv(_n, _real_data)
+
+
+def lconv(lx, k, real_data):
+    g = gauss if real_data else cgauss
+    off = (k - 1) // 2  # mode "same"
+
+    def make(api, real):
+        return ctx_of(api.fa.LinearConv(lx, k, real, "same", real_data, api.device))
+
+    def run(api, c, ins):
+        x, h = api.put(ins[0]), api.put(ins[1])
+        c.plan.set_filters_ptr(api.ptr(h), FILTERS)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), (BATCH, c.plan.out_length()), ins[0].dtype)
+
+    def truth(c, ins):
+        wide = np.float64 if real_data else np.complex128
+        return np.array([np.convolve(ins[0][b].astype(wide), ins[1][b % FILTERS].astype(wide))[off:off + lx] for b in range(BATCH)])
+
+    for what, scaled in (("signal", (0,)), ("filter", (1,))):
+        add(f"lconv {lx} K={k} same {'real' if real_data else 'complex'} scaled {what}", 1, make, (({}, "lconv overlap-save: "),),
+            lambda c, rng: [g(rng, BATCH, lx), g(rng, FILTERS, k)], run, truth, THREE, scaled=scaled)
+
+
+for _real_data in (False, True):
+    lconv(3000, 129, _real_data)
+
+
+# ---- the frame handles
+def has_fused_frames(n_fft):
+    """the fused frame kernels exist at n_fft 128 ... 1024 in both precisions"""
+    return n_fft in (128, 256, 512, 1024)
+
+
+def frame_ctx(api, cls, real, n_fft, hop, *more):
+    plan = cls(n_fft, *more, real, hop, None, True, "reflect", api.device)
+    w = window(np.random.default_rng(n_fft + hop), real, n_fft)
+    dw = api.put(w)
+    plan.set_window_ptr(api.ptr(dw))
+    return ctx_of(plan, w=w, dw=dw)
+
+
+def frames_of(n_fft):
+    """67 frames a row at n_fft 256: the fused tiles (64 frames at f32, 32 at f64; frame pairs: half as many) are more than one a row,
+    the last partly empty; 35 at 400: two slots of the composed sums"""
+    return 67 if n_fft == 256 else 35
+
+
+def stft(n_fft, hop):
+    nf = frames_of(n_fft)
+    length, bins = (nf - 1) * hop + 3, n_fft // 2 + 1
+    fused = has_fused_frames(n_fft)
+
+    def make(api, real):
+        c = frame_ctx(api, api.fa.Stft, real, n_fft, hop)
+        assert c.plan.frames(length) == stft_truth.frames(length, n_fft, hop, "reflect") == nf
+        return c
+
+    def forward(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, nf, bins), cdt(c.plan.real))
+
+    def inverse(api, c, ins):
+        s = api.put(ins[0])
+        back = c.plan.default_length(nf)
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, nf, back, BATCH), (BATCH, back), rdt(c.plan.real))
+
+    add(f"stft {n_fft} hop {hop}", 1, make, fusion_routes("stft fused rows, istft composed: real ", "stft composed, istft composed: real ", lambda real: fused),
+        lambda c, rng: [gauss(rng, BATCH, length)], forward, lambda c, ins: stft_truth.stft(ins[0], n_fft, hop, n_fft, c.w, "reflect"), TWO)
+    add(f"istft {n_fft} hop {hop}", 1, make, (({"fusion": 0}, "stft composed, istft composed: real "),),
+        lambda c, rng: [half_spectrum(rng, (BATCH, nf), n_fft)], inverse,
+        lambda c, ins: stft_truth.istft(ins[0], n_fft, hop, c.plan.default_length(nf), n_fft, c.w, "reflect"), FOUR)
+
+
+stft(256, 64)
+stft(400, 160)
+
+
+def mdct(n):
+    length = 9 * n + 5
+    fused = "mdct fused rows, imdct composed: " if n % 2 == 0 else None
+    composed = "mdct composed, imdct composed: " if n % 2 == 0 else "mdct full-length, imdct full-length: "
+
+    def make(api, real):
+        plan = api.fa.Mdct(n, real, True, api.device)
+        w = window(np.random.default_rng(n), real, 2 * n)
+        dw = api.put(w)
+        plan.set_window_ptr(api.ptr(dw))
+        nf = plan.frames(length)
+        assert nf == mdct_truth.frames(length, n, True) == 11
+        return ctx_of(plan, w=w, dw=dw, nf=nf)
+
+    def forward(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, c.nf, n), ins[0].dtype)
+
+    def inverse(api, c, ins):
+        s = api.put(ins[0])
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, c.nf, length, BATCH), (BATCH, length), ins[0].dtype)
+
+    add(f"mdct {n}", 1, make, fusion_routes(fused, composed, lambda real: fused is not None), lambda c, rng: [gauss(rng, BATCH, length)], forward,
+        lambda c, ins: mdct_truth.mdct(ins[0], n, c.w, True), TWO)
+    add(f"imdct {n}", 1, make, (({"fusion": 0}, composed),), lambda c, rng: [gauss(rng, BATCH, 11, n)], inverse,
+        lambda c, ins: mdct_truth.imdct(ins[0], n, length, c.w, True), FOUR)
+
+
+mdct(256)
+mdct(255)
+
+
+def pfb(P, T, D, real_rows):
+    nf = 20
+    length = P * T + (nf - 1) * D
+    bins = P // 2 + 1 if real_rows else P
+    kind = "real" if real_rows else "complex"
+
+    def make_with(cls):
+        def make(api, real):
+            plan = cls(api.fa)(P, T, real, D, real_rows, api.device)
+            h = np.ascontiguousarray(np.random.default_rng(P + T).standard_normal(P * T).astype(rdt(real)))
+            dh = api.put(h)
+            plan.set_filter_ptr(api.ptr(dh))
+            return ctx_of(plan, h=h, dh=dh)
+        return make
+
+    def forward(api, c, ins):
+        assert c.plan.frames(length) == pfb_truth.frames(length, P, T, D) == nf
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, nf, bins), cdt(c.plan.real))
+
+    def inverse(api, c, ins):
+        assert c.plan.length(nf) == ipfb_truth.full(nf, P, T, D) == length
+        s = api.put(ins[0])
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, nf, length, BATCH), (BATCH, length),
+                       rdt(c.plan.real) if real_rows else cdt(c.plan.real))
+
+    add(f"pfb P={P} T={T} D={D} {kind}", 1, make_with(lambda fa: fa.Pfb), fusion_routes("pfb fused rows: ", "pfb composed: "),
+        lambda c, rng: [(gauss if real_rows else cgauss)(rng, BATCH, length)], forward,
+        lambda c, ins: pfb_truth.pfb(ins[0], c.h, P, T, D, real_rows), TWO)
+    add(f"ipfb P={P} T={T} D={D} {kind}", 1, make_with(lambda fa: fa.Ipfb), (({}, "ipfb composed: "),),
+        lambda c, rng: [half_spectrum(rng, (BATCH, nf), P) if real_rows else cgauss(rng, BATCH, nf, P)], inverse,
+        lambda c, ins: ipfb_truth.synth(ins[0], c.h, P, T, D, real_rows, length), TWO)
+
+
+pfb(256, 4, 192, True)
+pfb(256, 4, 192, False)
+
+
+def resample(n, m, complex_rows):
+    def make(api, real):
+        plan = api.fa.Resample(n, m, real, api.device, not complex_rows)
+        w = resample_truth.window(np.random.default_rng(n + m), n, rdt(real))
+        dw = api.put(w)
+        plan.set_window_ptr(api.ptr(dw))
+        return ctx_of(plan, w=w, dw=dw)
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, BATCH), (BATCH, m), ins[0].dtype)
+
+    routes = (({"fusion": 0}, "resample complex: "),) if complex_rows else fusion_routes("resample real fused untangle: ", "resample real composed: ")
+    add(f"resample {n} -> {m} {'complex' if complex_rows else 'real'}", 1, make, routes,
+        lambda c, rng: [(cgauss if complex_rows else gauss)(rng, BATCH, n)], run, lambda c, ins: resample_truth.resample(ins[0], m, c.w), TWO)
+
+
+resample(3000, 2756, False)
+resample(1000, 1031, True)
+
+
+def czt(n, m, real_input):
+    def make(api, real):
+        return ctx_of(api.fa.Czt(n, m, 1.0, None, 1.0, 0.0, real, real_input, api.device))
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.transform_ptr(api.ptr(x), out, BATCH), (BATCH, m), cdt(c.plan.real))
+
+    add(f"czt {n} -> {m} {'real' if real_input else 'complex'}", 1, make, fusion_routes("czt one-launch: ", "czt composed: "),
+        lambda c, rng: [(gauss if real_input else cgauss)(rng, BATCH, n)], run, lambda c, ins: czt_truth.czt(ins[0], m, 1.0, -1.0 / m), czt_tol)
+
+
+czt(1000, 1000, False)
+czt(1000, 1000, True)
+
+
+def hilbert(n):
+    def make(api, real):
+        return ctx_of(api.fa.Hilbert(n, real, api.device))
+
+    def analytic(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.analytic_ptr(api.ptr(x), out, BATCH), (BATCH, n), cdt(c.plan.real))
+
+    def envelope(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.envelope_ptr(api.ptr(x), out, BATCH), (BATCH, n), ins[0].dtype)
+
+    routes = fusion_routes("hilbert one-launch: ", "hilbert composed: ", lambda real: n == 2048)
+    add(f"hilbert analytic {n}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, n)], analytic, lambda c, ins: hilbert_truth.analytic(ins[0]), TWO)
+    add(f"hilbert envelope {n}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, n)], envelope, lambda c, ins: hilbert_truth.envelope(ins[0]), TWO,
+        integers=n == 2048, edge=True)
+
+
+hilbert(2048)
+hilbert(1000)
+
+
+# ---- power, magnitude, Welch; cross spectrum and coherence; band energies
+def spectrogram(n_fft, hop):
+    nf = frames_of(n_fft)
+    length, bins = (nf - 1) * hop + 3, n_fft // 2 + 1
+    routes = fusion_routes("spectrogram fused rows, welch fused rows: real ", "spectrogram composed, welch composed: real ",
+                           lambda real: has_fused_frames(n_fft))
+
+    def make(api, real):
+        c = frame_ctx(api, api.fa.Spectrogram, real, n_fft, hop)
+        assert c.plan.frames(length) == nf
+        return c
+
+    def forward(power):
+        def run(api, c, ins):
+            x = api.put(ins[0])
+            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH, power, power == 1), (BATCH, nf, bins), ins[0].dtype)
+        return run
+
+    def welch(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.welch_ptr(api.ptr(x), out, length, BATCH, True, 0.37), (BATCH, bins), ins[0].dtype)
+
+    for power in (2, 1):
+        add(f"spectrogram {n_fft} hop {hop} power {power}", power, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power),
+            lambda c, ins, power=power: spectrogram_truth.spectrogram(ins[0], n_fft, hop, n_fft, c.w, "reflect", power, power == 1), FOUR,
+            integers=n_fft == 256, edge=power == 1)
+    add(f"welch {n_fft} hop {hop}", 2, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], welch,
+        lambda c, ins: spectrogram_truth.welch(ins[0], n_fft, hop, n_fft, c.w, "reflect", True, 0.37), FOUR, integers=n_fft == 256)
+
+
+spectrogram(256, 64)
+spectrogram(400, 160)
+
+
+def cross_spectrum(n_fft, hop):
+    nf = frames_of(n_fft)
+    length, bins = (nf - 1) * hop + 3, n_fft // 2 + 1
+    routes = fusion_routes("csd fused rows, coherence fused rows: real ", "csd composed, coherence composed: real ",
+                           lambda real: has_fused_frames(n_fft))
+
+    def make(api, real):
+        c = frame_ctx(api, api.fa.CrossSpectrum, real, n_fft, hop)
+        assert c.plan.frames(length) == nf
+        return c
+
+    def inputs(c, rng):
+        return list(csd_truth.pair(rng, BATCH, length, np.float64))
+
+    def csd(api, c, ins):
+        x, y = api.put(ins[0]), api.put(ins[1])
+        return api.run(lambda out: c.plan.csd_ptr(api.ptr(x), api.ptr(y), out, length, BATCH, True, 0.37), (BATCH, bins), cdt(c.plan.real))
+
+    def coherence(api, c, ins):
+        x, y = api.put(ins[0]), api.put(ins[1])
+        return api.run(lambda out: c.plan.coherence_ptr(api.ptr(x), api.ptr(y), out, length, BATCH), (BATCH, bins), ins[0].dtype)
+
+    add(f"csd {n_fft} hop {hop}", 2, make, routes, inputs, csd,
+        lambda c, ins: csd_truth.csd(ins[0], ins[1], n_fft, hop, n_fft, c.w, "reflect", True, 0.37), csd_tol, integers=n_fft == 256)
+    add(f"coherence {n_fft} hop {hop}", 0, make, routes, inputs, coherence,
+        lambda c, ins: csd_truth.coherence(ins[0], ins[1], n_fft, hop, n_fft, c.w, "reflect"), coherence_tol, integers=n_fft == 256)
+
+
+cross_spectrum(256, 64)
+cross_spectrum(400, 160)
+
+
+def band_spectrogram(n_fft, hop, bands):
+    nf = frames_of(n_fft)
+    length = (nf - 1) * hop + 3
+
+    def make(api, real):
+        c = frame_ctx(api, api.fa.BandSpectrogram, real, n_fft, hop, bands)
+        W = api.fa.mel_filterbank(n_fft // 2 + 1, 0.0, 8000.0, bands, 16000.0, None, "htk")
+        c.W = np.asarray(W).astype(rdt(real)).astype(np.float64)  # what the handle holds: the truth uses the rounded weights
+        c.plan.set_bands(c.W)
+        assert c.plan.frames(length) == nf and c.plan.bands() == bands
+        return c
+
+    def want(c, ins, power):
+        return bandspec_truth.band_spectrogram(ins[0], c.W, n_fft, hop, n_fft, c.w, "reflect", power, power == 1)
+
+    def forward(power, log):
+        def run(api, c, ins):
+            # under the log the floor is the median of the truth at this input: about half of the values clamp
+            c.floor = float(np.median(want(c, ins, power))) if log else 0.0
+            x = api.put(ins[0])
+            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH, power, power == 1, LOG_MULT if log else 0.0, c.floor),
+                           (BATCH, nf, bands), ins[0].dtype)
+        return run
+
+    routes = fusion_routes("bandspec fused rows: real ", "bandspec composed: real ")
+    for power in (1, 2):
+        add(f"bandspec {n_fft} {bands} bands power {power}", power, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power, False),
+            lambda c, ins, power=power: want(c, ins, power), FOUR)
+        add(f"bandspec {n_fft} {bands} bands power {power} log", None, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power, True),
+            lambda c, ins, power=power: np.maximum(want(c, ins, power), c.floor), FOUR, kd=power,
+            err=lambda c, out, w: rel_l2(np.exp(out.astype(np.float64) / LOG_MULT), w), integers=power == 2)
+
+
+band_spectrogram(256, 64, 20)
+
+BY_NAME = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+NAMES = list(BY_NAME)
+INTEGER_NAMES = [c.name for c in CASES if c.integers]
+EDGE_NAMES = [c.name for c in CASES if c.edge]
