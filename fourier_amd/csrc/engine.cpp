@@ -28,6 +28,7 @@
 #include "pfb_plan.h"
 #include "ipfb_plan.h"
 #include "resample_plan.h"
+#include "xcorr_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -657,6 +658,34 @@ FOURIER_DEFINE_IPFB_ABI(double, double)
 
 FOURIER_DEFINE_RESAMPLE_ABI(float, float)
 FOURIER_DEFINE_RESAMPLE_ABI(double, double)
+
+// pairwise cross-correlation and GCC-PHAT (fourier_hip_xcorr_*)
+#define FOURIER_DEFINE_XCORR_ABI(T, SUFFIX)                                                                      \
+  FOURIER_DEFINE_HANDLE_ABI(xcorr, fourier_xcorr_##SUFFIX, XcorrPlan<T>, SUFFIX)                                 \
+  extern "C" fc::fourier_xcorr_##SUFFIX* fourier_hip_xcorr_create_##SUFFIX(size_t size, size_t length, long long lag_first, size_t lags, \
+                                                                           int real_data, int device) {         \
+    return (fc::fourier_xcorr_##SUFFIX*)create_handle<XcorrPlan<T>>(size, length, lag_first, lags, real_data, device); \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_xcorr_size_##SUFFIX(const fc::fourier_xcorr_##SUFFIX* h) {                       \
+    return h ? ((const XcorrPlan<T>*)h)->size() : 0;                                                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_xcorr_length_##SUFFIX(const fc::fourier_xcorr_##SUFFIX* h) {                     \
+    return h ? ((const XcorrPlan<T>*)h)->length() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_xcorr_lags_##SUFFIX(const fc::fourier_xcorr_##SUFFIX* h) {                       \
+    return h ? ((const XcorrPlan<T>*)h)->lags() : 0;                                                             \
+  }                                                                                                              \
+  extern "C" int fourier_hip_xcorr_correlate_##SUFFIX(const fc::fourier_xcorr_##SUFFIX* h, const void* d_x, const void* d_y, void* d_out, \
+                                                      size_t batch, void* stream) {                              \
+    const XcorrPlan<T>* p = (const XcorrPlan<T>*)h;                                                              \
+    return guarded_handle(p, [&] { p->correlate(d_x, d_y, d_out, batch, (hipStream_t)stream); });                \
+  }                                                                                                              \
+  extern "C" int fourier_hip_xcorr_set_option_##SUFFIX(fc::fourier_xcorr_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<XcorrPlan<T>>(h, key, v);                                                           \
+  }
+
+FOURIER_DEFINE_XCORR_ABI(float, float)
+FOURIER_DEFINE_XCORR_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -204,6 +204,7 @@ typedef void (*ConvKernel)(ConvArgs);
 typedef void (*HilbertKernel)(HilbertArgs);
 typedef void (*CztKernel)(CztArgs);
 typedef void (*ResampleKernel)(ResampleArgs);
+typedef void (*XcorrKernel)(XcorrArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -323,6 +324,11 @@ template <typename T> struct Real {};
   CztKernel get_czt_kernel(Real<T>, int which);                                                                        \
   /* kernels_resample.cpp: the sweeps of the resampling handle, which = RESAMPLE_REMAP / RESAMPLE_UNTANGLE */                 \
   ResampleKernel get_resample_kernel(Real<T>, int which);                                                              \
+  /* kernels_xcorr.cpp: the cross-correlation of two real rows in one launch on the shapes of the two-level plans          */ \
+  /* (xcorr_small_kernel), plain or PHAT: the instances without scratch memory; the sweeps of the composed routes,        */ \
+  /* which = XCORR_PAD ... XCORR_WINDOW, real or complex values                                                         */ \
+  bool get_xcorr_small_kernel(Real<T>, int k, bool phat, KernelInfo& info);                                            \
+  XcorrKernel get_xcorr_kernel(Real<T>, int which, bool real_data, bool phat);                                         \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \
@@ -350,6 +356,8 @@ template <typename T> struct Real {};
   FOURIER_REGFFT_SHARD_LIST(FOURIER_DECLARE_REGFFT_SHARD, T)                                                           \
   /* kernels_experiments.cpp (experiments library) or env_product.cpp (product: nothing available) */                  \
   bool get_fused_kernel(Real<T>, int k, FusedInfo& info);                                                              \
+  /* ... every instance of xcorr_small_kernel, those with scratch memory included (product: none) */                   \
+  bool get_xcorr_spilling_kernel(Real<T>, int k, bool phat, KernelInfo& info);                                         \
   KernelInfo get_split_kernel(Real<T>, int L, int io);                                                                 \
   /* persistent LAST pass that prefetches its next tile (fft_last_prefetch_kernel); fn == nullptr where not built */     \
   KernelInfo get_prefetch_kernel(Real<T>, int L, int io);                                                               \

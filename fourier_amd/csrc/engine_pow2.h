@@ -291,6 +291,40 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
   }
 
+  // The cross-correlation of two real rows in one launch (xcorr_small_kernel; the cross-correlation handle): conv_small_kernel's shapes
+  // and tables; one kernel for each weighting, and only where it runs without scratch memory (kernels_xcorr.cpp; the development
+  // switch FOURIER_XCORR_SPILLING, read here, takes every instance from the experiments library instead).  Returns the weightings that have one: bit 0 none, bit 1 PHAT.
+  int enable_xcorr_small() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return 0;
+    const bool spilling = dev_env("FOURIER_XCORR_SPILLING") != nullptr;
+    int have = 0;
+    for (int e = 0; e < 2; ++e) {
+      KernelInfo k;
+      if (!xcorr_small_[e].fn && (spilling ? get_xcorr_spilling_kernel(Real<T>{}, ilog2(n_), e == 1, k) : get_xcorr_small_kernel(Real<T>{}, ilog2(n_), e == 1, k))) {
+        set_smem_attribute(k);
+        xcorr_small_[e] = k;
+      }
+      if (xcorr_small_[e].fn) have |= 1 << e;
+    }
+    if (have && !passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    return have;
+  }
+  // x, y: `batch` rows of n <= n_ reals each (x == y allowed); out: rows of `lags` reals, apart from both; first = lag_first mod n_
+  void run_xcorr_small(const void* x, const void* y, void* out, size_t batch, uint32_t n, uint32_t first, uint32_t lags, bool phat,
+                       hipStream_t stream, unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    const KernelInfo& k = xcorr_small_[phat ? 1 : 0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = x; a.xc_in2 = y; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.xc_n = n; a.xc_first = first; a.xc_lags = lags;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
+  }
+
   // The chirp-z transform in one launch (czt_small_kernel; the chirp-z handle): conv_small_kernel's shapes and tables; one kernel for
   // complex input rows, one for real ones.
   bool enable_czt_small(bool real_input) {
@@ -742,6 +776,7 @@ template <typename T> class Pow2Engine {
   int tl1_ = 0, tl2_ = 0;   // pass lengths of a one-launch (MODE_TWOLEVEL) plan
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
+  KernelInfo xcorr_small_[2];    // no weighting, PHAT
   KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
   std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel, BandSpecRowsKernel> frame_rows_;

@@ -19,4 +19,8 @@ KernelInfo get_prefetch_kernel(Real<double>, int, int) { return KernelInfo(); }
 KernelInfo get_skeleton_kernel(Real<float>, int, int) { return KernelInfo(); }
 KernelInfo get_skeleton_kernel(Real<double>, int, int) { return KernelInfo(); }
 
+// the cross-correlation kernel's instances that need scratch memory ("Cross-correlation")
+bool get_xcorr_spilling_kernel(Real<float>, int, bool, KernelInfo&) { return false; }
+bool get_xcorr_spilling_kernel(Real<double>, int, bool, KernelInfo&) { return false; }
+
 }  // namespace fourier_hip

@@ -72,6 +72,10 @@ struct PassArgs {
   const void* cz_a;
   const void* cz_b;
   uint32_t cz_n, cz_m;
+  // xcorr_small_kernel (XcorrPlan, xcorr_plan.h): rows of xc_n reals at `in` (x) and at xc_in2 (y), rows of xc_lags reals out: lag
+  // t of the n-point circular correlation goes to output position (t - xc_first) mod n where that is below xc_lags
+  const void* xc_in2;
+  uint32_t xc_n, xc_first, xc_lags;  // xc_first = lag_first mod n
 };
 
 
@@ -462,6 +466,25 @@ struct ResampleArgs {
   uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
   double nyq;                 // half spectra and untangle: the factor of the bin kh -- 1, 2 (m < n) or 1/2 (n < m)
   double scale;               // 1 / n, computed in T: m / n times the inverse's 1 / m
+};
+
+// ---- pairwise cross-correlation (kernels_xcorr.h; XcorrPlan, xcorr_plan.h): the sweeps of the composed routes, one lane per element of
+// the output side over a flat index; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of either side per launch).  The values are
+// reals where `real`, else complex values.
+// xcorr_pad_kernel: rows of n values -> rows of l values, zeros from n on.
+// xcorr_mul_kernel: `total` spectrum values X (in) and Y (in2) -> conj(X) Y * scale, or (phat) conj(X / |X|) (Y / |Y|) * scale with
+// |.| = sqrt(re^2 + im^2), 0 where either magnitude is 0; out may be in2.
+// xcorr_window_kernel: rows of l values r -> rows of `lags` values r[(first + j) mod l].
+enum { XCORR_PAD = 0, XCORR_MUL = 1, XCORR_WINDOW = 2 };
+struct XcorrArgs {
+  const void* in; const void* in2; void* out;
+  uint32_t n, l;              // values per row: the signal, the transform
+  uint32_t lags, first;       // window: values per output row, lag_first mod l
+  uint32_t total;             // pad: rows * l; mul: values; window: rows * lags
+  uint32_t div_m, div_l;      // idx / l (pad) or idx / lags (window) = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  int real, phat;
+  double scale;               // mul: the inverse's 1 / l, computed in T
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -2,6 +2,7 @@
 // Compiled once per precision: -DFOURIER_TU_REAL=float / double (fourier_amd/build.py).
 #include "engine_common.h"
 #include "kernels_experiments.h"
+#include "kernels_xcorr.h"
 #include "tile_shapes.h"
 
 namespace fourier_hip {
@@ -70,6 +71,12 @@ KernelInfo get_prefetch_kernel(Real<TUReal>, int L, int io) {
     case 2048: return io == IO_BLU_OUT ? make_prefetch_info<T, 2048, FOURIER_CG_2048, IO_BLU_OUT>() : make_prefetch_info<T, 2048, FOURIER_CG_2048, IO_PLAIN>();
     default: return KernelInfo();
   }
+}
+
+// every instance of the cross-correlation handle's one-launch kernel, those with scratch memory included (the product's table,
+// kernels_xcorr.cpp, holds the others only); selected by the development switch FOURIER_XCORR_SPILLING (engine_pow2.h)
+bool get_xcorr_spilling_kernel(Real<TUReal>, int k, bool phat, KernelInfo& info) {
+  return phat ? xcorr_small_by_length<TUReal, true>(k, info) : xcorr_small_by_length<TUReal, false>(k, info);
 }
 
 }  // namespace fourier_hip

@@ -598,6 +598,21 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_hilbert_small(d_in, d_out, batch, envelope, stream, nxcd_);
   }
 
+  // ---- the hook of the cross-correlation handle (XcorrPlan, xcorr_plan.h); exec() is not affected.  A one-launch two-level plan of L
+  // points (2^11 ... 2^15, f64 ... 2^14) runs `batch` pairs of rows of n <= L reals in one launch of xcorr_small_kernel: rows of `lags`
+  // reals out, apart from both inputs; `first` is lag_first mod L.  The caller keeps `batch` below 2^31.  enable_xcorr returns the
+  // weightings that have a kernel: bit 0 none, bit 1 PHAT.
+  int enable_xcorr() {
+    if (blu_ || !eng_) return 0;
+    DeviceGuard g(device_);
+    return eng_->enable_xcorr_small();
+  }
+  void exec_xcorr(const void* d_x, const void* d_y, void* d_out, size_t batch, size_t n, size_t first, size_t lags, bool phat,
+                  hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_xcorr_small(d_x, d_y, d_out, batch, (uint32_t)n, (uint32_t)first, (uint32_t)lags, phat, stream, nxcd_);
+  }
+
   // ---- the hook of the chirp-z handle (CztPlan, czt_plan.h); exec() is not affected.  A one-launch two-level plan of L points
   // (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n values (complex, or reals) in one launch of czt_small_kernel: rows of m complex
   // values out, apart from the input, n + m - 1 <= L.  The tables are the caller's: A (n entries), B (m entries), H (L entries, spectrum

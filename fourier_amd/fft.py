@@ -1512,6 +1512,169 @@ def envelope(x, dim=-1, out=None):
     return _hilbert(x, None, dim, out, False)
 
 
+class CrossCorrelation(_Handle):
+    """Batched pairwise cross-correlation and GCC-PHAT (include/fourier.h, fourier_hip_xcorr_*) on device memory: of rows x[b], y[b] of
+    n values, zero-extended to the transform length `length` = L >= n,
+        r[b, l] = sum_t conj(x[b, t]) y[b, (t + l) mod L],    out[b, j] = r[b, (lag_first + j) mod L],  j < lags,
+    `lags` values a row.  L >= 2n - 1 with lag_first = -(n - 1), lags = 2n - 1 is numpy.correlate(y, x, "full") (mind the order: a peak
+    at lag l > 0 means that y lags x by l samples); L == n with lag_first = 0, lags = L is the circular correlation.  Real rows
+    (real_data=True, the default) give real output, complex rows complex output.  Option "weighting" = 1 is the phase transform
+    (GCC-PHAT): every bin of conj(X) Y divided by |X| |Y|, exactly 0 where either is 0."""
+
+    _prefix = "fourier_hip_xcorr_"
+    _destroy = "fourier_hip_xcorr_destroy"
+
+    def __init__(self, n, length, lag_first, lags, real="f32", real_data=True, device=-1):
+        n, length, lag_first, lags = int(n), int(length), int(lag_first), int(lags)
+        if not 1 <= n <= length:
+            raise ValueError(f"need 1 <= n <= length, got {n}, {length}")
+        if not 1 <= lags <= length:
+            raise ValueError(f"need 1 <= lags <= length, got {lags}, {length}")
+        if abs(lag_first) >= length:
+            raise ValueError(f"need |lag_first| < length, got {lag_first}, {length}")
+        self._create(real, f"cross-correlation plan of {n} values in {length}", n, length, lag_first, lags, int(bool(real_data)), int(device))
+        self._n, self._l, self._first, self._lags, self.real_data = n, length, lag_first, lags, bool(real_data)
+
+    def size(self):
+        return self._n
+
+    def length(self):
+        return self._l
+
+    def lag_first(self):
+        return self._first
+
+    def lags(self):
+        return self._lags
+
+    def set_option(self, key, value):
+        """"fusion": 1 (default) = the one-launch kernel where the library has one (real rows, f64, no weighting, length 2^11 ... 2^14),
+        0 = the composed route.  "weighting": 0 (default) = none, 1 = PHAT."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def correlate_ptr(self, d_x, d_y, d_out, batch, stream=0):
+        """`batch` rows of n values at d_x and at d_y (which may be the same: the autocorrelation) -> `batch` rows of lags() values at
+        d_out, which may overlap neither, enqueued on `stream`."""
+        self._call("correlate", d_x, d_y, d_out, int(batch), stream)
+
+    def correlate(self, x, y, out=None):
+        """Contiguous (..., n) CUDA tensors of one shape, float (real_data) or complex of the handle's precision -> a new (..., lags)
+        tensor of the same dtype, or `out` (which may overlap neither input), on the current stream.  `y` may be `x`."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        dt = rdt if self.real_data else cdt
+        _require_cuda(x, dt)
+        _require_cuda(y, dt)
+        if tuple(x.shape) != tuple(y.shape) or x.device != y.device:
+            raise ValueError(f"x and y must have one shape and device, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        shape = tuple(x.shape[:-1]) + (self._lags,)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=x.device)
+        else:
+            _require_out(out, shape, dt, x.device)
+        batch = x.numel() // self._n
+        if batch:
+            self.correlate_ptr(x.data_ptr(), y.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+
+def create_xcorr_f32(n, length, lag_first, lags, real_data=True, device=-1):
+    return CrossCorrelation(n, length, lag_first, lags, "f32", real_data, device)
+
+
+def create_xcorr_f64(n, length, lag_first, lags, real_data=True, device=-1):
+    return CrossCorrelation(n, length, lag_first, lags, "f64", real_data, device)
+
+
+def _xcorr_window(n, max_lag, mode):
+    """(transform length, lag_first, lags) of xcorr's output"""
+    if mode not in ("linear", "circular"):
+        raise ValueError(f'mode must be "linear" or "circular", got {mode!r}')
+    if max_lag is not None:
+        max_lag = int(max_lag)
+        if max_lag < 0:
+            raise ValueError(f"need max_lag >= 0, got {max_lag}")
+    if mode == "circular":
+        if max_lag is None:
+            return n, 0, n
+        if 2 * max_lag + 1 > n:
+            raise ValueError(f"need 2 max_lag + 1 <= n in circular mode, got {max_lag}, {n}")
+        return n, -max_lag, 2 * max_lag + 1
+    if max_lag is None:
+        max_lag = n - 1
+    if max_lag > n - 1:
+        raise ValueError(f"need max_lag <= n - 1, got {max_lag}, {n}")
+    length = 1
+    while length < n + max_lag:  # no wrap inside the window: L - max_lag > n - 1
+        length *= 2
+    return length, -max_lag, 2 * max_lag + 1
+
+
+def correlation_lags(n, max_lag=None, mode="linear"):
+    """The lag of every output column of xcorr / gcc_phat for rows of n values: -max_lag ... max_lag, or (circular mode without max_lag)
+    0 ... n - 1 in the raw order, where lag l >= n / 2 is the negative lag l - n.  A numpy int64 array."""
+    import numpy as np
+
+    _, first, lags = _xcorr_window(int(n), max_lag, mode)
+    return np.arange(first, first + lags, dtype=np.int64)
+
+
+def xcorr(x, y, max_lag=None, mode="linear", weighting=None, dim=-1, out=None):
+    """Cross-correlation of the rows of two CUDA tensors of one shape and dtype (float32 / float64: real output; complex64 / complex128:
+    complex output) along `dim`, on the current stream: out[..., j] = sum_t conj(x[t]) y[t + lag_j], lag_j = correlation_lags(n,
+    max_lag, mode)[j].  mode="linear" (zero-extended, transform length next_pow2(n + max_lag), max_lag defaults to n - 1): lags
+    -max_lag ... max_lag, numpy.correlate(y, x, "full") for the default.  mode="circular" (transform length n): the raw order 0 ... n - 1
+    when max_lag is None, else the centred window with 2 max_lag + 1 <= n.  weighting=None, or "phat" for the phase transform.  Returns
+    a new tensor or `out`.  Only the last dimension of contiguous tensors is native; any other `dim` or layout is moved last with a
+    torch copy.  One cached CrossCorrelation handle per (n, window, dtype, device) and weighting."""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None):
+        raise TypeError("expected CUDA float32 / float64 / complex64 / complex128 tensors")
+    if not (_is_torch(y) and y.is_cuda and y.dtype == x.dtype and y.device == x.device):
+        raise TypeError("y must be a CUDA tensor of x's dtype on x's device")
+    if weighting not in (None, "phat"):
+        raise ValueError(f'weighting must be None or "phat", got {weighting!r}')
+    if tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f"x and y must have one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    d = _normalise_dims(x.dim(), (dim,))[0]
+    n = int(x.shape[d])
+    if n < 1:
+        raise ValueError("the correlated dimension must have length >= 1")
+    length, first, lags = _xcorr_window(n, max_lag, mode)
+    real, real_data = _precision(x.dtype)
+    shape = tuple(x.shape[:d]) + (lags,) + tuple(x.shape[d + 1:])
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == shape and out.device == x.device):
+        raise TypeError(f"out must be a CUDA {_names((x.dtype,))} tensor of shape {shape} on the input's device")
+    phat = weighting == "phat"
+    plan = _cached_plan(_weighted_xcorr, n, length, first, lags, real, real_data, int(_device_index(x)), phat)
+    if d == x.dim() - 1 and x.is_contiguous() and y.is_contiguous() and (out is None or out.is_contiguous()):
+        return plan.correlate(x, y, out)
+    xs = x.movedim(d, -1).contiguous()
+    res = plan.correlate(xs, xs if y is x else y.movedim(d, -1).contiguous()).movedim(-1, d)
+    if out is None:
+        return res.contiguous()
+    out.copy_(res)
+    return out
+
+
+def _weighted_xcorr(n, length, first, lags, real, real_data, device, phat):
+    plan = CrossCorrelation(n, length, first, lags, real, real_data, device)
+    plan.set_option("weighting", int(phat))
+    return plan
+
+
+def gcc_phat(x, y, max_lag=None, mode="linear", dim=-1, out=None):
+    """xcorr(x, y, max_lag, mode, weighting="phat", dim=dim, out=out): the generalized cross-correlation with phase transform, whose
+    peak is at the lag by which y trails x."""
+    return xcorr(x, y, max_lag, mode, "phat", dim, out)
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

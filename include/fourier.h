@@ -1367,6 +1367,82 @@ const char *fourier_hip_resample_describe_double(const FOURIER_STRUCT fourier_re
 int fourier_hip_resample_last_status_float(const FOURIER_STRUCT fourier_resample_float *);
 int fourier_hip_resample_last_status_double(const FOURIER_STRUCT fourier_resample_double *);
 
+/* ---------------- pairwise cross-correlation and GCC-PHAT (extension; the reference has none) ----------
+ * Of `batch` rows x[b] and `batch` rows y[b] of n = `size` values on DEVICE memory, row b at element offset b*n -- REALS T where the
+ * handle was created with real_data = 1, interleaved COMPLEX values with real_data = 0 --, zero-extended to the transform length
+ * L = `length` >= n, with X = fft(x~, L), Y = fft(y~, L) and G[k] = conj(X[k]) Y[k]:
+ *   r[b][l] = ifft(G psi)[l] = sum_t conj(x~[b][t]) y~[b][(t + l) mod L]      (psi = 1),
+ *   out[b][j] = r[b][(lag_first + j) mod L],   j = 0 .. lags-1,
+ * `batch` rows of `lags` values out, reals for real rows and complex values for complex rows.  1 <= n <= L, 1 <= lags <= L and
+ * |lag_first| < L (signed), else create fails.  L == n, lag_first = 0, lags = L is the circular correlation; L >= 2n - 1,
+ * lag_first = -(n - 1), lags = 2n - 1 is numpy.correlate(y, x, "full") and scipy.signal.correlate(y, x, "full") -- mind the argument
+ * order, it is the cross spectrum's conj(X) Y convention: a peak at lag l > 0 means that y lags x by l samples.
+ * Option "weighting": FOURIER_XCORR_WEIGHT_NONE (0, the default): psi = 1.  FOURIER_XCORR_WEIGHT_PHAT (1): the generalized
+ * cross-correlation with phase transform, G psi = conj(X / |X|) (Y / |Y|): the two unit phasors are formed separately, quotients first,
+ * |.| = sqrt(re^2 + im^2) (the magnitude convention above, not a hypot), and the bin is exactly 0 where |X[k]| or |Y[k]| is 0: an
+ * all-zero row gives an all-zero row, never a NaN.  There is no epsilon.  The 1/L of the inverse is folded into the product.
+ * d_x == d_y is allowed: the autocorrelation.  The output may not overlap either input.  A NULL pointer, a real buffer not aligned to
+ * sizeof(T) or a complex one not aligned to 2*sizeof(T), an overlap of the output with an input give FOURIER_HIP_INVALID_ARGUMENT.
+ * batch == 0 is a successful no-op.  L * 2 * sizeof(T) > 2^31 - 1: create fails (as fourier_hip_hilbert_create_*).  Stream-ordered on
+ * `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_xcorr_describe_* begins with the route's name):
+ *   "xcorr one-launch"  REAL rows, L = 2^11 ... 2^15 (double: ... 2^14), any n <= L and any window, where the kernel of that precision
+ *                       and weighting runs without scratch memory -- double without weighting; elsewhere the handle stays on the
+ *                       composed route and its description says so.  The two rows are scaled by powers of two to peaks in [1, 2),
+ *                       x becomes the real and y the imaginary part of ONE complex row, then FFT, an exchange that separates X and Y,
+ *                       the weighted product, inverse FFT and the store of the window in ONE launch on register-resident data; no
+ *                       scratch.  Under PHAT a SINGLE bin where one spectrum is exactly 0 and the other is not keeps a unit phasor
+ *                       there (X[k] is a difference of two roundings on this route); an all-zero row still gives an all-zero row.
+ *   "xcorr composed"    every L.  The two rows are padded and transformed APART (real rows: to half spectra of L/2 + 1 values), one
+ *                       sweep forms G psi / L, the unscaled inverse follows -- straight into the caller's output where the window is
+ *                       the whole row (lag_first == 0, lags == L) --, and a last sweep stores the window.  Complex rows have no
+ *                       one-launch route.
+ * On every route power-of-two scaling of either input scales the unweighted output exactly and leaves the PHAT output bit-identical
+ * while nothing over- or underflows.
+ * Option "fusion" (fourier_hip_xcorr_set_option_*): 1 = the one-launch route where it exists, the DEFAULT (it took 0.23 - 0.37 of the
+ * composed route's time at every measured shape), 0 = the composed route.  The plan owns a scratch of at most
+ * 1 GiB (never less than one row pair) and walks larger batches in chunks of it; the first call with a batch larger than any before
+ * allocates it unless fourier_hip_xcorr_reserve_* was called for at least that batch.  No atomics: the result is the same on
+ * repetition.  A NULL handle gives FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_xcorr_size_* / _length_* / _lags_* and "" from
+ * fourier_hip_xcorr_describe_*.  Handles are Send, not Sync, like the complex ones; status of the last call:
+ * fourier_hip_xcorr_last_status_*. */
+enum {
+  FOURIER_XCORR_WEIGHT_NONE = 0,
+  FOURIER_XCORR_WEIGHT_PHAT = 1
+};
+struct fourier_xcorr_float;
+struct fourier_xcorr_double;
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_xcorr_float *fourier_hip_xcorr_create_float(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length, long long lag_first,
+                                                           FOURIER_SIZE_TYPE lags, int real_data, int device);
+struct fourier_xcorr_double *fourier_hip_xcorr_create_double(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length, long long lag_first,
+                                                             FOURIER_SIZE_TYPE lags, int real_data, int device);
+/* NULL is a no-op. */
+void fourier_hip_xcorr_destroy_float(FOURIER_STRUCT fourier_xcorr_float *);
+void fourier_hip_xcorr_destroy_double(FOURIER_STRUCT fourier_xcorr_double *);
+/* n, L and the number of lags; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_xcorr_size_float(const FOURIER_STRUCT fourier_xcorr_float *);
+FOURIER_SIZE_TYPE fourier_hip_xcorr_size_double(const FOURIER_STRUCT fourier_xcorr_double *);
+FOURIER_SIZE_TYPE fourier_hip_xcorr_length_float(const FOURIER_STRUCT fourier_xcorr_float *);
+FOURIER_SIZE_TYPE fourier_hip_xcorr_length_double(const FOURIER_STRUCT fourier_xcorr_double *);
+FOURIER_SIZE_TYPE fourier_hip_xcorr_lags_float(const FOURIER_STRUCT fourier_xcorr_float *);
+FOURIER_SIZE_TYPE fourier_hip_xcorr_lags_double(const FOURIER_STRUCT fourier_xcorr_double *);
+int fourier_hip_xcorr_correlate_float(const FOURIER_STRUCT fourier_xcorr_float *, const void *d_x, const void *d_y, void *d_out,
+                                      FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_xcorr_correlate_double(const FOURIER_STRUCT fourier_xcorr_double *, const void *d_x, const void *d_y, void *d_out,
+                                       FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_xcorr_reserve_float(const FOURIER_STRUCT fourier_xcorr_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_xcorr_reserve_double(const FOURIER_STRUCT fourier_xcorr_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 / 1; "weighting": FOURIER_XCORR_WEIGHT_NONE / _PHAT.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_xcorr_set_option_float(FOURIER_STRUCT fourier_xcorr_float *, const char *key, long long value);
+int fourier_hip_xcorr_set_option_double(FOURIER_STRUCT fourier_xcorr_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_xcorr_describe_float(const FOURIER_STRUCT fourier_xcorr_float *);
+const char *fourier_hip_xcorr_describe_double(const FOURIER_STRUCT fourier_xcorr_double *);
+int fourier_hip_xcorr_last_status_float(const FOURIER_STRUCT fourier_xcorr_float *);
+int fourier_hip_xcorr_last_status_double(const FOURIER_STRUCT fourier_xcorr_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1832,6 +1908,48 @@ template <typename T> struct hilbert;
 FOURIER_DEFINE_CXX_HILBERT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_HILBERT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_HILBERT_WRAPPER
+
+/* pairwise cross-correlation and GCC-PHAT on device memory (extension): fourier::xcorr<float> / <double> */
+template <typename T> struct xcorr;
+
+#define FOURIER_DEFINE_CXX_XCORR_WRAPPER(T, SUFFIX)                                                \
+  template <> struct xcorr<T> {                                                                    \
+    xcorr(std::size_t size, std::size_t length, long long lag_first, std::size_t lags,             \
+          bool real_data = true, int device = -1)                                                  \
+        : impl(::fourier::c::fourier_hip_xcorr_create_##SUFFIX(size, length, lag_first, lags,      \
+                                                               real_data ? 1 : 0, device),        \
+               ::fourier::c::fourier_hip_xcorr_destroy_##SUFFIX) {}                                \
+    xcorr() = delete;                                                                              \
+    xcorr(const xcorr &) = delete;                                                                 \
+    xcorr(xcorr &&) = default;                                                                     \
+    xcorr &operator=(const xcorr &) = delete;                                                      \
+    xcorr &operator=(xcorr &&) = default;                                                          \
+    ~xcorr() = default;                                                                            \
+    std::size_t size() const { return ::fourier::c::fourier_hip_xcorr_size_##SUFFIX(impl.get()); } \
+    std::size_t length() const { return ::fourier::c::fourier_hip_xcorr_length_##SUFFIX(impl.get()); }\
+    std::size_t lags() const { return ::fourier::c::fourier_hip_xcorr_lags_##SUFFIX(impl.get()); } \
+    /* `batch` rows of n values at d_x and d_y (which may be the same) -> rows of lags values (no overlap) */\
+    int correlate_device(const void *d_x, const void *d_y, void *d_out, std::size_t batch,         \
+                         void *stream = nullptr) const {                                           \
+      return ::fourier::c::fourier_hip_xcorr_correlate_##SUFFIX(impl.get(), d_x, d_y, d_out, batch, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_xcorr_reserve_##SUFFIX(impl.get(), batch);                  \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_xcorr_set_option_##SUFFIX(impl.get(), key, value);          \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_xcorr_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_xcorr_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_xcorr_##SUFFIX,                                        \
+                      void (*)(::fourier::c::fourier_xcorr_##SUFFIX *)> impl;                      \
+  };
+FOURIER_DEFINE_CXX_XCORR_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_XCORR_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_XCORR_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
