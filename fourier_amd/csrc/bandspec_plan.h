@@ -31,6 +31,7 @@ template <typename T> class BandSpecPlan : public HandleBase {
     device_ = stft_->real().inner().device();
     DeviceGuard g(device_);
     frames_.cap = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = frames_.items = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     // Where the fused route is the default: wherever its kernels exist and bands <= bins.  The project's rule is that a default follows
     // a measurement: at 64 rows of 2^20 reals, (n_fft, hop, mels) = (512, 128, 40), (1024, 256, 80), (2048, 512, 128), the fused route
     // took 0.18 - 0.20 of the composed route's time at all five shapes where it exists (f32 0.40 - 0.44 ms against 2.14 - 2.34 ms, f64
@@ -124,7 +125,7 @@ template <typename T> class BandSpecPlan : public HandleBase {
     a.power = (uint32_t)power;
     a.log_mult = log_mult; a.log_floor = log_mult != 0 ? log_floor : 0.0;
     if (fusion_.on) {
-      for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
+      for_chunks(total, launch_items_, [&](size_t g0, size_t ng) {
         stft_->fused_launch_at(a.f, in, length, fr, g0, ng);
         a.f.out = out + g0 * bands_;
         stft_->real().inner().exec_frames(a, stream, power);
@@ -153,6 +154,7 @@ template <typename T> class BandSpecPlan : public HandleBase {
   std::unique_ptr<StftPlan<T>> stft_;
   int device_ = 0;
   FusionSwitch fusion_;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
   FrameScratch<T> frames_;
   DevBuf lo_, off_, w_;
   bool have_bank_ = false;

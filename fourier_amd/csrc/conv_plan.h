@@ -42,6 +42,7 @@ template <typename T> class ConvPlan : public HandleBase {
       fused_route_ = plan_->enable_conv_bank();
     }
     scratch_cap_ = scratch_bound("FOURIER_CONV_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
     set_fusion(true);
   }
 
@@ -166,7 +167,7 @@ template <typename T> class ConvPlan : public HandleBase {
   // conv_mul_kernel (len values per row) or real_conv_mid_kernel (rows of len = h) over nb rows of the scratch, in launches of at
   // most REAL_LAUNCH_BYTES; b0: the first row's index in the call
   void sweep(int which, cpx<T>* z, size_t nb, size_t len, size_t b0, hipStream_t stream) const {
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / (len * ELEM));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / (len * ELEM));
     const uint32_t lanes = which == CONV_REAL_MID ? (uint32_t)(len / 2 + 1) : (uint32_t)len;
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
@@ -198,6 +199,7 @@ template <typename T> class ConvPlan : public HandleBase {
   DevBuf bank_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
 };
 
 }  // namespace fourier_hip

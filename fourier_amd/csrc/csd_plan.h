@@ -32,6 +32,7 @@ template <typename T> class CsdPlan : public HandleBase {
     device_ = stft_->real().inner().device();
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     // Where the fused route is the default: nowhere yet.  The project's rule is that a default follows a measurement: the fused route
     // has to beat the composed one on every shape of tools/csd_bench.py by more than the spread between repetitions of one arm
     // ("Cross-spectral density and coherence").  Option "fusion" = 1 selects the fused kernel wherever it exists.
@@ -137,14 +138,14 @@ template <typename T> class CsdPlan : public HandleBase {
   // rows per group of a call: their partials (four planes a slot) fit the bound (never less than one row's) and one launch's 32-bit indices
   size_t prepare_partials(size_t fr, size_t batch) const {
     const size_t tiles = tiles_of(fr), row = tiles * CSD_PLANES * bins() * sizeof(T);
-    const size_t rows_per = std::min(chunk_rows(batch, scratch_cap_, row), std::max<size_t>(1, LAUNCH_ITEMS / std::max(fr, tiles * WELCH_TILE)));
+    const size_t rows_per = std::min(chunk_rows(batch, scratch_cap_, row), std::max<size_t>(1, launch_items_ / std::max(fr, tiles * WELCH_TILE)));
     part_.ensure(rows_per * row);
     return rows_per;
   }
   // frame pairs per chunk of the composed route; sizes the scratch (2 x (bins complex + n_fft reals) per pair) and RealPlan's buffers
   size_t prepare_frames(size_t total) const {
     const size_t pair = 2 * (bins() * ELEM + n_fft() * sizeof(T));
-    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, pair), LAUNCH_ITEMS / 2);
+    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, pair), std::max<size_t>(1, launch_items_ / 2));
     scratch_.ensure(chunk * pair);
     stft_->real().reserve(2 * chunk);
     return chunk;
@@ -166,6 +167,7 @@ template <typename T> class CsdPlan : public HandleBase {
   FusionSwitch fusion_;
   mutable DevBuf scratch_, part_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -93,6 +93,8 @@ template <typename T> class CztPlan : public HandleBase {
       if (s->plan->enable_czt(real_)) one_ = s;
     }
     scratch_cap_ = scratch_bound("FOURIER_CZT_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", (size_t)1 << 30);
     set_fusion(one_ && !own_one_);  // the measured default: one launch where both routes run the same L
   }
 
@@ -128,7 +130,7 @@ template <typename T> class CztPlan : public HandleBase {
     const char* in = (const char*)d_in;
     cpx<T>* out = (cpx<T>*)d_out;
     if (route_ == ONE_LAUNCH) {  // one workgroup a row: launches of less than 2^31 workgroups
-      for_chunks(batch, (size_t)1 << 30, [&](size_t c0, size_t nb) {
+      for_chunks(batch, launch_items_, [&](size_t c0, size_t nb) {
         one_->plan->exec_czt(in + c0 * n_ * vs, out + c0 * m_, nb, n_, m_, atab_.p, btab_.p, one_->htab.p, real_, stream);
       });
       return;
@@ -192,7 +194,7 @@ template <typename T> class CztPlan : public HandleBase {
   // at most REAL_LAUNCH_BYTES of the work array
   void sweep(int which, const void* in, void* out, size_t nb, hipStream_t stream) const {
     const size_t L = comp_->L, vs = real_ ? sizeof(T) : ELEM;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / (L * ELEM));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / (L * ELEM));
     const bool first = which == CZT_IN;
     const size_t irow = first ? n_ * vs : L * ELEM, orow = first ? L * ELEM : m_ * ELEM;
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
@@ -214,7 +216,7 @@ template <typename T> class CztPlan : public HandleBase {
   // work rows (.) H in place: conv_mul_kernel (kernels_conv.h) with a bank of one table
   void multiply(cpx<T>* z, size_t nb, hipStream_t stream) const {
     const size_t L = comp_->L;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / (L * ELEM));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / (L * ELEM));
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
       ConvArgs a{};
@@ -243,6 +245,8 @@ template <typename T> class CztPlan : public HandleBase {
   Route route_ = COMPOSED;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
+  size_t launch_items_ = (size_t)1 << 30;  // rows of the one-launch route of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -11,11 +11,12 @@ template <typename T> struct FrameScratch {
   static constexpr size_t ELEM = sizeof(cpx<T>);
   mutable DevBuf buf;
   size_t cap = REAL_SCRATCH_BYTES;
+  size_t items = StftPlan<T>::LAUNCH_ITEMS;  // frames of one launch (the owner sets it with cap)
 
   // frames per chunk for `total` frames; sizes the scratch and RealPlan's buffers
   size_t prepare(const StftPlan<T>& stft, size_t total) const {
     const size_t frame = stft.bins() * ELEM + stft.n_fft() * sizeof(T);
-    const size_t chunk = std::min(chunk_rows(total, cap, frame), StftPlan<T>::LAUNCH_ITEMS);
+    const size_t chunk = std::min(chunk_rows(total, cap, frame), items);
     buf.ensure(chunk * frame);
     stft.real().reserve(chunk);
     return chunk;

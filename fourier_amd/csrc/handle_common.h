@@ -66,6 +66,13 @@ static inline size_t scratch_bound(const char* name, size_t dflt) {
   const char* e = dev_env(name);
   return e ? (size_t)std::strtoull(e, nullptr, 10) : dflt;
 }
+// a launch bound: `dflt` (what the kernels' 32-bit indices and 31-bit byte offsets allow), or what the development switch `name`
+// says where that is smaller and not 0 (FOURIER_LAUNCH_BYTES, FOURIER_LAUNCH_ITEMS; visible and read as scratch_bound's are)
+static inline size_t launch_bound(const char* name, size_t dflt) {
+  const char* e = dev_env(name);
+  const size_t v = e ? (size_t)std::strtoull(e, nullptr, 10) : dflt;
+  return v == 0 ? dflt : std::min(v, dflt);
+}
 
 // workgroups of 256 threads for a grid-stride sweep over `elems` elements
 static inline unsigned elementwise_grid(size_t elems) {

@@ -37,6 +37,8 @@ template <typename T> class HilbertPlan : public HandleBase {
       has_fused_ = plan_->enable_hilbert();
     }
     scratch_cap_ = scratch_bound("FOURIER_HILBERT_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", (size_t)1 << 30);
     set_fusion(false);
   }
 
@@ -82,7 +84,7 @@ template <typename T> class HilbertPlan : public HandleBase {
     const T* in = (const T*)d_in;
     if (route_ == ONE_LAUNCH) {  // one workgroup a row: launches of less than 2^31 workgroups
       const size_t orow = n_ * (envelope ? sizeof(T) : ELEM);
-      for_chunks(batch, (size_t)1 << 30, [&](size_t c0, size_t nb) {
+      for_chunks(batch, launch_items_, [&](size_t c0, size_t nb) {
         plan_->exec_hilbert(in + c0 * n_, (char*)d_out + c0 * orow, nb, envelope, stream);
       });
       return;
@@ -109,7 +111,7 @@ template <typename T> class HilbertPlan : public HandleBase {
   // hilbert_expand_kernel (rows of N/2 + 1 -> rows of N) or hilbert_abs_kernel (rows of N complex values -> rows of N reals) over nb
   // rows, in launches of at most REAL_LAUNCH_BYTES of the complex side
   void sweep(int which, const void* in, void* out, size_t nb, hipStream_t stream) const {
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / (n_ * ELEM));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / (n_ * ELEM));
     const bool expand = which == HILBERT_EXPAND;
     const size_t irow = (expand ? h_ + 1 : n_) * ELEM, orow = n_ * (expand ? ELEM : sizeof(T));
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
@@ -136,6 +138,8 @@ template <typename T> class HilbertPlan : public HandleBase {
   Route route_ = COMPOSED;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
+  size_t launch_items_ = (size_t)1 << 30;  // rows of the one-launch route of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

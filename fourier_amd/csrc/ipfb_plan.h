@@ -39,6 +39,7 @@ template <typename T> class IpfbPlan : public HandleBase {
     }
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     filt_.upload(std::vector<T>(span_, (T)1));
     desc_ = std::string("ipfb composed: ") + (real_out_ ? real_->describe() : plan_->describe());
   }
@@ -106,7 +107,7 @@ template <typename T> class IpfbPlan : public HandleBase {
   // the gather launches of a chunk: samples t0 ... t0 + span - 1 of nb rows from the frames f_lo ... f_lo + nfr - 1 in the scratch, in
   // pieces of at most LAUNCH_ITEMS samples of a row and LAUNCH_ITEMS lanes
   void gather(IpfbArgs& a, char* out, size_t nb, size_t t0, size_t span, size_t f_lo, size_t nfr, hipStream_t stream) const {
-    for_chunks(span, LAUNCH_ITEMS, [&](size_t s0, size_t ns) {
+    for_chunks(span, launch_items_, [&](size_t s0, size_t ns) {
       const size_t t = t0 + s0;
       // fb: the first frame that does not end before t, among those in the scratch
       const size_t fb = std::min(std::max(f_lo, t >= span_ ? (t - span_) / hop_ + 1 : 0), f_lo + nfr - 1);
@@ -115,7 +116,7 @@ template <typename T> class IpfbPlan : public HandleBase {
       a.q0 = (uint32_t)(fb - f_lo);
       a.kcount = (uint32_t)(nfr - (fb - f_lo));
       a.span = (uint32_t)ns;
-      for_chunks(nb, std::max<size_t>(1, LAUNCH_ITEMS / ns), [&](size_t r0, size_t nr) {
+      for_chunks(nb, std::max<size_t>(1, launch_items_ / ns), [&](size_t r0, size_t nr) {
         a.in = (const char*)scratch_.p + r0 * nfr * p_ * vs_;
         a.out = out + r0 * a.length * vs_;
         // two reals per store where every row of the launch starts its range on a 2 * sizeof(T)-aligned address
@@ -148,6 +149,7 @@ template <typename T> class IpfbPlan : public HandleBase {
   DevBuf filt_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // samples of a row, and lanes, of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

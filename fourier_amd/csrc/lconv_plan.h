@@ -40,6 +40,7 @@ template <typename T> class LinearConvPlan : public HandleBase {
     val_ = real_ ? sizeof(T) : ELEM;
     if (lx * val_ > ROW_BYTES_MAX || lout_ * val_ > ROW_BYTES_MAX) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "rows above 2^31 bytes");
     scratch_cap_ = scratch_bound("FOURIER_CONV_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_WORKGROUPS);
     select(0, true);
   }
 
@@ -114,7 +115,7 @@ template <typename T> class LinearConvPlan : public HandleBase {
     const char* in = (const char*)d_in;
     char* out = (char*)d_out;
     if (route_ == OVERLAP_SAVE) {
-      const size_t rows_per = std::max<size_t>(1, LAUNCH_WORKGROUPS / geo_.wpr);
+      const size_t rows_per = std::max<size_t>(1, launch_items_ / geo_.wpr);
       for_chunks(batch, rows_per, [&](size_t b0, size_t nb) {
         plan_->exec_lconv(in + b0 * lx_ * val_, out + b0 * lout_ * val_, nb, bank_.p, filters_, b0, real_, geo_, stream);
       });
@@ -202,7 +203,7 @@ template <typename T> class LinearConvPlan : public HandleBase {
   // lconv_copy_kernel: word skip + k of every input row (w_in words) -> word k of the output row (w_out words), zero beyond the input row
   void copy_rows(const void* src, void* dst, size_t rows, size_t w_in, size_t w_out, size_t skip, hipStream_t stream) const {
     const size_t segs = (w_out + LCONV_SEG - 1) / LCONV_SEG;
-    const size_t rows_per = std::max<size_t>(1, LAUNCH_WORKGROUPS / segs);
+    const size_t rows_per = std::max<size_t>(1, launch_items_ / segs);
     for_chunks(rows, rows_per, [&](size_t r0, size_t nr) {
       ConvArgs a{};
       a.in = (const T*)src + r0 * w_in;
@@ -230,6 +231,7 @@ template <typename T> class LinearConvPlan : public HandleBase {
   DevBuf bank_, taps_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_WORKGROUPS;  // workgroups of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

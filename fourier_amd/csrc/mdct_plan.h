@@ -31,6 +31,7 @@ template <typename T> class MdctPlan : public HandleBase {
     device_ = inner_->device();
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     // host f64, cast.  Even n: A[j] = exp(-i pi (4j + 1) / 4n) = W_8n^(4j+1), B[j] = exp(-i pi j / n) = W_2n^j, j < h;
     // odd n: D[m] = exp(-i pi m / 2n) = W_4n^m, m < 2n, C[k] = exp(-i pi (n + 1)(2k + 1) / 4n) = W_8n^((n+1)(2k+1)), k < n
     const uint64_t n64 = n_;
@@ -98,7 +99,7 @@ template <typename T> class MdctPlan : public HandleBase {
     a.scale = normalized ? std::sqrt(2.0 / (double)n_) : 1.0;
     if (fusion_.on) {
       a.pairs = (uintptr_t)out % ELEM == 0;
-      for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
+      for_chunks(total, launch_items_, [&](size_t g0, size_t ng) {
         frame_launch_at(a, in, length, fr, g0, ng);
         a.out = out + g0 * n_;
         inner_->exec_frames(a, stream);
@@ -194,7 +195,7 @@ template <typename T> class MdctPlan : public HandleBase {
   }
   // frames per chunk of the composed forward routes
   size_t prepare_forward(size_t total) const {
-    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, frame_bytes()), LAUNCH_ITEMS);
+    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, frame_bytes()), launch_items_);
     prepare(chunk);
     return chunk;
   }
@@ -202,7 +203,7 @@ template <typename T> class MdctPlan : public HandleBase {
   // inverse() size from the same function)
   FrameOverlap overlap() const { return {2 * n_, n_, pad_}; }
   FrameInverseChunks inverse_chunks(size_t fr, size_t batch) const {
-    return frame_inverse_chunks(overlap(), fr, batch, std::min(scratch_cap_ / frame_bytes(), LAUNCH_ITEMS));
+    return frame_inverse_chunks(overlap(), fr, batch, std::min(scratch_cap_ / frame_bytes(), launch_items_));
   }
 
   size_t n_, h_;
@@ -214,6 +215,7 @@ template <typename T> class MdctPlan : public HandleBase {
   DevBuf win_, twa_, twb_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -40,6 +40,7 @@ template <typename T> class PfbPlan : public HandleBase {
     }
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     filt_.upload(std::vector<T>(span_, (T)1));
     // Where the fused route is the default: wherever its kernel exists.  Every measured shape of every (precision, input kind) -- P 256
     // and 1024, T 4 and 8, D = P and 3 P / 4, 64 rows of 2^20 values -- took 0.46 - 0.67 of the composed route's time (f64 complex rows,
@@ -105,7 +106,7 @@ template <typename T> class PfbPlan : public HandleBase {
     if (fusion_.on) {
       const Plan<T>& inner = real_in_ ? real_->inner() : *plan_;
       if (real_in_) a.tw = real_->twiddles();
-      for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
+      for_chunks(total, launch_items_, [&](size_t g0, size_t ng) {
         launch_at(a, d_in, length, fr, g0, ng);
         // the real rows' load takes two reals per access where every frame starts on an even element of a 2 * sizeof(T)-aligned row
         a.pairs = real_in_ && hop_ % 2 == 0 && length % 2 == 0 && (uintptr_t)a.in % (2 * sizeof(T)) == 0;
@@ -135,7 +136,7 @@ template <typename T> class PfbPlan : public HandleBase {
   }
   // frames per chunk of the composed route; sizes the scratch and the inner plan's buffers
   size_t prepare(size_t total) const {
-    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, p_ * vs_), LAUNCH_ITEMS);
+    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, p_ * vs_), launch_items_);
     scratch_.ensure(chunk * p_ * vs_);
     if (real_in_) real_->reserve(chunk);
     else plan_->reserve_for(chunk, false);
@@ -152,6 +153,7 @@ template <typename T> class PfbPlan : public HandleBase {
   DevBuf filt_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -28,6 +28,7 @@ template <typename T> class R2RPlan : public HandleBase {
     for (size_t j = 0; j < ct.size(); ++j) ct[j] = root<T>(j, 4 * (uint64_t)n_);
     ct_.upload(ct);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
     desc_ = std::string(even_ ? "r2r half-length: " : "r2r full-length: ") + inner_->describe();
   }
 
@@ -87,7 +88,7 @@ template <typename T> class R2RPlan : public HandleBase {
   // values have the same size)
   void sweep(int which, const void* in, void* out, size_t nb, int sine, double scale, double edge, hipStream_t stream) const {
     const size_t row = h_ * ELEM;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / row);
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / row);
     const uint32_t lanes = (uint32_t)((which == R2R_PACK || which == R2R_UNPACK) ? (h_ + 1) / 2 : h_ / 2 + 1);
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
@@ -126,6 +127,7 @@ template <typename T> class R2RPlan : public HandleBase {
   DevBuf tw_, ct_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
 };
 
 }  // namespace fourier_hip

@@ -33,6 +33,7 @@ template <typename T> class RealPlan : public HandleBase {
     DeviceGuard g(inner_->device());
     if (even_) tw_.upload(real_untangle_twiddles<T>(n_));
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
     desc_ = std::string(even_ ? "real half-length: " : "real full-length: ") + inner_->describe();
   }
 
@@ -116,7 +117,7 @@ template <typename T> class RealPlan : public HandleBase {
   // the untangle sweep over nb rows, in launches of at most REAL_LAUNCH_BYTES per side
   void sweep(int which, const cpx<T>* in, cpx<T>* out, size_t nb, double scale, hipStream_t stream) const {
     const size_t zrow = h_ * ELEM, xrow = (h_ + 1) * ELEM;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / xrow);
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / xrow);
     const uint32_t pairs = (uint32_t)(h_ / 2 + 1);
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
@@ -150,6 +151,7 @@ template <typename T> class RealPlan : public HandleBase {
   DevBuf tw_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one untangle launch (development switch FOURIER_LAUNCH_BYTES)
 };
 
 }  // namespace fourier_hip

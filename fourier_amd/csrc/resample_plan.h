@@ -43,6 +43,7 @@ template <typename T> class ResamplePlan : public HandleBase {
       device_ = pin_->device();
     }
     scratch_cap_ = scratch_bound("FOURIER_RESAMPLE_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
     // Where the fused untangle route is the default: wherever it exists.  Every real even / even shape measured -- 64 rows of 2^20 ->
     // 2^19 and 2^20 -> 2^21, 1024 rows of 48000 -> 44100 and 44100 -> 48000, f32 and f64 -- took 0.79 - 0.84 of the composed route's
     // time, the gap beyond the larger max - min of the two arms on all 8 lines ("Fourier-domain resampling";
@@ -157,7 +158,7 @@ template <typename T> class ResamplePlan : public HandleBase {
     const bool fused = which == RESAMPLE_UNTANGLE;
     const size_t ivals = fused ? n_ / 2 : real_ ? n_ / 2 + 1 : n_, ovals = fused ? m_ / 2 : real_ ? m_ / 2 + 1 : m_;
     const size_t irow = ivals * ELEM, orow = ovals * ELEM;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / std::max(irow, orow));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / std::max(irow, orow));
     const size_t k = std::min(n_, m_);
     const size_t lanes = fused ? ovals / 2 + 1 : ovals;  // per row
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
@@ -195,6 +196,7 @@ template <typename T> class ResamplePlan : public HandleBase {
   bool has_win_ = false;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
 };
 
 }  // namespace fourier_hip

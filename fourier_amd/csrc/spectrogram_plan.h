@@ -30,6 +30,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     device_ = stft_->real().inner().device();
     DeviceGuard g(device_);
     scratch_cap_ = frames_.cap = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = frames_.items = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     // Where the fused route is the default: nowhere yet.  The project's rule is that a default follows a measurement (the STFT's fused
     // route became one after tools/stft_bench.py), and tools/spectrogram_bench.py has not run on an MI355X -- DESIGN.md section 4, "Power
     // spectrogram and Welch average".  Option "fusion" = 1 selects the fused kernels wherever they exist.
@@ -80,7 +81,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
     a.bins = (uint32_t)bins;
     a.power = (uint32_t)power;
     if (fusion_.on) {
-      for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
+      for_chunks(total, launch_items_, [&](size_t g0, size_t ng) {
         stft_->fused_launch_at(a.f, in, length, fr, g0, ng);
         a.f.out = out + g0 * bins;
         stft_->real().inner().exec_frames(a, stream, power);
@@ -152,7 +153,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
   // rows per group of a Welch call: their partials fit the bound (never less than one row's) and one launch's 32-bit indices
   size_t prepare_partials(size_t fr, size_t batch) const {
     const size_t tiles = tiles_of(fr), row = tiles * bins() * sizeof(T);
-    const size_t rows_per = std::min(chunk_rows(batch, scratch_cap_, row), std::max<size_t>(1, LAUNCH_ITEMS / std::max(fr, tiles * WELCH_TILE)));
+    const size_t rows_per = std::min(chunk_rows(batch, scratch_cap_, row), std::max<size_t>(1, launch_items_ / std::max(fr, tiles * WELCH_TILE)));
     part_.ensure(rows_per * row);
     return rows_per;
   }
@@ -170,6 +171,7 @@ template <typename T> class SpectrogramPlan : public HandleBase {
   FrameScratch<T> frames_;  // the composed routes' scratch (frame_scratch.h)
   mutable DevBuf part_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

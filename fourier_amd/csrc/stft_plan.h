@@ -42,6 +42,7 @@ template <typename T> class StftPlan : public HandleBase {
     device_ = real_->inner().device();
     DeviceGuard g(device_);
     scratch_cap_ = scratch_bound("FOURIER_REAL_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", LAUNCH_ITEMS);
     load_window(std::vector<T>(wl_, (T)1));
     // Where the fused route is the default: wherever its kernel exists.  Every (precision, n_fft) measured 0.31 - 0.42 of the composed
     // route's time at hop = n_fft / 4 and n_fft / 2, against a spread of 1 - 4 % ("Short-time Fourier transform";
@@ -137,7 +138,7 @@ template <typename T> class StftPlan : public HandleBase {
     cpx<T>* out = (cpx<T>*)d_out;
     if (fusion_.on) {
       StftArgs a = fused_args(length, fr, normalized);
-      for_chunks(total, LAUNCH_ITEMS, [&](size_t g0, size_t ng) {
+      for_chunks(total, launch_items_, [&](size_t g0, size_t ng) {
         fused_launch_at(a, in, length, fr, g0, ng);
         a.out = out + g0 * bins_;
         real_->inner().exec_frames(a, stream);
@@ -200,7 +201,7 @@ template <typename T> class StftPlan : public HandleBase {
   }
   // frames per chunk of the composed forward route; sizes the scratch and RealPlan's buffers
   size_t prepare_forward(size_t total) const {
-    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, n_ * sizeof(T)), LAUNCH_ITEMS);
+    const size_t chunk = std::min(chunk_rows(total, scratch_cap_, n_ * sizeof(T)), launch_items_);
     scratch_.ensure(chunk * n_ * sizeof(T));
     real_->reserve(chunk);
     return chunk;
@@ -248,6 +249,7 @@ template <typename T> class StftPlan : public HandleBase {
   mutable std::map<std::pair<size_t, size_t>, std::unique_ptr<DevBuf>> env_;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_items_ = LAUNCH_ITEMS;  // frames of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -59,6 +59,8 @@ template <typename T> class XcorrPlan : public HandleBase {
       device_ = plan_->device();
     }
     scratch_cap_ = scratch_bound("FOURIER_XCORR_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
+    launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
+    launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", (size_t)1 << 30);
     // Where the one-launch route is the default: wherever it exists.  Every shape measured -- f64, L = 2^11, 2^13, 2^14, n = L / 2, the
     // full linear window, 512 MiB of input -- took 0.23 - 0.37 of the composed route's time, the gap beyond the larger max - min of the
     // two arms on all 3 lines ("Cross-correlation"; profiles/xcorr/xcorr_bench.jsonl).
@@ -109,7 +111,7 @@ template <typename T> class XcorrPlan : public HandleBase {
     const char* y = (const char*)d_y;
     char* out = (char*)d_out;
     if (route_ == ONE_LAUNCH) {  // one workgroup a row pair: launches of less than 2^31 workgroups
-      for_chunks(batch, (size_t)1 << 30, [&](size_t c0, size_t nb) {
+      for_chunks(batch, launch_items_, [&](size_t c0, size_t nb) {
         plan_->exec_xcorr(x + c0 * n_ * vs, y + c0 * n_ * vs, out + c0 * lags_ * vs, nb, n_, first_, lags_, phat_, stream);
       });
       return;
@@ -174,7 +176,7 @@ template <typename T> class XcorrPlan : public HandleBase {
     const size_t ivals = which == XCORR_PAD ? n_ : which == XCORR_MUL ? spec : l_;
     const size_t ovals = which == XCORR_PAD ? l_ : which == XCORR_MUL ? spec : lags_;
     const size_t irow = ivals * vs, orow = ovals * vs;
-    const size_t rows_per = std::max<size_t>(1, REAL_LAUNCH_BYTES / std::max(irow, orow));
+    const size_t rows_per = std::max<size_t>(1, launch_bytes_ / std::max(irow, orow));
     for (size_t r0 = 0; r0 < nb; r0 += rows_per) {
       const size_t rows = std::min(rows_per, nb - r0);
       XcorrArgs a{};
@@ -204,6 +206,8 @@ template <typename T> class XcorrPlan : public HandleBase {
   Route route_ = COMPOSED;
   mutable DevBuf scratch_;
   size_t scratch_cap_ = REAL_SCRATCH_BYTES;
+  size_t launch_bytes_ = REAL_LAUNCH_BYTES;  // of either side of one sweep launch (development switch FOURIER_LAUNCH_BYTES)
+  size_t launch_items_ = (size_t)1 << 30;  // rows of the one-launch route of one launch (development switch FOURIER_LAUNCH_ITEMS)
 };
 
 }  // namespace fourier_hip

@@ -65,7 +65,8 @@ def test_product_library_has_no_environment_switches_and_no_experiment_kernels(t
     measured-slower designs are not compiled into it."""
     base = {n: make(fa, n, np.complex64).describe() for n in (1 << 14, 1 << 21, 1 << 22, 1 << 23, 96, 999983)}
     for var in ("FOURIER_NO_TWOLEVEL", "FOURIER_WIDE_2048", "FOURIER_SPLIT_2048", "FOURIER_PLAN_4096", "FOURIER_THREE_PASS_2P23",
-                "FOURIER_L2_FUSED", "FOURIER_MIX_GENERIC", "FOURIER_MIX_MAX_N", "FOURIER_BLU_SHORT_FIRST", "FOURIER_CONV_XCD_PLAIN"):
+                "FOURIER_L2_FUSED", "FOURIER_MIX_GENERIC", "FOURIER_MIX_MAX_N", "FOURIER_BLU_SHORT_FIRST", "FOURIER_CONV_XCD_PLAIN",
+                "FOURIER_LAUNCH_BYTES", "FOURIER_LAUNCH_ITEMS"):
         monkeypatch.setenv(var, "1")
     assert {n: make(fa, n, np.complex64).describe() for n in base} == base
     with pytest.raises(fa.FourierError):
