@@ -106,6 +106,11 @@ _XCORR = ("fourier_hip_xcorr_", {  # pairwise cross-correlation and GCC-PHAT of 
     "destroy": (None, [vp]), "size": (sz, [vp]), "length": (sz, [vp]), "lags": (sz, [vp]),
     "correlate": (ci, [vp, vp, vp, vp, sz, vp]),  # handle, d_x, d_y, d_out, batch, stream
     "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_DELAY = ("fourier_hip_delay_", {  # fractional delay and delay-and-sum of real or complex rows, delays and weights on the device
+    "create": (vp, [sz, sz, sz, ci, ci]),  # size, length, channels, real_data, device
+    "destroy": (None, [vp]), "size": (sz, [vp]), "length": (sz, [vp]), "channels": (sz, [vp]),
+    "apply": (ci, [vp, vp, vp, vp, vp, sz, vp]),  # handle, d_in, d_delays, d_weights (may be NULL), d_out, batch, stream
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -134,8 +139,9 @@ PFB_SYMBOLS = list(_signatures(_PFB))
 IPFB_SYMBOLS = list(_signatures(_IPFB))
 RESAMPLE_SYMBOLS = list(_signatures(_RESAMPLE))
 XCORR_SYMBOLS = list(_signatures(_XCORR))
+DELAY_SYMBOLS = list(_signatures(_DELAY))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -145,7 +151,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -29,6 +29,7 @@
 #include "ipfb_plan.h"
 #include "resample_plan.h"
 #include "xcorr_plan.h"
+#include "delay_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -686,6 +687,34 @@ FOURIER_DEFINE_RESAMPLE_ABI(double, double)
 
 FOURIER_DEFINE_XCORR_ABI(float, float)
 FOURIER_DEFINE_XCORR_ABI(double, double)
+
+// fractional delay and delay-and-sum (fourier_hip_delay_*)
+#define FOURIER_DEFINE_DELAY_ABI(T, SUFFIX)                                                                      \
+  FOURIER_DEFINE_HANDLE_ABI(delay, fourier_delay_##SUFFIX, DelayPlan<T>, SUFFIX)                                 \
+  extern "C" fc::fourier_delay_##SUFFIX* fourier_hip_delay_create_##SUFFIX(size_t size, size_t length, size_t channels, int real_data, \
+                                                                           int device) {                        \
+    return (fc::fourier_delay_##SUFFIX*)create_handle<DelayPlan<T>>(size, length, channels, real_data, device);  \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_delay_size_##SUFFIX(const fc::fourier_delay_##SUFFIX* h) {                       \
+    return h ? ((const DelayPlan<T>*)h)->size() : 0;                                                             \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_delay_length_##SUFFIX(const fc::fourier_delay_##SUFFIX* h) {                     \
+    return h ? ((const DelayPlan<T>*)h)->length() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_delay_channels_##SUFFIX(const fc::fourier_delay_##SUFFIX* h) {                   \
+    return h ? ((const DelayPlan<T>*)h)->channels() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_delay_apply_##SUFFIX(const fc::fourier_delay_##SUFFIX* h, const void* d_in, const void* d_delays, \
+                                                  const void* d_weights, void* d_out, size_t batch, void* stream) { \
+    const DelayPlan<T>* p = (const DelayPlan<T>*)h;                                                              \
+    return guarded_handle(p, [&] { p->apply(d_in, d_delays, d_weights, d_out, batch, (hipStream_t)stream); });   \
+  }                                                                                                              \
+  extern "C" int fourier_hip_delay_set_option_##SUFFIX(fc::fourier_delay_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<DelayPlan<T>>(h, key, v);                                                           \
+  }
+
+FOURIER_DEFINE_DELAY_ABI(float, float)
+FOURIER_DEFINE_DELAY_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

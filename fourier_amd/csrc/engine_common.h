@@ -205,6 +205,7 @@ typedef void (*HilbertKernel)(HilbertArgs);
 typedef void (*CztKernel)(CztArgs);
 typedef void (*ResampleKernel)(ResampleArgs);
 typedef void (*XcorrKernel)(XcorrArgs);
+typedef void (*DelayKernel)(DelayArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -329,6 +330,11 @@ template <typename T> struct Real {};
   /* which = XCORR_PAD ... XCORR_WINDOW, real or complex values                                                         */ \
   bool get_xcorr_small_kernel(Real<T>, int k, bool phat, KernelInfo& info);                                            \
   XcorrKernel get_xcorr_kernel(Real<T>, int which, bool real_data, bool phat);                                         \
+  /* kernels_delay.cpp: the fractional delay of real rows in one launch on the shapes of the two-level plans              */ \
+  /* (delay_small_kernel), where it spills no more than the envelope kernel of the same shape; the composed routes' sweep */ \
+  /* delay_mul_kernel on half spectra (real_data) or whole spectra                                                       */ \
+  bool get_delay_small_kernel(Real<T>, int k, KernelInfo& info);                                                       \
+  DelayKernel get_delay_kernel(Real<T>, bool real_data);                                                               \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

@@ -291,6 +291,33 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
   }
 
+  // The fractional delay of real rows in one launch (delay_small_kernel; the delay handle): conv_small_kernel's shapes and tables, where
+  // kernels_delay.cpp holds an instance of the length.
+  bool enable_delay_small() {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    if (delay_small_.fn) return true;
+    KernelInfo k;
+    if (!get_delay_small_kernel(Real<T>{}, ilog2(n_), k)) return false;
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    set_smem_attribute(k);
+    delay_small_ = k;
+    return true;
+  }
+  // in: `batch` rows of n <= n_ reals; out: rows of n reals, in == out allowed; delays, weights (may be null): `batch` reals each
+  void run_delay_small(const void* in, const void* delays, const void* weights, void* out, size_t batch, uint32_t n, hipStream_t stream,
+                       unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.dl_delays = delays; a.dl_weights = weights; a.dl_n = n;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    launch(nullptr, 0, delay_small_.fn, batch, delay_small_.NT, delay_small_.smem, stream, a);
+  }
+
   // The cross-correlation of two real rows in one launch (xcorr_small_kernel; the cross-correlation handle): conv_small_kernel's shapes
   // and tables; one kernel for each weighting, and only where it runs without scratch memory (kernels_xcorr.cpp; the development
   // switch FOURIER_XCORR_SPILLING, read here, takes every instance from the experiments library instead).  Returns the weightings that have one: bit 0 none, bit 1 PHAT.
@@ -777,6 +804,7 @@ template <typename T> class Pow2Engine {
   KernelInfo blu_small_, conv_, conv_bank_, conv_small_, lconv_small_[2];  // lconv_small_: complex rows, real rows
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
   KernelInfo xcorr_small_[2];    // no weighting, PHAT
+  KernelInfo delay_small_;       // the fractional delay of real rows
   KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
   std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel, BandSpecRowsKernel> frame_rows_;

@@ -76,6 +76,11 @@ struct PassArgs {
   // t of the n-point circular correlation goes to output position (t - xc_first) mod n where that is below xc_lags
   const void* xc_in2;
   uint32_t xc_n, xc_first, xc_lags;  // xc_first = lag_first mod n
+  // delay_small_kernel (DelayPlan, delay_plan.h): rows of dl_n reals in and out; row b of the launch is delayed by dl_delays[b]
+  // samples and scaled by dl_weights[b] (null: 1), both reals T on the device
+  const void* dl_delays;
+  const void* dl_weights;
+  uint32_t dl_n;
 };
 
 
@@ -485,6 +490,23 @@ struct XcorrArgs {
   uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
   int real, phat;
   double scale;               // mul: the inverse's 1 / l, computed in T
+};
+
+// ---- fractional delay and delay-and-sum (kernels_delay.h; DelayPlan, delay_plan.h): the composed routes' one sweep, one lane per
+// output bin over a flat index; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of either side per launch).
+// delay_mul_kernel: groups of `channels` consecutive spectra of `spec` bins (the half spectrum l / 2 + 1 of real rows, or all l bins) ->
+// one row of `spec` bins a group, sum_c w[c] X[c][k] m(k, d[c]) * scale in ascending c; the delays and weights (null: 1) are reals T,
+// one per input row, and never enter an address.
+struct DelayArgs {
+  const void* in; void* out;
+  const void* delays; const void* weights;  // of the launch's first input row on
+  uint32_t l, spec;           // the transform length; bins per row
+  uint32_t channels;          // input rows per output row
+  uint32_t total;             // output rows * spec
+  uint32_t div_m, div_l;      // idx / spec = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t len_m, len_l;      // the same for x / l, used where l <= 65536 (the exponent k * d_int fits 32 bits)
+  uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
+  double scale;               // the inverse's 1 / l, computed in T
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

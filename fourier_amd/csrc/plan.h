@@ -613,6 +613,21 @@ template <typename T> class Plan : public HandleBase {
     eng_->run_xcorr_small(d_x, d_y, d_out, batch, (uint32_t)n, (uint32_t)first, (uint32_t)lags, phat, stream, nxcd_);
   }
 
+  // ---- the hook of the delay handle (DelayPlan, delay_plan.h); exec() is not affected.  A one-launch two-level plan of L points
+  // (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n <= L reals in one launch of delay_small_kernel: row b delayed by d_delays[b]
+  // samples, circularly over L, and scaled by d_weights[b] (null: 1); rows of n reals out, d_out == d_in allowed.  The caller keeps
+  // `batch` below 2^31.
+  bool enable_delay() {
+    if (blu_ || !eng_) return false;
+    DeviceGuard g(device_);
+    return eng_->enable_delay_small();
+  }
+  void exec_delay(const void* d_in, const void* d_delays, const void* d_weights, void* d_out, size_t batch, size_t n,
+                  hipStream_t stream) const {
+    DeviceGuard g(device_);
+    eng_->run_delay_small(d_in, d_delays, d_weights, d_out, batch, (uint32_t)n, stream, nxcd_);
+  }
+
   // ---- the hook of the chirp-z handle (CztPlan, czt_plan.h); exec() is not affected.  A one-launch two-level plan of L points
   // (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n values (complex, or reals) in one launch of czt_small_kernel: rows of m complex
   // values out, apart from the input, n + m - 1 <= L.  The tables are the caller's: A (n entries), B (m entries), H (L entries, spectrum

@@ -1675,6 +1675,156 @@ def gcc_phat(x, y, max_lag=None, mode="linear", dim=-1, out=None):
     return xcorr(x, y, max_lag, mode, "phat", dim, out)
 
 
+class Delay(_Handle):
+    """Batched fractional delay and delay-and-sum (include/fourier.h, fourier_hip_delay_*) on device memory: rows of n values,
+    zero-extended to the transform length `length` = L >= n, are delayed by one delay per row (in samples, any finite real, read from
+    DEVICE memory), optionally weighted, and summed over groups of `channels` = C consecutive rows:
+        Y[g] = sum_c w[gC + c] fft(x[gC + c], L) m(., d[gC + c]),    out[g] = ifft(Y[g])[:n],    m(k, d) = exp(-2 pi i k d / L)
+    with signed bin indices k and cos(pi d) at the Nyquist bin.  A POSITIVE delay delays: out[t] = x[t - d]; to align a channel that
+    arrived late by tau pass -tau.  The shift is circular over L: L >= n + ceil(max |d|) is the linear delay with zeros shifting in,
+    L == n the circular shift.  Real rows (real_data=True, the default) give real output, complex rows complex output."""
+
+    _prefix = "fourier_hip_delay_"
+    _destroy = "fourier_hip_delay_destroy"
+
+    def __init__(self, n, length, real="f32", real_data=True, channels=1, device=-1):
+        n, length, channels = int(n), int(length), int(channels)
+        if not 1 <= n <= length:
+            raise ValueError(f"need 1 <= n <= length, got {n}, {length}")
+        if channels < 1:
+            raise ValueError(f"need channels >= 1, got {channels}")
+        self._create(real, f"delay plan of {n} values in {length}, {channels} channels", n, length, channels, int(bool(real_data)), int(device))
+        self._n, self._l, self._c, self.real_data = n, length, channels, bool(real_data)
+
+    def size(self):
+        return self._n
+
+    def length(self):
+        return self._l
+
+    def channels(self):
+        return self._c
+
+    def set_option(self, key, value):
+        """"fusion": 1 (default) = the one-launch kernel where the library has one (real rows, one channel, length 2^11 ... 2^15, f64
+        ... 2^14), 0 = the composed route."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def apply_ptr(self, d_in, d_delays, d_weights, d_out, batch, stream=0):
+        """`batch` rows of n values at d_in, `batch` delays at d_delays and `batch` weights at d_weights (None or 0: every weight 1), all
+        of the handle's real type on the device -> batch / channels() rows of n values at d_out (d_in allowed when channels() == 1),
+        enqueued on `stream`."""
+        self._call("apply", d_in, d_delays, d_weights or None, d_out, int(batch), stream)
+
+    def apply(self, x, delays, weights=None, out=None):
+        """A contiguous (..., n) CUDA tensor, float (real_data) or complex of the handle's precision, whose row count is a multiple of
+        channels(); `delays` and `weights` (optional) contiguous real CUDA tensors with one element per row of x -> a new tensor, or
+        `out` (which may be `x` when channels() == 1): shape x.shape for one channel, else (rows / channels, n), on the current stream."""
+        import torch
+
+        rdt, cdt = _torch_dtypes(self.real)
+        dt = rdt if self.real_data else cdt
+        _require_cuda(x, dt)
+        _require_cuda(delays, rdt)
+        if weights is not None:
+            _require_cuda(weights, rdt)
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        batch = x.numel() // self._n
+        if batch % self._c:
+            raise ValueError(f"{batch} rows are not a multiple of {self._c} channels")
+        for name, t in (("delays", delays), ("weights", weights)):
+            if t is not None and (t.numel() != batch or t.device != x.device):
+                raise ValueError(f"{name} must hold one element per row of x ({batch}) on its device, got {tuple(t.shape)}")
+        shape = tuple(x.shape) if self._c == 1 else (batch // self._c, self._n)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=x.device)
+        else:
+            _require_out(out, shape, dt, x.device)
+            a0, b0 = x.data_ptr(), out.data_ptr()
+            nin, nout = x.numel() * x.element_size(), out.numel() * out.element_size()
+            if (a0 != b0 or self._c > 1) and a0 < b0 + nout and b0 < a0 + nin:
+                raise ValueError("input and output overlap" + (" partially" if self._c == 1 else ""))
+        if batch:
+            self.apply_ptr(x.data_ptr(), delays.data_ptr(), None if weights is None else weights.data_ptr(), out.data_ptr(), batch, _stream(x))
+        return out
+
+
+def create_delay_f32(n, length, real_data=True, channels=1, device=-1):
+    return Delay(n, length, "f32", real_data, channels, device)
+
+
+def create_delay_f64(n, length, real_data=True, channels=1, device=-1):
+    return Delay(n, length, "f64", real_data, channels, device)
+
+
+def _delay_rows(x, lead, delays, weights, length, channels, out, out_shape):
+    """fractional_delay / delay_and_sum: one value of `delays` (and `weights`) per row of x, broadcast over `lead` on the device"""
+    import torch
+
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None):
+        raise TypeError("expected a CUDA float32 / float64 / complex64 / complex128 tensor")
+    real, real_data = _precision(x.dtype)
+    rdt = _torch_dtypes(real)[0]
+    n = int(x.shape[-1])
+    if n < 1:
+        raise ValueError("the delayed dimension must have length >= 1")
+    length = n if length is None else int(length)
+    if length < n:
+        raise ValueError(f"need length >= n, got {length}, {n}")
+
+    def per_row(v, name):
+        if _is_torch(v):
+            if not (v.is_cuda and v.device == x.device and v.dtype == rdt):
+                raise TypeError(f"{name} must be a CUDA {_names((rdt,))} tensor on x's device, or a Python number")
+        elif isinstance(v, (int, float)):
+            v = torch.full((), float(v), dtype=rdt, device=x.device)  # broadcast on the device
+        else:
+            raise TypeError(f"{name} must be a CUDA {_names((rdt,))} tensor on x's device, or a Python number")
+        try:
+            return v.expand(lead).contiguous()
+        except RuntimeError:
+            raise ValueError(f"{name} of shape {tuple(v.shape)} do not broadcast to {tuple(lead)}") from None
+
+    d = per_row(delays, "delays")
+    w = None if weights is None else per_row(weights, "weights")
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == tuple(out_shape)
+                                and out.device == x.device and out.is_contiguous()):
+        raise TypeError(f"out must be a contiguous CUDA {_names((x.dtype,))} tensor of shape {tuple(out_shape)} on the input's device")
+    plan = _cached_plan(Delay, n, length, real, real_data, channels, int(_device_index(x)))
+    res = plan.apply(x.contiguous().view(-1, n), d, w, None if out is None else out.view(-1, n))
+    return out if out is not None else res.view(out_shape)
+
+
+def fractional_delay(x, delays, length=None, out=None):
+    """The rows of a CUDA tensor `x` of shape (..., n) (float32 / float64: real output; complex64 / complex128: complex output), each
+    delayed by its own number of samples, on the current stream: out[..., t] = x[..., t - d] by the band-limited (Fourier)
+    interpolation of the row.  `delays`: a real CUDA tensor of x's precision broadcastable to x.shape[:-1], or a Python number (it is
+    broadcast on the device; nothing is copied to the host either way).  A positive delay delays.  `length` is the transform length
+    L >= n over which the shift is circular: length=None means L = n, the CIRCULAR shift (what leaves on the right comes back on the
+    left); pass L >= n + ceil(max |d|) for the linear delay with zeros shifting in.  Returns a new tensor of x's shape, or `out`
+    (which may be `x`).  One cached Delay handle per (n, length, dtype, device)."""
+    if _is_torch(x) and x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    shape = tuple(x.shape) if _is_torch(x) else ()
+    return _delay_rows(x, shape[:-1], delays, None, length, 1, out, shape)
+
+
+def delay_and_sum(x, delays, weights=None, length=None, out=None):
+    """Delay-and-sum beamforming of a CUDA tensor `x` of shape (..., C, n): out[..., t] = sum_c weights[..., c] x[..., c, t -
+    delays[..., c]], shape (..., n), on the current stream.  `delays` and `weights` (None: every weight 1, a plain sum and not a
+    mean): real CUDA tensors of x's precision broadcastable to x.shape[:-1], or Python numbers.  The channels are summed on their
+    spectra: C forward transforms and ONE inverse a group.  A positive delay delays; to align a channel that arrived late by tau pass
+    -tau.  `length` as in fractional_delay: None means L = n, the CIRCULAR shift.  Returns a new tensor or `out` (which may not
+    overlap `x`).  One cached Delay handle per (n, length, C, dtype, device)."""
+    if _is_torch(x) and x.dim() < 2:
+        raise ValueError("expected at least two dimensions (..., C, n)")
+    shape = tuple(x.shape) if _is_torch(x) else (1, 1)
+    if shape[-2] < 1:
+        raise ValueError("expected at least one channel")
+    return _delay_rows(x, shape[:-1], delays, weights, length, shape[-2], out, shape[:-2] + shape[-1:])
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

@@ -1443,6 +1443,77 @@ const char *fourier_hip_xcorr_describe_double(const FOURIER_STRUCT fourier_xcorr
 int fourier_hip_xcorr_last_status_float(const FOURIER_STRUCT fourier_xcorr_float *);
 int fourier_hip_xcorr_last_status_double(const FOURIER_STRUCT fourier_xcorr_double *);
 
+/* ---------------- fractional delay and delay-and-sum (extension; the reference has none) ----------
+ * `batch` rows x[r] of n = `size` values on DEVICE memory, row r at element offset r*n -- REALS T where the handle was created with
+ * real_data = 1, interleaved COMPLEX values with real_data = 0 --, zero-extended to the transform length L = `length` >= n, are
+ * delayed by d[r] samples each, optionally weighted by w[r], and summed over groups of C = `channels` consecutive rows (C = 1: the
+ * plain fractional delay).  With X = fft(x~, L):
+ *   Y[g][k] = sum_{c < C, ascending c} w[gC+c] X[gC+c][k] m(k, d[gC+c]),    out[g][t] = ifft(Y[g])[t],  t = 0 .. n-1,
+ *   m(k, d) = exp(-2 pi i k' d / L),  k' = k for k < L/2 and k - L for k > L/2;   m(L/2, d) = cos(pi d)  (even L, real and complex rows),
+ * batch / C rows of n values out, reals for real rows and complex values for complex rows.  A POSITIVE d delays: out[t] = x[t - d]; to
+ * align a channel that arrived late by tau pass -tau.  The shift is circular over L; with L >= n + ceil(max |d|) it is the linear
+ * delay with zeros shifting in, and L == n is the circular shift (an integer d: numpy.roll).
+ * d_delays and d_weights hold one value of the handle's real type T per INPUT row, on the device: the delays in samples, the weights
+ * reals.  d_weights == NULL means every weight is 1 (a plain sum, not a mean).  Nothing about them crosses to the host: the argmax of
+ * a GCC-PHAT can feed d_delays directly, and a captured graph may be replayed after they were overwritten.  Any finite T is a valid
+ * delay; the phase error does not grow with |d| or with k: d is reduced modulo L by fmod and split into rint and a remainder (all
+ * exact), (k d_int) mod L is formed in integer arithmetic, the fraction adds at most a quarter turn, and one accurate sincospi of the
+ * sum follows.  A delay never enters an address: a delay or weight that is not finite makes the output rows of its group not finite
+ * and touches nothing else; it is not an error.
+ * 1 <= n <= L, C >= 1 and real_data 0 / 1, else create fails; so it does for L * 2 * sizeof(T) > 2^31 - 1 (as
+ * fourier_hip_hilbert_create_*) and for C * L * 2 * sizeof(T) > 2^31 - 1.  batch % C != 0, a NULL d_in / d_delays / d_out, a real
+ * buffer (d_delays and d_weights included) not aligned to sizeof(T) or a complex one not aligned to 2*sizeof(T), a partial overlap of
+ * input and output, and ANY overlap of them when C > 1 give FOURIER_HIP_INVALID_ARGUMENT.  d_out == d_in is allowed when C == 1.
+ * batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_delay_describe_* begins with the route's name):
+ *   "delay one-launch"  REAL rows, C == 1, L = 2^11 ... 2^15 (double: ... 2^14), any n <= L: load, FFT, the phase (from the bin index, no
+ *                       table), inverse FFT and the store of the first n values in ONE launch on register-resident data; no scratch.
+ *   "delay composed"    every L, real and complex rows, every C: the rows are padded to L and transformed (real rows: to half spectra of
+ *                       L/2 + 1 values), ONE sweep forms Y / L for each group, ONE unscaled inverse a group follows -- straight into the
+ *                       caller's output where n == L --, and a last sweep stores the first n values.  A group of C channels costs C
+ *                       forward transforms and one inverse.
+ * On every route scaling the input, or every weight, by a power of two scales the output exactly while nothing over- or underflows.
+ * Option "fusion" (fourier_hip_delay_set_option_*): 1 = the one-launch route where it exists, the DEFAULT (it took 0.26 - 0.42 of the
+ * composed route's time at every measured shape, DESIGN.md section 4, "Fractional delay"), 0 = the composed route.  The plan owns a scratch of at most 1 GiB (never less than one group) and walks larger
+ * batches in chunks of whole groups; the first call with a batch larger than any before allocates it unless
+ * fourier_hip_delay_reserve_* was called for at least that batch.  No atomics: the result is the same on repetition.  A NULL handle
+ * gives FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_delay_size_* / _length_* / _channels_* and "" from
+ * fourier_hip_delay_describe_*.  Handles are Send, not Sync, like the complex ones; status of the last call:
+ * fourier_hip_delay_last_status_*. */
+struct fourier_delay_float;
+struct fourier_delay_double;
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_delay_float *fourier_hip_delay_create_float(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE channels,
+                                                           int real_data, int device);
+struct fourier_delay_double *fourier_hip_delay_create_double(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length, FOURIER_SIZE_TYPE channels,
+                                                             int real_data, int device);
+/* NULL is a no-op. */
+void fourier_hip_delay_destroy_float(FOURIER_STRUCT fourier_delay_float *);
+void fourier_hip_delay_destroy_double(FOURIER_STRUCT fourier_delay_double *);
+/* n, L and C; 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_delay_size_float(const FOURIER_STRUCT fourier_delay_float *);
+FOURIER_SIZE_TYPE fourier_hip_delay_size_double(const FOURIER_STRUCT fourier_delay_double *);
+FOURIER_SIZE_TYPE fourier_hip_delay_length_float(const FOURIER_STRUCT fourier_delay_float *);
+FOURIER_SIZE_TYPE fourier_hip_delay_length_double(const FOURIER_STRUCT fourier_delay_double *);
+FOURIER_SIZE_TYPE fourier_hip_delay_channels_float(const FOURIER_STRUCT fourier_delay_float *);
+FOURIER_SIZE_TYPE fourier_hip_delay_channels_double(const FOURIER_STRUCT fourier_delay_double *);
+/* `batch` input rows, `batch` delays, `batch` weights or NULL -> batch / C output rows. */
+int fourier_hip_delay_apply_float(const FOURIER_STRUCT fourier_delay_float *, const void *d_in, const void *d_delays,
+                                  const void *d_weights, void *d_out, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_delay_apply_double(const FOURIER_STRUCT fourier_delay_double *, const void *d_in, const void *d_delays,
+                                   const void *d_weights, void *d_out, FOURIER_SIZE_TYPE batch, void *stream);
+int fourier_hip_delay_reserve_float(const FOURIER_STRUCT fourier_delay_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_delay_reserve_double(const FOURIER_STRUCT fourier_delay_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 / 1.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_delay_set_option_float(FOURIER_STRUCT fourier_delay_float *, const char *key, long long value);
+int fourier_hip_delay_set_option_double(FOURIER_STRUCT fourier_delay_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_delay_describe_float(const FOURIER_STRUCT fourier_delay_float *);
+const char *fourier_hip_delay_describe_double(const FOURIER_STRUCT fourier_delay_double *);
+int fourier_hip_delay_last_status_float(const FOURIER_STRUCT fourier_delay_float *);
+int fourier_hip_delay_last_status_double(const FOURIER_STRUCT fourier_delay_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -1950,6 +2021,48 @@ template <typename T> struct xcorr;
 FOURIER_DEFINE_CXX_XCORR_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_XCORR_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_XCORR_WRAPPER
+
+/* fractional delay and delay-and-sum on device memory (extension): fourier::delay<float> / <double> */
+template <typename T> struct delay;
+
+#define FOURIER_DEFINE_CXX_DELAY_WRAPPER(T, SUFFIX)                                                \
+  template <> struct delay<T> {                                                                    \
+    delay(std::size_t size, std::size_t length, std::size_t channels = 1, bool real_data = true,   \
+          int device = -1)                                                                         \
+        : impl(::fourier::c::fourier_hip_delay_create_##SUFFIX(size, length, channels,             \
+                                                               real_data ? 1 : 0, device),        \
+               ::fourier::c::fourier_hip_delay_destroy_##SUFFIX) {}                                \
+    delay() = delete;                                                                              \
+    delay(const delay &) = delete;                                                                 \
+    delay(delay &&) = default;                                                                     \
+    delay &operator=(const delay &) = delete;                                                      \
+    delay &operator=(delay &&) = default;                                                          \
+    ~delay() = default;                                                                            \
+    std::size_t size() const { return ::fourier::c::fourier_hip_delay_size_##SUFFIX(impl.get()); } \
+    std::size_t length() const { return ::fourier::c::fourier_hip_delay_length_##SUFFIX(impl.get()); }\
+    std::size_t channels() const { return ::fourier::c::fourier_hip_delay_channels_##SUFFIX(impl.get()); }\
+    /* `batch` rows of n values, `batch` delays, `batch` weights or nullptr -> batch / channels rows */\
+    int apply_device(const void *d_in, const void *d_delays, const void *d_weights, void *d_out,   \
+                     std::size_t batch, void *stream = nullptr) const {                            \
+      return ::fourier::c::fourier_hip_delay_apply_##SUFFIX(impl.get(), d_in, d_delays, d_weights, d_out, batch, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_delay_reserve_##SUFFIX(impl.get(), batch);                  \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_delay_set_option_##SUFFIX(impl.get(), key, value);          \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_delay_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_delay_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_delay_##SUFFIX,                                        \
+                      void (*)(::fourier::c::fourier_delay_##SUFFIX *)> impl;                      \
+  };
+FOURIER_DEFINE_CXX_DELAY_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_DELAY_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_DELAY_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
