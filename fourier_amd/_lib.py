@@ -111,6 +111,11 @@ _DELAY = ("fourier_hip_delay_", {  # fractional delay and delay-and-sum of real 
     "destroy": (None, [vp]), "size": (sz, [vp]), "length": (sz, [vp]), "channels": (sz, [vp]),
     "apply": (ci, [vp, vp, vp, vp, vp, sz, vp]),  # handle, d_in, d_delays, d_weights (may be NULL), d_out, batch, stream
     "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_CEPSTRUM = ("fourier_hip_cepstrum_", {  # real cepstrum (mode 0) and minimum-phase reconstruction (mode 1) of real rows
+    "create": (vp, [sz, sz, sz, ci, ci]),  # size, length, outputs, mode, device
+    "destroy": (None, [vp]), "size": (sz, [vp]), "length": (sz, [vp]), "outputs": (sz, [vp]), "mode": (ci, [vp]),
+    "apply": (ci, [vp, vp, vp, sz, ctypes.c_double, ctypes.c_double, vp]),  # handle, d_in, d_out, batch, log_mult, log_floor, stream
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -140,8 +145,9 @@ IPFB_SYMBOLS = list(_signatures(_IPFB))
 RESAMPLE_SYMBOLS = list(_signatures(_RESAMPLE))
 XCORR_SYMBOLS = list(_signatures(_XCORR))
 DELAY_SYMBOLS = list(_signatures(_DELAY))
+CEPSTRUM_SYMBOLS = list(_signatures(_CEPSTRUM))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS + CEPSTRUM_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -151,7 +157,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -30,6 +30,7 @@
 #include "resample_plan.h"
 #include "xcorr_plan.h"
 #include "delay_plan.h"
+#include "cepstrum_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -715,6 +716,37 @@ FOURIER_DEFINE_XCORR_ABI(double, double)
 
 FOURIER_DEFINE_DELAY_ABI(float, float)
 FOURIER_DEFINE_DELAY_ABI(double, double)
+
+// real cepstrum and minimum-phase reconstruction (fourier_hip_cepstrum_*)
+#define FOURIER_DEFINE_CEPSTRUM_ABI(T, SUFFIX)                                                                   \
+  FOURIER_DEFINE_HANDLE_ABI(cepstrum, fourier_cepstrum_##SUFFIX, CepstrumPlan<T>, SUFFIX)                        \
+  extern "C" fc::fourier_cepstrum_##SUFFIX* fourier_hip_cepstrum_create_##SUFFIX(size_t size, size_t length, size_t outputs, int mode, \
+                                                                                 int device) {                  \
+    return (fc::fourier_cepstrum_##SUFFIX*)create_handle<CepstrumPlan<T>>(size, length, outputs, mode, device);  \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_cepstrum_size_##SUFFIX(const fc::fourier_cepstrum_##SUFFIX* h) {                 \
+    return h ? ((const CepstrumPlan<T>*)h)->size() : 0;                                                          \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_cepstrum_length_##SUFFIX(const fc::fourier_cepstrum_##SUFFIX* h) {               \
+    return h ? ((const CepstrumPlan<T>*)h)->length() : 0;                                                        \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_cepstrum_outputs_##SUFFIX(const fc::fourier_cepstrum_##SUFFIX* h) {              \
+    return h ? ((const CepstrumPlan<T>*)h)->outputs() : 0;                                                       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_cepstrum_mode_##SUFFIX(const fc::fourier_cepstrum_##SUFFIX* h) {                    \
+    return h ? ((const CepstrumPlan<T>*)h)->mode() : -1;                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_cepstrum_apply_##SUFFIX(const fc::fourier_cepstrum_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                     size_t batch, double log_mult, double log_floor, void* stream) { \
+    const CepstrumPlan<T>* p = (const CepstrumPlan<T>*)h;                                                        \
+    return guarded_handle(p, [&] { p->apply(d_in, d_out, batch, log_mult, log_floor, (hipStream_t)stream); });   \
+  }                                                                                                              \
+  extern "C" int fourier_hip_cepstrum_set_option_##SUFFIX(fc::fourier_cepstrum_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<CepstrumPlan<T>>(h, key, v);                                                        \
+  }
+
+FOURIER_DEFINE_CEPSTRUM_ABI(float, float)
+FOURIER_DEFINE_CEPSTRUM_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

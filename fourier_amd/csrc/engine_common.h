@@ -206,6 +206,7 @@ typedef void (*CztKernel)(CztArgs);
 typedef void (*ResampleKernel)(ResampleArgs);
 typedef void (*XcorrKernel)(XcorrArgs);
 typedef void (*DelayKernel)(DelayArgs);
+typedef void (*CepstrumKernel)(CepstrumArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -335,6 +336,11 @@ template <typename T> struct Real {};
   /* delay_mul_kernel on half spectra (real_data) or whole spectra                                                       */ \
   bool get_delay_small_kernel(Real<T>, int k, KernelInfo& info);                                                       \
   DelayKernel get_delay_kernel(Real<T>, bool real_data);                                                               \
+  /* kernels_cepstrum.cpp: the cepstrum (minphase: the minimum-phase row) of real rows in one launch on the shapes of the */ \
+  /* two-level plans (cepstrum_small_kernel), where it spills no more than the envelope kernel of the same shape; the     */ \
+  /* composed route's sweeps, which = CEPSTRUM_LOG ... CEPSTRUM_EXP                                                       */ \
+  bool get_cepstrum_small_kernel(Real<T>, int k, bool minphase, KernelInfo& info);                                     \
+  CepstrumKernel get_cepstrum_kernel(Real<T>, int which);                                                              \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \
@@ -364,6 +370,8 @@ template <typename T> struct Real {};
   bool get_fused_kernel(Real<T>, int k, FusedInfo& info);                                                              \
   /* ... every instance of xcorr_small_kernel, those with scratch memory included (product: none) */                   \
   bool get_xcorr_spilling_kernel(Real<T>, int k, bool phat, KernelInfo& info);                                         \
+  /* ... every instance of cepstrum_small_kernel, those left out of the product included (product: none) */            \
+  bool get_cepstrum_spilling_kernel(Real<T>, int k, bool minphase, KernelInfo& info);                                  \
   KernelInfo get_split_kernel(Real<T>, int L, int io);                                                                 \
   /* persistent LAST pass that prefetches its next tile (fft_last_prefetch_kernel); fn == nullptr where not built */     \
   KernelInfo get_prefetch_kernel(Real<T>, int L, int io);                                                               \

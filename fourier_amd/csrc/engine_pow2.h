@@ -318,6 +318,36 @@ template <typename T> class Pow2Engine {
     launch(nullptr, 0, delay_small_.fn, batch, delay_small_.NT, delay_small_.smem, stream, a);
   }
 
+  // The cepstrum (mode 0) or the minimum-phase row (mode 1) of real rows in one launch (cepstrum_small_kernel; the cepstrum handle):
+  // conv_small_kernel's shapes and tables, where kernels_cepstrum.cpp holds an instance of the length and the mode (the development
+  // switch FOURIER_CEPSTRUM_SPILLING, read here, takes every instance from the experiments library instead).
+  bool enable_cepstrum_small(int mode) {
+    if (tiny_ || passes_.size() != 1 || passes_[0]->mode != MODE_TWOLEVEL) return false;
+    if (cepstrum_small_[mode].fn) return true;
+    KernelInfo k;
+    const bool spilling = dev_env("FOURIER_CEPSTRUM_SPILLING") != nullptr;
+    if (!(spilling ? get_cepstrum_spilling_kernel(Real<T>{}, ilog2(n_), mode != 0, k) : get_cepstrum_small_kernel(Real<T>{}, ilog2(n_), mode != 0, k))) return false;
+    if (!passes_[0]->tw_hi.p) passes_[0]->tw_hi.upload(product_table<T>(n_, tl2_, tl1_));  // (as enable_conv_small)
+    set_smem_attribute(k);
+    cepstrum_small_[mode] = k;
+    return true;
+  }
+  // in: `batch` rows of n <= n_ reals; out: rows of m <= n_ reals, in == out allowed where m == n; floor2 = log_floor^2 in T
+  void run_cepstrum_small(const void* in, void* out, size_t batch, uint32_t n, uint32_t m, int mode, double log_mult, double floor2,
+                          hipStream_t stream, unsigned nxcd) const {
+    if (batch == 0) return;
+    const Pass& ps = *passes_[0];
+    PassArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = in; a.out = out;
+    a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
+    a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
+    a.cp_n = n; a.cp_m = m; a.cp_log_mult = log_mult; a.cp_floor2 = floor2;
+    a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
+    const KernelInfo& k = cepstrum_small_[mode];
+    launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);
+  }
+
   // The cross-correlation of two real rows in one launch (xcorr_small_kernel; the cross-correlation handle): conv_small_kernel's shapes
   // and tables; one kernel for each weighting, and only where it runs without scratch memory (kernels_xcorr.cpp; the development
   // switch FOURIER_XCORR_SPILLING, read here, takes every instance from the experiments library instead).  Returns the weightings that have one: bit 0 none, bit 1 PHAT.
@@ -805,6 +835,7 @@ template <typename T> class Pow2Engine {
   KernelInfo hilbert_small_[2];  // the analytic signal, the envelope
   KernelInfo xcorr_small_[2];    // no weighting, PHAT
   KernelInfo delay_small_;       // the fractional delay of real rows
+  KernelInfo cepstrum_small_[2]; // the cepstrum, the minimum-phase row
   KernelInfo czt_small_[2];      // complex input rows, real input rows
   StageTables<T>* conv_st_ = nullptr;
   std::tuple<StftRowsKernel, MdctRowsKernel, SpectrogramRowsKernel, CsdRowsKernel, PfbRowsKernel, BandSpecRowsKernel> frame_rows_;

@@ -22,5 +22,8 @@ KernelInfo get_skeleton_kernel(Real<double>, int, int) { return KernelInfo(); }
 // the cross-correlation kernel's instances that need scratch memory ("Cross-correlation")
 bool get_xcorr_spilling_kernel(Real<float>, int, bool, KernelInfo&) { return false; }
 bool get_xcorr_spilling_kernel(Real<double>, int, bool, KernelInfo&) { return false; }
+// the cepstrum kernel's instances that spill more than the envelope kernel of their shape ("Cepstrum and minimum phase")
+bool get_cepstrum_spilling_kernel(Real<float>, int, bool, KernelInfo&) { return false; }
+bool get_cepstrum_spilling_kernel(Real<double>, int, bool, KernelInfo&) { return false; }
 
 }  // namespace fourier_hip

@@ -81,6 +81,10 @@ struct PassArgs {
   const void* dl_delays;
   const void* dl_weights;
   uint32_t dl_n;
+  // cepstrum_small_kernel (CepstrumPlan, cepstrum_plan.h): rows of cp_n reals in, rows of cp_m reals out;
+  // g = 0.5 cp_log_mult ln(max(|X|^2, cp_floor2)), cp_floor2 = log_floor^2 computed in T
+  uint32_t cp_n, cp_m;
+  double cp_log_mult, cp_floor2;
 };
 
 
@@ -507,6 +511,22 @@ struct DelayArgs {
   uint32_t len_m, len_l;      // the same for x / l, used where l <= 65536 (the exponent k * d_int fits 32 bits)
   uint32_t in_bytes, out_bytes;  // descriptor ranges of this launch
   double scale;               // the inverse's 1 / l, computed in T
+};
+
+// ---- cepstrum and minimum phase (kernels_cepstrum.h; CepstrumPlan, cepstrum_plan.h): the composed route's three sweeps, all in place,
+// one lane per value over a flat index; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES per launch).
+// cepstrum_log_kernel: `total` half-spectrum values X -> {0.5 log_mult ln(max(|X|^2, floor2)) * scale, 0}.
+// cepstrum_fold_kernel: rows of l reals c -> chat: weight 1 at 0 and (even l) at l / 2, 2 below l / 2, 0 above.
+// cepstrum_exp_kernel: `total` half-spectrum values C -> exp(Re C) (cos Im C, sin Im C) * scale.
+enum { CEPSTRUM_LOG = 0, CEPSTRUM_FOLD = 1, CEPSTRUM_EXP = 2 };
+struct CepstrumArgs {
+  void* data;
+  uint32_t l;                 // fold: values per row
+  uint32_t total;             // values of this launch
+  uint32_t div_m, div_l;      // fold: idx / l = (umulhi(idx, div_m) + idx) >> div_l
+  uint32_t bytes;             // descriptor range of this launch
+  double log_mult, floor2;    // log: log_floor^2, computed in T
+  double scale;               // log, exp: the inverse's 1 / l, computed in T
 };
 
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c

@@ -3,6 +3,7 @@
 #include "engine_common.h"
 #include "kernels_experiments.h"
 #include "kernels_xcorr.h"
+#include "kernels_cepstrum.h"
 #include "tile_shapes.h"
 
 namespace fourier_hip {
@@ -77,6 +78,13 @@ KernelInfo get_prefetch_kernel(Real<TUReal>, int L, int io) {
 // kernels_xcorr.cpp, holds the others only); selected by the development switch FOURIER_XCORR_SPILLING (engine_pow2.h)
 bool get_xcorr_spilling_kernel(Real<TUReal>, int k, bool phat, KernelInfo& info) {
   return phat ? xcorr_small_by_length<TUReal, true>(k, info) : xcorr_small_by_length<TUReal, false>(k, info);
+}
+
+// every instance of the cepstrum handle's one-launch kernel, those that spill more than the envelope kernel of their shape included
+// (the product's table, kernels_cepstrum.cpp, holds the others only); selected by the development switch FOURIER_CEPSTRUM_SPILLING
+// (engine_pow2.h)
+bool get_cepstrum_spilling_kernel(Real<TUReal>, int k, bool minphase, KernelInfo& info) {
+  return minphase ? cepstrum_small_by_length<TUReal, true>(k, info) : cepstrum_small_by_length<TUReal, false>(k, info);
 }
 
 }  // namespace fourier_hip

@@ -1825,6 +1825,130 @@ def delay_and_sum(x, delays, weights=None, length=None, out=None):
     return _delay_rows(x, shape[:-1], delays, weights, length, shape[-2], out, shape[:-2] + shape[-1:])
 
 
+class Cepstrum(_Handle):
+    """Batched real cepstrum and minimum-phase reconstruction (include/fourier.h, fourier_hip_cepstrum_*) on device memory: rows of n
+    reals, zero-extended to the transform length `length` = L >= n.  With X = fft(x, L) and the per-call reals log_mult != 0 and
+    log_floor >= 0, g = log_mult ln(max(|X|, log_floor)) (the accurate logarithm) and
+        mode 0 (Cepstrum.CEPSTRUM)       out = ifft(g)[:outputs]
+        mode 1 (Cepstrum.MINIMUM_PHASE)  c = ifft(g) folded onto the quefrencies 0 ... L/2 (weights 1, 2 ... 2, 1 at even L), C = fft(.),
+                                         out = Re ifft(exp(C))[:outputs]
+    Mode 1 with log_mult = 1 is scipy.signal.minimum_phase(x, method="homomorphic", n_fft=L, half=False), with log_mult = 0.5 its
+    half=True, up to two documented deviations: the floor is log_floor applied with max (scipy adds 1e-7 x the smallest positive |X|)
+    and at even L quefrency L/2 keeps weight 1 (scipy: 0).  log_floor = 0 on a bin that is exactly 0 makes that row's output not
+    finite and touches nothing else."""
+
+    _prefix = "fourier_hip_cepstrum_"
+    _destroy = "fourier_hip_cepstrum_destroy"
+    CEPSTRUM, MINIMUM_PHASE = 0, 1
+
+    def __init__(self, n, length, real="f32", outputs=None, mode=0, device=-1):
+        n, length = int(n), int(length)
+        outputs = n if outputs is None else int(outputs)
+        if not 1 <= n <= length:
+            raise ValueError(f"need 1 <= n <= length, got {n}, {length}")
+        if not 1 <= outputs <= length:
+            raise ValueError(f"need 1 <= outputs <= length, got {outputs}, {length}")
+        if mode not in (0, 1):
+            raise ValueError(f"mode is 0 (cepstrum) or 1 (minimum phase), got {mode}")
+        self._create(real, f"cepstrum plan of {n} values in {length}, {outputs} outputs, mode {mode}", n, length, outputs, int(mode), int(device))
+        self._n, self._l, self._m, self._mode = n, length, outputs, int(mode)
+
+    def size(self):
+        return self._n
+
+    def length(self):
+        return self._l
+
+    def outputs(self):
+        return self._m
+
+    def mode(self):
+        return self._mode
+
+    def set_option(self, key, value):
+        """"fusion": 1 (default) = the one-launch kernel where the library has one (length 2^11 ... 2^15, f64 ... 2^14; the f32
+        minimum-phase row at 2^11, 2^12 and 2^14 only), 0 = the composed route."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def apply_ptr(self, d_in, d_out, batch, log_mult=1.0, log_floor=0.0, stream=0):
+        """`batch` rows of n reals of the handle's type at d_in -> `batch` rows of outputs() reals at d_out (d_in allowed where
+        outputs() == n), enqueued on `stream`."""
+        self._call("apply", d_in, d_out, int(batch), float(log_mult), float(log_floor), stream)
+
+    def apply(self, x, log_mult=1.0, log_floor=0.0, out=None):
+        """A contiguous (..., n) CUDA float tensor of the handle's precision -> a new tensor of shape (..., outputs()), or `out` (which
+        may be `x` where outputs() == n), on the current stream."""
+        import torch
+
+        rdt = _torch_dtypes(self.real)[0]
+        _require_cuda(x, rdt)
+        if x.dim() == 0 or x.shape[-1] != self._n:
+            raise ValueError(f"last dimension must be {self._n}, got {tuple(x.shape)}")
+        batch = x.numel() // self._n
+        shape = tuple(x.shape[:-1]) + (self._m,)
+        if out is None:
+            out = torch.empty(shape, dtype=rdt, device=x.device)
+        else:
+            _require_out(out, shape, rdt, x.device)
+            a0, b0 = x.data_ptr(), out.data_ptr()
+            nin, nout = x.numel() * x.element_size(), out.numel() * out.element_size()
+            if (a0 != b0 or self._m != self._n) and a0 < b0 + nout and b0 < a0 + nin:
+                raise ValueError("input and output overlap")
+        if batch:
+            self.apply_ptr(x.data_ptr(), out.data_ptr(), batch, log_mult, log_floor, _stream(x))
+        return out
+
+
+def create_cepstrum_f32(n, length, outputs=None, mode=0, device=-1):
+    return Cepstrum(n, length, "f32", outputs, mode, device)
+
+
+def create_cepstrum_f64(n, length, outputs=None, mode=0, device=-1):
+    return Cepstrum(n, length, "f64", outputs, mode, device)
+
+
+def _cepstrum_rows(x, length, outputs, mode, log_mult, log_floor, out):
+    if not (_is_torch(x) and x.is_cuda and _precision(x.dtype) is not None and _precision(x.dtype)[1]):
+        raise TypeError("expected a CUDA float32 / float64 tensor")
+    if x.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    real = _precision(x.dtype)[0]
+    n = int(x.shape[-1])
+    if n < 1:
+        raise ValueError("the transformed dimension must have length >= 1")
+    length = n if length is None else int(length)
+    if length < n:
+        raise ValueError(f"need length >= n, got {length}, {n}")
+    outputs = n if outputs is None else int(outputs)
+    if not 1 <= outputs <= length:
+        raise ValueError(f"need 1 <= outputs <= length, got {outputs}, {length}")
+    shape = tuple(x.shape[:-1]) + (outputs,)
+    if out is not None and not (_is_torch(out) and out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == shape
+                                and out.device == x.device and out.is_contiguous()):
+        raise TypeError(f"out must be a contiguous CUDA {_names((x.dtype,))} tensor of shape {shape} on the input's device")
+    plan = _cached_plan(Cepstrum, n, length, real, outputs, mode, int(_device_index(x)))
+    return plan.apply(x.contiguous(), log_mult, log_floor, out)
+
+
+def real_cepstrum(x, length=None, outputs=None, log_floor=0.0, out=None):
+    """The real cepstrum irfft(log(max(|rfft(x, L)|, log_floor)))[..., :outputs] along the last axis of a CUDA float32 / float64 tensor
+    `x` of shape (..., n), on the current stream.  `length` = L >= n is the transform length (None: n), `outputs` <= L the number of
+    quefrencies kept (None: n).  log_floor = 0 on a bin that is exactly 0 makes that row not finite.  A non-contiguous `x` is copied.
+    Returns a new tensor or `out` (which may be `x` where outputs == n).  One cached Cepstrum handle per (n, length, outputs, dtype,
+    device)."""
+    return _cepstrum_rows(x, length, outputs, Cepstrum.CEPSTRUM, 1.0, log_floor, out)
+
+
+def minimum_phase(x, length=None, outputs=None, half=False, log_floor=0.0, out=None):
+    """The minimum-phase row with the magnitude response of each row (half=True: with the square root of it) along the last axis of a
+    CUDA float32 / float64 tensor `x` of shape (..., n), on the current stream: scipy.signal.minimum_phase(x, method="homomorphic",
+    n_fft=length, half=half) without its truncation to (n + 1) / 2 taps -- `outputs` values are kept (None: n) -- and with the two
+    documented deviations of the Cepstrum class (the floor is `log_floor` applied with max; at even length quefrency length / 2 keeps
+    weight 1).  `length` >= n (None: n); choose it several times n, as scipy's default n_fft does, for an accurate result.  Returns a
+    new tensor or `out` (which may be `x` where outputs == n).  One cached Cepstrum handle per (n, length, outputs, dtype, device)."""
+    return _cepstrum_rows(x, length, outputs, Cepstrum.MINIMUM_PHASE, 0.5 if half else 1.0, log_floor, out)
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

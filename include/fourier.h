@@ -1514,6 +1514,86 @@ const char *fourier_hip_delay_describe_double(const FOURIER_STRUCT fourier_delay
 int fourier_hip_delay_last_status_float(const FOURIER_STRUCT fourier_delay_float *);
 int fourier_hip_delay_last_status_double(const FOURIER_STRUCT fourier_delay_double *);
 
+/* ---------------- real cepstrum and minimum-phase reconstruction (extension; the reference has none) ----------
+ * `batch` rows x[r] of n = `size` REALS T on DEVICE memory, row r at element offset r*n, zero-extended to the transform length
+ * L = `length` >= n.  With X = fft(x~, L) and the per-call reals log_mult != 0 and log_floor >= 0:
+ *   g[k] = log_mult ln(max(|X[k]|, log_floor)),
+ * formed as 0.5 log_mult ln(max(re^2 + im^2, log_floor^2)) with the accurate logarithm, never the fast hardware one.
+ *   mode 0, CEPSTRUM:       c = ifft(g), which is real and even;  out[r][q] = c[q], q = 0 .. m-1, m = `outputs` <= L
+ *                           (log_mult = 1: the real cepstrum irfft(log|rfft(x)|)).
+ *   mode 1, MINIMUM_PHASE:  the fold chat[0] = c[0]; chat[q] = 2 c[q] for 0 < q < L/2 (odd L: q <= (L-1)/2); chat[L/2] = c[L/2]
+ *                           (even L); chat[q] = 0 above.  C = fft(chat), E[k] = exp(Re C[k]) (cos Im C[k], sin Im C[k]),
+ *                           h = Re ifft(E);  out[r][t] = h[t], t = 0 .. m-1.  log_mult = 1 is
+ *                           scipy.signal.minimum_phase(x, method="homomorphic", n_fft=L, half=False), log_mult = 0.5 its half=True.
+ * Two deviations from scipy 1.15.3.  The FLOOR: scipy adds 1e-7 x the smallest positive |X| to |X|, a reduction over the data; here
+ * the floor is the caller's log_floor, applied with max.  The FOLD AT EVEN L: scipy's window leaves quefrency L/2 at weight 0; here
+ * it keeps weight 1 (Oppenheim and Schafer, eq. 13.42b).  On firwin(101, 0.3) at L = 2048 and 8192 the two definitions agree to
+ * 2.3e-7 and 1.8e-7 relative in f64.
+ * log_floor == 0 on a bin that is exactly 0 gives -inf there: that row's output is not finite, nothing else is touched, and it is
+ * not an error.  No value of a row enters an address.  A NaN in a row makes that row's output NaN.
+ * Amplitude range: re^2 + im^2 must neither overflow nor flush to zero in T, so sqrt(min normal) < |X[k]| < sqrt(max):
+ * 1.1e-19 .. 1.8e19 in float, 1.5e-154 .. 1.3e154 in double (a bin below the range counts as 0: the floor, or -inf).  Scaling x by
+ * 2^j moves c[0] by j log_mult ln 2 and h by 2^(j log_mult): bit-exact power-of-two scaling is NOT claimed for this family.
+ * The phase of E goes through one accurate sincospi of Im C / pi, the exponential is the accurate one.
+ * n == 0, n > L, m == 0, m > L, a mode other than 0 / 1 make create fail; so does L * 2 * sizeof(T) > 2^31 - 1 (as
+ * fourier_hip_hilbert_create_*).  log_mult == 0, a log_mult or log_floor that is not finite, log_floor < 0, a NULL buffer, a buffer not
+ * aligned to sizeof(T), and an overlap of input and output other than d_out == d_in with m == n give FOURIER_HIP_INVALID_ARGUMENT.
+ * batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Routes (fourier_hip_cepstrum_describe_* begins with the route's name):
+ *   "cepstrum one-launch"  L = 2^11 ... 2^15 (double: ... 2^14) where the library holds a kernel of the mode: load, FFT, logarithm,
+ *                          inverse FFT -- and for mode 1 the fold, FFT, complex exponential and inverse FFT -- and the store of the
+ *                          first m values in ONE launch on register-resident data; no scratch.
+ *   "cepstrum composed"    every L (odd and Bluestein lengths included): the rows are padded to L, transformed to half spectra, ONE
+ *                          sweep forms g / L in place, an unscaled inverse follows; mode 1 goes on with a fold sweep, a forward
+ *                          transform, a sweep that forms E / L and an unscaled inverse; the last inverse writes straight into the
+ *                          caller's output where m == L, else a last sweep stores the first m values.
+ * Option "fusion" (fourier_hip_cepstrum_set_option_*): 1 = the one-launch route where it exists, the DEFAULT (it took 0.26 - 0.53 of
+ * the composed route's time at every measured shape, DESIGN.md section 4, "Cepstrum and minimum phase"), 0 = the composed route.
+ * The plan owns a scratch of at most 1 GiB (never less than one row)
+ * and walks larger batches in chunks of whole rows; the first call with a batch larger than any before allocates it unless
+ * fourier_hip_cepstrum_reserve_* was called for at least that batch.  No atomics: the result is the same on repetition.  A NULL
+ * handle gives FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_cepstrum_size_* / _length_* / _outputs_*, -1 from
+ * fourier_hip_cepstrum_mode_* and "" from fourier_hip_cepstrum_describe_*.  Handles are Send, not Sync, like the complex ones; status
+ * of the last call: fourier_hip_cepstrum_last_status_*. */
+struct fourier_cepstrum_float;
+struct fourier_cepstrum_double;
+
+#define FOURIER_CEPSTRUM_MODE_CEPSTRUM 0
+#define FOURIER_CEPSTRUM_MODE_MINIMUM_PHASE 1
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_cepstrum_float *fourier_hip_cepstrum_create_float(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length,
+                                                                 FOURIER_SIZE_TYPE outputs, int mode, int device);
+struct fourier_cepstrum_double *fourier_hip_cepstrum_create_double(FOURIER_SIZE_TYPE size, FOURIER_SIZE_TYPE length,
+                                                                   FOURIER_SIZE_TYPE outputs, int mode, int device);
+/* NULL is a no-op. */
+void fourier_hip_cepstrum_destroy_float(FOURIER_STRUCT fourier_cepstrum_float *);
+void fourier_hip_cepstrum_destroy_double(FOURIER_STRUCT fourier_cepstrum_double *);
+/* n, L and m; 0 for a NULL handle.  The mode; -1 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_size_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_size_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_length_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_length_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_outputs_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+FOURIER_SIZE_TYPE fourier_hip_cepstrum_outputs_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+int fourier_hip_cepstrum_mode_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+int fourier_hip_cepstrum_mode_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+/* `batch` rows of n reals -> `batch` rows of m reals. */
+int fourier_hip_cepstrum_apply_float(const FOURIER_STRUCT fourier_cepstrum_float *, const void *d_in, void *d_out,
+                                     FOURIER_SIZE_TYPE batch, double log_mult, double log_floor, void *stream);
+int fourier_hip_cepstrum_apply_double(const FOURIER_STRUCT fourier_cepstrum_double *, const void *d_in, void *d_out,
+                                      FOURIER_SIZE_TYPE batch, double log_mult, double log_floor, void *stream);
+int fourier_hip_cepstrum_reserve_float(const FOURIER_STRUCT fourier_cepstrum_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_cepstrum_reserve_double(const FOURIER_STRUCT fourier_cepstrum_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 0 / 1.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_cepstrum_set_option_float(FOURIER_STRUCT fourier_cepstrum_float *, const char *key, long long value);
+int fourier_hip_cepstrum_set_option_double(FOURIER_STRUCT fourier_cepstrum_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_cepstrum_describe_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+const char *fourier_hip_cepstrum_describe_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+int fourier_hip_cepstrum_last_status_float(const FOURIER_STRUCT fourier_cepstrum_float *);
+int fourier_hip_cepstrum_last_status_double(const FOURIER_STRUCT fourier_cepstrum_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -2063,6 +2143,48 @@ template <typename T> struct delay;
 FOURIER_DEFINE_CXX_DELAY_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_DELAY_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_DELAY_WRAPPER
+
+/* real cepstrum (mode 0) and minimum-phase reconstruction (mode 1) on device memory (extension): fourier::cepstrum<float> / <double> */
+template <typename T> struct cepstrum;
+
+#define FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER(T, SUFFIX)                                             \
+  template <> struct cepstrum<T> {                                                                 \
+    cepstrum(std::size_t size, std::size_t length, std::size_t outputs, int mode = 0,              \
+             int device = -1)                                                                      \
+        : impl(::fourier::c::fourier_hip_cepstrum_create_##SUFFIX(size, length, outputs, mode, device),\
+               ::fourier::c::fourier_hip_cepstrum_destroy_##SUFFIX) {}                             \
+    cepstrum() = delete;                                                                           \
+    cepstrum(const cepstrum &) = delete;                                                           \
+    cepstrum(cepstrum &&) = default;                                                               \
+    cepstrum &operator=(const cepstrum &) = delete;                                                \
+    cepstrum &operator=(cepstrum &&) = default;                                                    \
+    ~cepstrum() = default;                                                                         \
+    std::size_t size() const { return ::fourier::c::fourier_hip_cepstrum_size_##SUFFIX(impl.get()); }\
+    std::size_t length() const { return ::fourier::c::fourier_hip_cepstrum_length_##SUFFIX(impl.get()); }\
+    std::size_t outputs() const { return ::fourier::c::fourier_hip_cepstrum_outputs_##SUFFIX(impl.get()); }\
+    int mode() const { return ::fourier::c::fourier_hip_cepstrum_mode_##SUFFIX(impl.get()); }      \
+    /* `batch` rows of size() reals -> `batch` rows of outputs() reals */                          \
+    int apply_device(const void *d_in, void *d_out, std::size_t batch, double log_mult = 1.0,      \
+                     double log_floor = 0.0, void *stream = nullptr) const {                       \
+      return ::fourier::c::fourier_hip_cepstrum_apply_##SUFFIX(impl.get(), d_in, d_out, batch, log_mult, log_floor, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_cepstrum_reserve_##SUFFIX(impl.get(), batch);               \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_cepstrum_set_option_##SUFFIX(impl.get(), key, value);       \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_cepstrum_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_cepstrum_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_cepstrum_##SUFFIX,                                     \
+                      void (*)(::fourier::c::fourier_cepstrum_##SUFFIX *)> impl;                   \
+  };
+FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
