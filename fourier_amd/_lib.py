@@ -36,6 +36,13 @@ _CONV = ("fourier_hip_conv_", {  # convolution with a prepared filter bank
     "create": (vp, [sz, ci, ci]), "destroy": (None, [vp]), "size": (sz, [vp]), "filters": (sz, [vp]),
     "set_filters": (ci, [vp, vp, sz, sz, ci, vp]), "apply": (ci, [vp, vp, vp, sz, vp]), "reserve": (ci, [vp, sz]),
     "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_CONVND = ("fourier_hip_convnd_", {  # N-D convolution of real items with a prepared filter bank
+    "create": (vp, [ci, ctypes.POINTER(sz), ci]), "destroy": (None, [vp]), "rank": (ci, [vp]), "shape": (ci, [vp, ctypes.POINTER(sz)]),
+    "filters": (sz, [vp]),
+    "set_filters": (ci, [vp, vp, ctypes.POINTER(sz), sz, ci, vp]),  # handle, d_taps, taps_shape, filters, correlate, stream
+    "set_window": (ci, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),  # handle, in_shape, out_first, out_shape
+    "apply_batch": (ci, [vp, vp, vp, sz, sz, vp]),  # handle, d_in, d_out, batch, filter_first, stream
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _LCONV = ("fourier_hip_lconv_", {  # linear convolution (full / same / valid) with a prepared filter bank
     "create": (vp, [sz, sz, ci, ci, ci]), "destroy": (None, [vp]), "length": (sz, [vp]), "taps": (sz, [vp]), "out_length": (sz, [vp]),
     "filters": (sz, [vp]), "set_filters": (ci, [vp, vp, sz, ci, vp]), "apply": (ci, [vp, vp, vp, sz, vp]), "reserve": (ci, [vp, sz]),
@@ -146,8 +153,9 @@ RESAMPLE_SYMBOLS = list(_signatures(_RESAMPLE))
 XCORR_SYMBOLS = list(_signatures(_XCORR))
 DELAY_SYMBOLS = list(_signatures(_DELAY))
 CEPSTRUM_SYMBOLS = list(_signatures(_CEPSTRUM))
+CONVND_SYMBOLS = list(_signatures(_CONVND))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS + CEPSTRUM_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS + CEPSTRUM_SYMBOLS + CONVND_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -157,7 +165,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM, _CONVND):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -56,7 +56,7 @@ def mix_shards(name="MIX"):
 
 def translation_units():
     """(object name, source file, extra -D flags, group) for every object of the two libraries.  Groups: 'host', 'env_product',
-    'env_experiments', 'pass', 'onelaunch', 'misc', 'real', 'r2r', 'stft', 'mdct', 'spectrogram', 'csd', 'bandspec', 'conv', 'hilbert', 'czt', 'pfb', 'resample', 'xcorr', 'delay', 'cepstrum', 'axis', 'mixed', 'chirpz', 'experiments' (tools/build_variants.py rebuilds by group)."""
+    'env_experiments', 'pass', 'onelaunch', 'misc', 'real', 'r2r', 'stft', 'mdct', 'spectrogram', 'csd', 'bandspec', 'conv', 'convnd', 'hilbert', 'czt', 'pfb', 'resample', 'xcorr', 'delay', 'cepstrum', 'axis', 'mixed', 'chirpz', 'experiments' (tools/build_variants.py rebuilds by group)."""
     tus = [("engine", "engine.cpp", [], "host"),
            ("rtc", "rtc.cpp", [], "host"),
            ("env_product", "env_product.cpp", [], "env_product"),
@@ -82,6 +82,7 @@ def translation_units():
         tus.append((f"kernels_csd_{tag}", "kernels_csd.cpp", d, "csd"))
         tus.append((f"kernels_bandspec_{tag}", "kernels_bandspec.cpp", d, "bandspec"))
         tus.append((f"kernels_conv_{tag}", "kernels_conv.cpp", d, "conv"))
+        tus.append((f"kernels_convnd_{tag}", "kernels_convnd.cpp", d, "convnd"))
         tus.append((f"kernels_hilbert_{tag}", "kernels_hilbert.cpp", d, "hilbert"))
         tus.append((f"kernels_czt_{tag}", "kernels_czt.cpp", d, "czt"))
         tus.append((f"kernels_pfb_{tag}", "kernels_pfb.cpp", d, "pfb"))

@@ -16,6 +16,7 @@
 #include "axis_plan.h"
 #include "realnd_plan.h"
 #include "conv_plan.h"
+#include "convnd_plan.h"
 #include "lconv_plan.h"
 #include "r2r_plan.h"
 #include "stft_plan.h"
@@ -218,6 +219,46 @@ FOURIER_DEFINE_REALND_ABI(double, double)
 
 FOURIER_DEFINE_CONV_ABI(float, float)
 FOURIER_DEFINE_CONV_ABI(double, double)
+
+// N-D convolution with a prepared filter bank (fourier_hip_convnd_*)
+#define FOURIER_DEFINE_CONVND_ABI(T, SUFFIX)                                                                     \
+  FOURIER_DEFINE_HANDLE_ABI(convnd, fourier_convnd_##SUFFIX, ConvNdPlan<T>, SUFFIX)                              \
+  extern "C" fc::fourier_convnd_##SUFFIX* fourier_hip_convnd_create_##SUFFIX(int rank, const size_t* shape, int device) { \
+    return (fc::fourier_convnd_##SUFFIX*)create_handle<ConvNdPlan<T>>(rank, shape, device);                      \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_rank_##SUFFIX(const fc::fourier_convnd_##SUFFIX* h) {                        \
+    return h ? ((const ConvNdPlan<T>*)h)->rank() : 0;                                                            \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_shape_##SUFFIX(const fc::fourier_convnd_##SUFFIX* h, size_t* out) {          \
+    if (!h || !out) return fc::FOURIER_HIP_INVALID_ARGUMENT;                                                     \
+    const std::vector<size_t>& s = ((const ConvNdPlan<T>*)h)->shape();                                           \
+    for (size_t d = 0; d < s.size(); ++d) out[d] = s[d];                                                         \
+    return fc::FOURIER_HIP_OK;                                                                                   \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_convnd_filters_##SUFFIX(const fc::fourier_convnd_##SUFFIX* h) {                  \
+    return h ? ((const ConvNdPlan<T>*)h)->filters() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_set_filters_##SUFFIX(fc::fourier_convnd_##SUFFIX* h, const void* d_taps, const size_t* taps_shape, \
+                                                         size_t filters, int correlate, void* stream) {          \
+    ConvNdPlan<T>* p = (ConvNdPlan<T>*)h;                                                                        \
+    return guarded_handle(p, [&] { p->set_filters(d_taps, taps_shape, filters, correlate != 0, (hipStream_t)stream); }); \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_set_window_##SUFFIX(fc::fourier_convnd_##SUFFIX* h, const size_t* in_shape,  \
+                                                        const size_t* out_first, const size_t* out_shape) {      \
+    ConvNdPlan<T>* p = (ConvNdPlan<T>*)h;                                                                        \
+    return guarded_handle(p, [&] { p->set_window(in_shape, out_first, out_shape); });                            \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_apply_batch_##SUFFIX(const fc::fourier_convnd_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                         size_t batch, size_t filter_first, void* stream) {      \
+    const ConvNdPlan<T>* p = (const ConvNdPlan<T>*)h;                                                            \
+    return guarded_handle(p, [&] { p->apply(d_in, d_out, batch, filter_first, (hipStream_t)stream); });          \
+  }                                                                                                              \
+  extern "C" int fourier_hip_convnd_set_option_##SUFFIX(fc::fourier_convnd_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<ConvNdPlan<T>>(h, key, v);                                                          \
+  }
+
+FOURIER_DEFINE_CONVND_ABI(float, float)
+FOURIER_DEFINE_CONVND_ABI(double, double)
 
 // linear convolution with a prepared filter bank (fourier_hip_lconv_*)
 #define FOURIER_DEFINE_LCONV_ABI(T, SUFFIX)                                                                      \

@@ -201,6 +201,7 @@ static inline StftArgs& frame_block(BandSpecArgs& a) { return a.f; }
 static inline PfbArgs& frame_block(PfbArgs& a) { return a; }
 typedef void (*AxisKernel)(AxisArgs);
 typedef void (*ConvKernel)(ConvArgs);
+typedef void (*ConvNdKernel)(ConvNdArgs);
 typedef void (*HilbertKernel)(HilbertArgs);
 typedef void (*CztKernel)(CztArgs);
 typedef void (*ResampleKernel)(ResampleArgs);
@@ -316,6 +317,8 @@ template <typename T> struct Real {};
   IpfbKernel get_ipfb_kernel(Real<T>);                                                                                 \
   /* kernels_conv.cpp: the sweeps of the convolution handle, which = CONV_MUL ... CONV_LTAPS (kernel_args.h) */             \
   ConvKernel get_conv_sweep_kernel(Real<T>, int which);                                                                \
+  /* kernels_convnd.cpp: the sweeps of the N-D convolution handle, which = CONVND_MID ... CONVND_MUL (kernel_args.h) */      \
+  ConvNdKernel get_convnd_kernel(Real<T>, int which);                                                                  \
   /* kernels_hilbert.cpp: the analytic signal or the envelope of real rows in one launch on the shapes of the two-level */ \
   /* plans of 2^11 ... 2^15 (hilbert_small_kernel); the sweeps of the composed route, which = HILBERT_EXPAND / HILBERT_ABS */ \
   bool get_hilbert_small_kernel(Real<T>, int k, bool envelope, KernelInfo& info);                                      \

@@ -367,6 +367,32 @@ struct ConvArgs {
   int widen, real;            // lconv taps: real taps -> complex rows; the values are reals (else complex)
 };
 
+// ---- N-D convolution with a filter bank (kernels_convnd.h; ConvNdPlan, convnd_plan.h)
+// realnd_conv_mid_kernel: the middle of the packed route, in place on Z (items of rows x h): the workgroups and rows of the N-D real
+// sweeps (`r`: in == out == Z, tw, h, lanes, segs, nd and the dividers as realnd_post_kernel reads them; scale unused), the bank H of
+// `filters` half spectra of rows x (h + 1), item b of this launch with filter (first + b) mod filters.  Row bases are 64-bit, offsets
+// within a row 32-bit.
+// convnd_pad_kernel / convnd_crop_kernel: window copies between items of lines of words T.  Destination line (i_a, i_b, i_c) of an
+// item of dl[0] x dl[1] x dl[2] lines of dw words (unused leading sizes 1), word k, is word offw + k of line (i_a + off[0], i_b +
+// off[1], i_c + off[2]) of the source item of sl[0] x sl[1] x sl[2] lines of sw words; the pad sweep stores zero where that lies
+// outside the source item, the crop sweep's windows lie inside it.  One workgroup per LCONV_SEG words of a destination line over a flat
+// index of lines x segs; line addresses are 64-bit.
+// convnd_mul_kernel (the composed route's product where an item is beyond conv_mul_kernel's 32-bit index): dst[b][r][k] *=
+// bank[(first + b) mod filters][r][k] over items of dlines rows of dw complex values, one workgroup per row and segment of 256 columns.
+enum { CONVND_MID = 0, CONVND_PAD = 1, CONVND_CROP = 2, CONVND_MUL = 3 };
+struct ConvNdArgs {
+  RealArgs r;                 // mid
+  const void* bank;
+  uint32_t filters, first;    // first < filters
+  uint32_t f_m, f_l;          // the divider for `filters`
+  const void* src; void* dst; // window copies
+  uint32_t dl[3], sl[3], off[3];
+  uint32_t dlines, slines;    // lines per destination and per source item
+  uint32_t segs;              // workgroups per destination line
+  uint32_t seg_m, seg_l, line_m, line_l, c_m, c_l, b_m, b_l;  // dividers by segs, dlines, dl[2], dl[1]
+  uint64_t dw, sw, offw;
+};
+
 // ---- analytic signal and envelope (kernels_hilbert.h; HilbertPlan, hilbert_plan.h): the sweeps of the composed route, one lane per
 // element over a flat index of rows x n; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES of the complex side per launch).
 // hilbert_expand_kernel: rows of h + 1 complex values X (a half spectrum) -> rows of n complex values X[k] m[k] * scale, m = 1 for

@@ -84,8 +84,7 @@ template <typename T> class RealNdPlan : public HandleBase {
     } else {
       rows1d_->reserve(chunk * rows_);
     }
-    for (size_t d = 0; d < axis_.size(); ++d)
-      if (axis_[d]) AxisRoute<T>::of(*axis_[d]).reserve(outer(d, chunk), inner(d, cols));
+    reserve_axes(chunk, cols);
     return chunk;
   }
   void reserve(size_t batch) const { (void)prepare(batch); }
@@ -138,6 +137,42 @@ template <typename T> class RealNdPlan : public HandleBase {
     });
   }
 
+  // ---- the stages of the packed route, for a handle that runs them around a sweep of its own on its own scratch (ConvNdPlan,
+  // convnd_plan.h); rank >= 2
+  bool packed() const { return packed_; }
+  int device() const { return device_; }
+  size_t rows() const { return rows_; }    // R = n_1 x ... x n_{r-1}
+  size_t width() const { return w_; }      // W
+  const std::vector<size_t>& shape() const { return shape_; }
+  const Plan<T>& row_plan() const { return *row_; }  // the h-point plan of the rows (packed)
+  // the axis routes' buffers for chunks of `chunk` items of rows x cols
+  void reserve_axes(size_t chunk, size_t cols) const {
+    for (size_t d = 0; d < axis_.size(); ++d)
+      if (axis_[d]) AxisRoute<T>::of(*axis_[d]).reserve(outer(d, chunk), inner(d, cols));
+  }
+  // one axis transform per leading dimension over nb items of rows x cols, in place
+  void axes_in_place(cpx<T>* z, size_t nb, size_t cols, int code, hipStream_t stream) const { axes(z, z, nb, cols, code, stream); }
+  // the row indexing of an N-D sweep (realnd_rows, kernels_real.h) and the untangle twiddles; returns the workgroup size
+  uint32_t sweep_geometry(RealArgs& a) const {
+    const uint32_t lanes = (uint32_t)((h_ + 1) / 2);
+    uint32_t threads = 64;
+    while (threads < lanes && threads < REAL_THREADS_H) threads *= 2;
+    const uint32_t segs = (lanes + threads - 1) / threads;
+    a.tw = tw_.p;
+    a.h = (uint32_t)h_;
+    a.nd_rows = (uint32_t)rows_;
+    a.lanes = lanes;
+    a.segs = segs;
+    const size_t lead = shape_.size() - 1;  // 1 ... 3 leading sizes, right-aligned into nd[0 .. 2]
+    for (int i = 0; i < 3; ++i) a.nd[i] = 1;
+    for (size_t d = 0; d < lead; ++d) a.nd[3 - lead + d] = (uint32_t)shape_[d];
+    divider(segs, a.seg_m, a.seg_l);
+    divider((uint32_t)rows_, a.row_m, a.row_l);
+    divider(a.nd[2], a.c_m, a.c_l);
+    divider(a.nd[1], a.b_m, a.b_l);
+    return threads;
+  }
+
  private:
   // one complex plan per distinct length
   const Plan<T>* plan_of(size_t n, int device) {
@@ -175,23 +210,8 @@ template <typename T> class RealNdPlan : public HandleBase {
 
   // the N-D sweep over nb items: one workgroup per row and segment of lanes, launches of whole items with fewer than 2^31 workgroups
   void sweep(int which, const cpx<T>* in, cpx<T>* out, size_t nb, double scale, hipStream_t stream) const {
-    const uint32_t lanes = (uint32_t)((h_ + 1) / 2);
-    uint32_t threads = 64;
-    while (threads < lanes && threads < REAL_THREADS_H) threads *= 2;
-    const uint32_t segs = (lanes + threads - 1) / threads;
     RealArgs a{};
-    a.tw = tw_.p;
-    a.h = (uint32_t)h_;
-    a.nd_rows = (uint32_t)rows_;
-    a.lanes = lanes;
-    a.segs = segs;
-    const size_t lead = shape_.size() - 1;  // 1 ... 3 leading sizes, right-aligned into nd[0 .. 2]
-    for (int i = 0; i < 3; ++i) a.nd[i] = 1;
-    for (size_t d = 0; d < lead; ++d) a.nd[3 - lead + d] = (uint32_t)shape_[d];
-    divider(segs, a.seg_m, a.seg_l);
-    divider((uint32_t)rows_, a.row_m, a.row_l);
-    divider(a.nd[2], a.c_m, a.c_l);
-    divider(a.nd[1], a.b_m, a.b_l);
+    const uint32_t threads = sweep_geometry(a), segs = a.segs;
     a.scale = scale;
     const bool post = which == REAL_ND_POST;
     const size_t zi = rows_ * h_, xi = rows_ * (h_ + 1);

@@ -12,6 +12,7 @@ library; arrays holding several transforms are streamed through the device in ch
 tensors go through the device-resident batched ABI on the current stream.
 All compute happens in libfourier.so (HIP); there is no CPU fallback.
 """
+import ctypes
 import enum
 
 import numpy as np
@@ -557,6 +558,210 @@ def fftconvolve(x, taps, mode="full", correlate=False, out=None):
     p = _cached_plan(LinearConv, int(x.shape[-1]), int(taps.shape[-1]), real, mode, real_data, int(_device_index(x)))
     p.set_filters(taps, correlate)
     return p.apply(x, out)
+
+
+class FftConvNd(_Handle):
+    """Batched N-D circular convolution / correlation of REAL items with a prepared filter bank (include/fourier.h,
+    fourier_hip_convnd_*) on device memory, over the trailing len(shape) = 2, 3 or 4 dimensions.  `shape` is the transform shape S:
+    items of in_shape <= S are zero-extended to S, convolved circularly with filter (filter_first + b) mod F, and the window
+    [out_first, out_first + out_shape) is stored (set_window; the default is S, 0, S).  The filters are given in the time domain
+    (set_filters) and transformed once.  Rank 1 is FftConv(real_data=True)."""
+
+    _prefix = "fourier_hip_convnd_"
+    _destroy = "fourier_hip_convnd_destroy"
+
+    def __init__(self, shape, real="f32", device=-1):
+        shape = tuple(int(n) for n in shape)
+        if not 2 <= len(shape) <= 4 or any(n < 1 for n in shape):
+            raise ValueError(f"shape must have 2 to 4 lengths >= 1 (rank 1 is FftConv), got {shape}")
+        self._shape = shape
+        self._create(real, f"N-D convolution plan of shape {shape}", len(shape), self._sizes(shape), int(device))
+        self._in, self._first, self._out = shape, (0,) * len(shape), shape
+
+    @staticmethod
+    def _sizes(values):
+        return (ctypes.c_size_t * len(values))(*values)
+
+    def shape(self):
+        return self._shape
+
+    def filters(self):
+        return int(self._fn("filters")(self._h))
+
+    def set_option(self, key, value):
+        """"fusion": 1 = the fused untangle route where the last length is even, 0 = the composed route (rfftn, product sweep, irfftn)."""
+        self._call("set_option", key.encode(), int(value))
+
+    def set_filters_ptr(self, d_taps, taps_shape, filters=1, correlate=False, stream=0):
+        """`filters` contiguous blocks of taps_shape <= S reals at d_taps -> the bank, enqueued on `stream`."""
+        taps_shape = tuple(int(n) for n in taps_shape)
+        if len(taps_shape) != len(self._shape):
+            raise ValueError(f"taps_shape must have {len(self._shape)} lengths, got {taps_shape}")
+        self._call("set_filters", d_taps, self._sizes(taps_shape), int(filters), int(bool(correlate)), stream)
+
+    def set_window(self, in_shape=None, out_first=None, out_shape=None):
+        """The extent of the items read (zero-extended to S at the high end) and the window of the circular result stored; None is the
+        default of each (S, 0, S).  Host state: takes effect from the next apply."""
+        r = len(self._shape)
+        win = [tuple(int(n) for n in (d if v is None else v)) for v, d in ((in_shape, self._shape), (out_first, (0,) * r), (out_shape, self._shape))]
+        if any(len(v) != r or any(n < 0 for n in v) for v in win):
+            raise ValueError(f"in_shape, out_first and out_shape must have {r} non-negative lengths")
+        self._call("set_window", *(self._sizes(v) for v in win))
+        self._in, self._first, self._out = win
+
+    def apply_ptr(self, d_in, d_out, batch, filter_first=0, stream=0):
+        """`batch` items of in_shape reals at d_in -> `batch` items of out_shape reals at d_out, enqueued on `stream`."""
+        self._call("apply_batch", d_in, d_out, int(batch), int(filter_first), stream)
+
+    def _dtype(self):
+        return _torch_dtypes(self.real)[0]
+
+    def set_filters(self, taps, correlate=False):
+        """Contiguous CUDA tensor of shape k or (F,) + k with k <= S in every dimension, of the handle's real dtype; on the current stream."""
+        r = len(self._shape)
+        _require_cuda(taps, self._dtype())
+        k = tuple(taps.shape[-r:])
+        if taps.dim() not in (r, r + 1) or taps.numel() == 0 or any(a > n for a, n in zip(k, self._shape)):
+            raise ValueError(f"taps must have shape k or (F,) + k with 1 <= k <= {self._shape}, got {tuple(taps.shape)}")
+        self.set_filters_ptr(taps.data_ptr(), k, taps.shape[0] if taps.dim() == r + 1 else 1, correlate, _stream(taps))
+
+    def apply(self, x, filter_first=0, out=None):
+        """Contiguous (..., *in_shape) CUDA tensor of the handle's real dtype -> a new (..., *out_shape) tensor, or `out` (which may be
+        `x` under the default window, and may not overlap it otherwise), on the current stream.  Item b of the flattened leading
+        dimensions uses filter (filter_first + b) mod F."""
+        import torch
+
+        r = len(self._shape)
+        _require_cuda(x, self._dtype())
+        if x.dim() < r or tuple(x.shape[-r:]) != self._in:
+            raise ValueError(f"the last {r} dimensions must be {self._in}, got {tuple(x.shape)}")
+        if int(filter_first) < 0:
+            raise ValueError("filter_first must not be negative")
+        shape = tuple(x.shape[:-r]) + self._out
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        elif out is not x or shape != tuple(x.shape):
+            _require_out(out, shape, x.dtype, x.device)
+        batch = 1
+        for n in x.shape[:-r]:
+            batch *= int(n)
+        if batch:
+            self.apply_ptr(x.data_ptr(), out.data_ptr(), batch, filter_first, _stream(x))
+        return out
+
+
+def create_convnd_f32(shape, device=-1):
+    return FftConvNd(shape, "f32", device)
+
+
+def create_convnd_f64(shape, device=-1):
+    return FftConvNd(shape, "f64", device)
+
+
+def next_fast_len(n, even=False):
+    """The smallest m >= n of the form 2^a 3^b 5^c 7^d (with even=True: the smallest even one), the padded length fftconvolven picks
+    per dimension.  An UNMEASURED heuristic: lengths of small prime factors run on the mixed-radix and register-stage plans, but no
+    measurement ranks the candidates; pass `shape=` where a measured length is known."""
+    m = max(int(n), 1)
+    if even and m % 2:
+        m += 1
+    while True:
+        rest = m
+        for p in (2, 3, 5, 7):
+            while rest % p == 0:
+                rest //= p
+        if rest == 1:
+            return m
+        m += 2 if even else 1
+
+
+def _convnd_run(x, taps, dims, r, correlate, window, out):
+    """The N-D handle of the transform shape window[0] over the `dims` of x (None: the trailing r), cached per (shape, dtype, device);
+    filters and window are set on every call."""
+    shape, in_shape, first, out_shape = window
+    real = _precision(x.dtype)[0]
+    if dims is None:
+        perm = None
+    else:
+        norm = _normalise_dims(x.dim(), dims)
+        perm = None if norm == tuple(range(x.dim() - r, x.dim())) else tuple(d for d in range(x.dim()) if d not in norm) + norm
+    src = x if perm is None else x.permute(perm).contiguous()
+    p = _cached_plan(FftConvNd, tuple(shape), real, int(_device_index(x)))
+    p.set_window(in_shape, first, out_shape)
+    p.set_filters(taps, correlate)
+    if perm is None:
+        return p.apply(src, 0, out)
+    inv = [0] * len(perm)
+    for i, d in enumerate(perm):
+        inv[d] = i
+    back = p.apply(src).permute(inv)
+    if out is None:
+        return back.contiguous()
+    _require_out(out, tuple(back.shape), x.dtype, x.device)
+    out.copy_(back)
+    return out
+
+
+def _convnd_taps(x, taps, r):
+    _require_cuda(x, _torch_dtypes("f32")[0], _torch_dtypes("f64")[0])
+    if not 2 <= r <= 4 or x.dim() < r:
+        raise ValueError(f"2 to 4 transformed dimensions of a tensor that has them, got {r} of {x.dim()}")
+    if not _is_torch(taps) or taps.dim() not in (r, r + 1) or taps.numel() == 0:
+        raise TypeError(f"taps must be a tensor of shape k or (F,) + k with {r} lengths in k")
+    return tuple(int(n) for n in taps.shape[-r:])
+
+
+def fftconvn(x, taps, dims=None, correlate=False, out=None):
+    """Circular convolution (or correlation) of a contiguous CUDA float32 / float64 tensor over `dims` with real `taps` of the same
+    dtype and shape k or (F,) + k, k <= the lengths of `dims`; dimensions outside `dims` are the batch, item b with filter b mod F.
+    dims=None means the trailing taps.dim() dimensions and one filter (give `dims` for a bank).  Two to four dimensions; one is
+    fftconv.  Dimensions that are not the trailing block in order are permuted into a contiguous copy first (slower).  Handles are
+    cached per (shape, dtype, device) and the filters are set on EVERY call; keep an FftConvNd to apply the same filters repeatedly."""
+    r = taps.dim() if dims is None else len(tuple(dims))
+    _convnd_taps(x, taps, r)
+    norm = tuple(range(x.dim() - r, x.dim())) if dims is None else _normalise_dims(x.dim(), dims)
+    shape = tuple(int(x.shape[d]) for d in norm)
+    return _convnd_run(x, taps, dims, r, correlate, (shape, shape, (0,) * r, shape), out)
+
+
+def fftconv2(x, taps, correlate=False, out=None):
+    """fftconvn over the last two dimensions; taps of shape (k1, k2) or (F, k1, k2)."""
+    return fftconvn(x, taps, (-2, -1), correlate, out)
+
+
+def fftconvolven(x, taps, mode="full", correlate=False, shape=None, out=None, rank=None):
+    """Linear convolution of a contiguous CUDA float32 / float64 tensor over its trailing `rank` dimensions (default: taps.dim(), one
+    filter; give `rank` for a bank) with real `taps` of shape k or (F,) + k, as scipy.signal.convolve over those dimensions: with
+    items of shape a, "full" is a + k - 1 values per dimension, "same" the a values from (k - 1) // 2 on, "valid" the a - k + 1 values
+    from k - 1 on (a >= k in every dimension).  correlate=True flips the taps along every transformed dimension and convolves, which
+    is scipy.signal.correlate for real data.  The transform shape is next_fast_len(a + k - 1) per dimension, even in the last one so
+    that the fused route exists, or `shape` (>= a + k - 1 in every dimension).  Handles are cached per (shape, dtype, device) and
+    the filters are set on EVERY call; keep an FftConvNd to apply the same filters repeatedly."""
+    import torch
+
+    if mode not in LCONV_MODES:
+        raise ValueError(f"mode must be one of {sorted(LCONV_MODES)}, got {mode!r}")
+    r = int(rank) if rank is not None else (len(tuple(shape)) if shape is not None else (taps.dim() if _is_torch(taps) else 0))
+    k = _convnd_taps(x, taps, r)
+    a = tuple(int(n) for n in x.shape[-r:])
+    full = tuple(n + m - 1 for n, m in zip(a, k))
+    if mode == "valid" and any(n < m for n, m in zip(a, k)):
+        raise ValueError(f"mode 'valid' needs items of at least the taps' shape {k} in every dimension, got {a}")
+    if shape is None:
+        shape = tuple(next_fast_len(n, even=(d == r - 1)) for d, n in enumerate(full))
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != r or any(s < n for s, n in zip(shape, full)):
+        raise ValueError(f"shape must have {r} lengths of at least {full}, got {shape}")
+    first = {"full": (0,) * r, "same": tuple((m - 1) // 2 for m in k), "valid": tuple(m - 1 for m in k)}[mode]
+    size = {"full": full, "same": a, "valid": tuple(n - m + 1 for n, m in zip(a, k))}[mode]
+    if correlate:
+        taps = torch.flip(taps, tuple(range(-r, 0))).contiguous()
+    return _convnd_run(x, taps, None, r, False, (shape, a, first, size), out)
+
+
+def fftconvolve2(x, taps, mode="full", correlate=False, shape=None, out=None):
+    """fftconvolven over the last two dimensions; taps of shape (k1, k2) or (F, k1, k2)."""
+    return fftconvolven(x, taps, mode, correlate, shape, out, rank=2)
 
 
 R2R_KINDS = {("dct", 2): 0, ("dct", 3): 1, ("dst", 2): 2, ("dst", 3): 3}  # FOURIER_R2R_DCT2 ... FOURIER_R2R_DST3

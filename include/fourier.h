@@ -521,6 +521,91 @@ const char *fourier_hip_conv_describe_double(const FOURIER_STRUCT fourier_conv_d
 int fourier_hip_conv_last_status_float(const FOURIER_STRUCT fourier_conv_float *);
 int fourier_hip_conv_last_status_double(const FOURIER_STRUCT fourier_conv_double *);
 
+/* ---------------- N-D convolution with a prepared filter bank (extension; the reference has none) ----------
+ * A handle is made for a transform shape S = [n_1, ..., n_{r-1}, W] of rank r = 2, 3 or 4 (every length >= 1; P = prod S) and a
+ * device.  It serves REAL data over the trailing r dimensions of contiguous items; rank 1 is fourier_hip_conv_* (real_data != 0) and
+ * is refused here (FOURIER_HIP_UNSUPPORTED: create returns NULL), as is a rank above 4.  The item bounds are fourier_hip_realnd_*'s.
+ * The handle holds a bank of F >= 1 filters, given in the time domain as `filters` contiguous blocks of taps_shape <= S reals (every
+ * length >= 1) and transformed once by fourier_hip_convnd_set_filters_* with the handle's own forward transform in T.
+ * fourier_hip_convnd_apply_batch_* maps `batch` contiguous items of in_shape reals at d_in to `batch` items of out_shape reals at
+ * d_out on DEVICE memory.  Item b
+ *   is zero-extended from in_shape <= S to S at the high end of every dimension,
+ *   is convolved circularly over S with filter f = (filter_first + b) mod F (b counted over the whole call),
+ *       y = irfftn(rfftn(x, S) * H[f], S),   H[f] = rfftn(h[f] zero-extended to S) / P   (conj H[f] where correlate != 0:
+ *       y[n] = sum_m x[(n + m) mod S] h[m], the circular correlation),
+ *   and the window [out_first, out_first + out_shape) of y is stored; out_first + out_shape <= S in every dimension, the window never
+ *   wraps.
+ * fourier_hip_convnd_set_window_* sets in_shape, out_first and out_shape (arrays of r lengths; host state, no device work; the
+ * default is S, 0, S) and may be called between applies.  With in_shape = a, taps k, S >= a + k - 1, out_first = 0 / (k - 1) / 2 /
+ * k - 1 and out_shape = a + k - 1 / a / a - k + 1 the items are scipy.signal.convolve's "full" / "same" / "valid".
+ * The bins that are their own mirror (columns 0 and W/2 of the rows that are their own mirror row) are real and are multiplied by
+ * the real part of H, as numpy's irfftn drops their imaginary parts.  No atomics: a repetition is bit-equal, and scaling the input by
+ * a power of two scales the output exactly.
+ * d_in == d_out is in place and allowed when in_shape == out_shape == S; any other overlap, a NULL pointer, a pointer not aligned to
+ * 2*sizeof(T) (taps: sizeof(T)), a length of 0 or above S in taps_shape, in_shape or out_shape, a window beyond S, filters == 0, or
+ * apply before any filters were set give FOURIER_HIP_INVALID_ARGUMENT.  batch == 0 is a successful no-op.  set_filters and apply are
+ * stream-ordered on `stream` like fourier_hip_transform_batch_*; set_filters may allocate (and so synchronise) when the bank grows,
+ * and may be called again to replace the bank, not while a call on the handle is in flight.
+ * Routes, chosen at create (fourier_hip_convnd_describe_* names the route and the plans under it):
+ *   even W   "convnd fused untangle: ..."  [a pad sweep into the scratch where in_shape != S,] the W/2-point row plan forward on the
+ *                                          packed reals, the leading axes' transforms in place, ONE sweep in place (untangle with the
+ *                                          mirror rows, product with the half spectrum, retangle), the axes' unscaled inverses, the
+ *                                          row plan's unscaled inverse [and a crop sweep under any window but the whole of S].
+ *                                          The half spectrum never reaches memory.
+ *   odd W    "convnd composed: ..."        [pad,] rfftn into a half-spectrum scratch, one product sweep in place, unscaled irfftn
+ *                                          [, crop]
+ * Option "fusion" (fourier_hip_convnd_set_option_*): 1 = as above, 0 = the composed route for every W.  The default is the value
+ * that measured faster (README.md, "N-D convolution").
+ * Bytes per item of N = P reals of f32, algorithmic, the bank not counted: fused 40 N (rows 8 N + 8 N, axes 8 N + 8 N, the sweep
+ * 8 N) against 56 N composed (rfftn 24 N, product 8 N, irfftn 24 N); a window adds its copy.
+ * Device memory the handle owns: the bank, F x P/W x (W/2 + 1) complex, the plans' own tables and buffers, and a scratch of at most
+ * 1 GiB (never less than one item); larger batches are walked in chunks of whole items.  The handle sits on a whole real-input N-D
+ * plan (fourier_hip_realnd_*), which transforms the filters and runs the composed route, and so also keeps that plan's own scratch.
+ * After fourier_hip_convnd_reserve_* for `batch` items, apply calls of at most `batch` items on the route of that moment never
+ * allocate; after a change of "fusion" call reserve again.  Handles are Send, not Sync; the status of the last call that did work
+ * (set_filters, set_window, apply_batch, reserve) is fourier_hip_convnd_last_status_*. */
+struct fourier_convnd_float;
+struct fourier_convnd_double;
+
+/* NULL on failure (rank outside 2 ... 4, a NULL shape or a length of 0 included). */
+struct fourier_convnd_float *fourier_hip_convnd_create_float(int rank, const FOURIER_SIZE_TYPE *shape, int device);
+struct fourier_convnd_double *fourier_hip_convnd_create_double(int rank, const FOURIER_SIZE_TYPE *shape, int device);
+/* NULL is a no-op. */
+void fourier_hip_convnd_destroy_float(FOURIER_STRUCT fourier_convnd_float *);
+void fourier_hip_convnd_destroy_double(FOURIER_STRUCT fourier_convnd_double *);
+/* r; 0 for a NULL handle. */
+int fourier_hip_convnd_rank_float(const FOURIER_STRUCT fourier_convnd_float *);
+int fourier_hip_convnd_rank_double(const FOURIER_STRUCT fourier_convnd_double *);
+/* S into out[0 .. r-1]; FOURIER_HIP_INVALID_ARGUMENT for a NULL handle or a NULL out. */
+int fourier_hip_convnd_shape_float(const FOURIER_STRUCT fourier_convnd_float *, FOURIER_SIZE_TYPE *out);
+int fourier_hip_convnd_shape_double(const FOURIER_STRUCT fourier_convnd_double *, FOURIER_SIZE_TYPE *out);
+/* F; 0 before set_filters and for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_convnd_filters_float(const FOURIER_STRUCT fourier_convnd_float *);
+FOURIER_SIZE_TYPE fourier_hip_convnd_filters_double(const FOURIER_STRUCT fourier_convnd_double *);
+int fourier_hip_convnd_set_filters_float(FOURIER_STRUCT fourier_convnd_float *, const void *d_taps, const FOURIER_SIZE_TYPE *taps_shape,
+                                         FOURIER_SIZE_TYPE filters, int correlate, void *stream);
+int fourier_hip_convnd_set_filters_double(FOURIER_STRUCT fourier_convnd_double *, const void *d_taps, const FOURIER_SIZE_TYPE *taps_shape,
+                                          FOURIER_SIZE_TYPE filters, int correlate, void *stream);
+int fourier_hip_convnd_set_window_float(FOURIER_STRUCT fourier_convnd_float *, const FOURIER_SIZE_TYPE *in_shape,
+                                        const FOURIER_SIZE_TYPE *out_first, const FOURIER_SIZE_TYPE *out_shape);
+int fourier_hip_convnd_set_window_double(FOURIER_STRUCT fourier_convnd_double *, const FOURIER_SIZE_TYPE *in_shape,
+                                         const FOURIER_SIZE_TYPE *out_first, const FOURIER_SIZE_TYPE *out_shape);
+int fourier_hip_convnd_apply_batch_float(const FOURIER_STRUCT fourier_convnd_float *, const void *d_in, void *d_out,
+                                         FOURIER_SIZE_TYPE batch, FOURIER_SIZE_TYPE filter_first, void *stream);
+int fourier_hip_convnd_apply_batch_double(const FOURIER_STRUCT fourier_convnd_double *, const void *d_in, void *d_out,
+                                          FOURIER_SIZE_TYPE batch, FOURIER_SIZE_TYPE filter_first, void *stream);
+/* Pre-size the scratch and the plans' buffers: afterwards apply calls of at most `batch` items never allocate. */
+int fourier_hip_convnd_reserve_float(const FOURIER_STRUCT fourier_convnd_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_convnd_reserve_double(const FOURIER_STRUCT fourier_convnd_double *, FOURIER_SIZE_TYPE batch);
+/* "fusion": 1 / 0 = the composed route.  FOURIER_HIP_INVALID_ARGUMENT for anything else. */
+int fourier_hip_convnd_set_option_float(FOURIER_STRUCT fourier_convnd_float *, const char *key, long long value);
+int fourier_hip_convnd_set_option_double(FOURIER_STRUCT fourier_convnd_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_convnd_describe_float(const FOURIER_STRUCT fourier_convnd_float *);
+const char *fourier_hip_convnd_describe_double(const FOURIER_STRUCT fourier_convnd_double *);
+int fourier_hip_convnd_last_status_float(const FOURIER_STRUCT fourier_convnd_float *);
+int fourier_hip_convnd_last_status_double(const FOURIER_STRUCT fourier_convnd_double *);
+
 /* ---------------- linear convolution with a prepared filter bank by overlap-save (extension; the reference has none) ----------
  * A handle is made for a row length Lx >= 1, a tap count K >= 1, a mode, a kind of data (real_data == 0: rows of interleaved complex
  * T with complex taps, else rows of reals T with real taps) and a device.  It holds a bank of F >= 1 filters of K taps, given in the
@@ -2372,6 +2457,57 @@ template <typename T> struct conv;
 FOURIER_DEFINE_CXX_CONV_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CONV_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CONV_WRAPPER
+
+/* N-D convolution of real items with a prepared filter bank on device memory (extension): fourier::convnd<float> / <double> */
+template <typename T> struct convnd;
+
+#define FOURIER_DEFINE_CXX_CONVND_WRAPPER(T, SUFFIX)                                                \
+  template <> struct convnd<T> {                                                                    \
+    convnd(int rank, const std::size_t *shape, int device = -1)                                     \
+        : impl(::fourier::c::fourier_hip_convnd_create_##SUFFIX(rank, shape, device),               \
+               ::fourier::c::fourier_hip_convnd_destroy_##SUFFIX) {}                                \
+    convnd() = delete;                                                                              \
+    convnd(const convnd &) = delete;                                                                \
+    convnd(convnd &&) = default;                                                                    \
+    convnd &operator=(const convnd &) = delete;                                                     \
+    convnd &operator=(convnd &&) = default;                                                         \
+    ~convnd() = default;                                                                            \
+    int rank() const { return ::fourier::c::fourier_hip_convnd_rank_##SUFFIX(impl.get()); }         \
+    /* S into out[0 .. rank-1] */                                                                   \
+    int shape(std::size_t *out) const { return ::fourier::c::fourier_hip_convnd_shape_##SUFFIX(impl.get(), out); } \
+    std::size_t filters() const { return ::fourier::c::fourier_hip_convnd_filters_##SUFFIX(impl.get()); } \
+    /* `filters` blocks of taps_shape reals -> the bank */                                          \
+    int set_filters_device(const void *d_taps, const std::size_t *taps_shape, std::size_t filters = 1, \
+                           bool correlate = false, void *stream = nullptr) {                        \
+      return ::fourier::c::fourier_hip_convnd_set_filters_##SUFFIX(impl.get(), d_taps, taps_shape, filters, \
+                                                                   correlate ? 1 : 0, stream);      \
+    }                                                                                               \
+    /* the extent of the items read and the window of the result stored (default: S, 0, S) */       \
+    int set_window(const std::size_t *in_shape, const std::size_t *out_first, const std::size_t *out_shape) { \
+      return ::fourier::c::fourier_hip_convnd_set_window_##SUFFIX(impl.get(), in_shape, out_first, out_shape); \
+    }                                                                                               \
+    /* `batch` items of in_shape reals -> `batch` items of out_shape reals, item b with filter (filter_first + b) mod F */ \
+    int apply_device(const void *d_in, void *d_out, std::size_t batch, std::size_t filter_first = 0, \
+                     void *stream = nullptr) const {                                                \
+      return ::fourier::c::fourier_hip_convnd_apply_batch_##SUFFIX(impl.get(), d_in, d_out, batch, filter_first, stream); \
+    }                                                                                               \
+    int reserve(std::size_t batch) const {                                                          \
+      return ::fourier::c::fourier_hip_convnd_reserve_##SUFFIX(impl.get(), batch);                  \
+    }                                                                                               \
+    int set_option(const char *key, long long value) {                                              \
+      return ::fourier::c::fourier_hip_convnd_set_option_##SUFFIX(impl.get(), key, value);          \
+    }                                                                                               \
+    const char *describe() const { return ::fourier::c::fourier_hip_convnd_describe_##SUFFIX(impl.get()); } \
+    int last_status() const { return ::fourier::c::fourier_hip_convnd_last_status_##SUFFIX(impl.get()); } \
+    explicit operator bool() const { return static_cast<bool>(impl); }                              \
+                                                                                                    \
+  private:                                                                                          \
+    ::std::unique_ptr<::fourier::c::fourier_convnd_##SUFFIX,                                        \
+                      void (*)(::fourier::c::fourier_convnd_##SUFFIX *)> impl;                      \
+  };
+FOURIER_DEFINE_CXX_CONVND_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_CONVND_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_CONVND_WRAPPER
 
 /* linear convolution with a prepared filter bank on device memory (extension): fourier::lconv<float> / <double> */
 template <typename T> struct lconv;
