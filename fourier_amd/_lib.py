@@ -123,6 +123,13 @@ _CEPSTRUM = ("fourier_hip_cepstrum_", {  # real cepstrum (mode 0) and minimum-ph
     "destroy": (None, [vp]), "size": (sz, [vp]), "length": (sz, [vp]), "outputs": (sz, [vp]), "mode": (ci, [vp]),
     "apply": (ci, [vp, vp, vp, sz, ctypes.c_double, ctypes.c_double, vp]),  # handle, d_in, d_out, batch, log_mult, log_floor, stream
     "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_NUFFT = ("fourier_hip_nufft_", {  # non-uniform FFT, 1-D types 1 and 2, points shared by the rows of a batch
+    "create": (vp, [sz, ctypes.c_double, ci]),  # n_modes, eps, device
+    "destroy": (None, [vp]), "modes": (sz, [vp]), "points": (sz, [vp]),
+    "set_points": (ci, [vp, vp, sz, vp]),  # handle, h_points (f64 on the host), m, stream
+    "to_modes_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),  # handle, d_in, d_out, batch, sign, order, stream
+    "to_points_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -154,8 +161,9 @@ XCORR_SYMBOLS = list(_signatures(_XCORR))
 DELAY_SYMBOLS = list(_signatures(_DELAY))
 CEPSTRUM_SYMBOLS = list(_signatures(_CEPSTRUM))
 CONVND_SYMBOLS = list(_signatures(_CONVND))
+NUFFT_SYMBOLS = list(_signatures(_NUFFT))
 ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REALND_SYMBOLS + CONV_SYMBOLS + LCONV_SYMBOLS + STFT_SYMBOLS + MDCT_SYMBOLS
-               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS + CEPSTRUM_SYMBOLS + CONVND_SYMBOLS)
+               + SPECTROGRAM_SYMBOLS + CSD_SYMBOLS + BANDSPEC_SYMBOLS + HILBERT_SYMBOLS + CZT_SYMBOLS + PFB_SYMBOLS + IPFB_SYMBOLS + RESAMPLE_SYMBOLS + XCORR_SYMBOLS + DELAY_SYMBOLS + CEPSTRUM_SYMBOLS + CONVND_SYMBOLS + NUFFT_SYMBOLS)
 # The r2r family is listed apart: tests/test_abi.py compares ALL_SYMBOLS with the names a letters-only pattern finds in the header,
 # and that pattern cannot see a name with a digit in it.  tests/test_r2r_abi.py holds the same three-way check for these.
 R2R_SYMBOLS = list(_signatures(_R2R))
@@ -165,7 +173,7 @@ def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM, _CONVND):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM, _CONVND, _NUFFT):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

@@ -32,6 +32,7 @@
 #include "xcorr_plan.h"
 #include "delay_plan.h"
 #include "cepstrum_plan.h"
+#include "nufft_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -788,6 +789,39 @@ FOURIER_DEFINE_DELAY_ABI(double, double)
 
 FOURIER_DEFINE_CEPSTRUM_ABI(float, float)
 FOURIER_DEFINE_CEPSTRUM_ABI(double, double)
+
+// non-uniform FFT, 1-D types 1 and 2 (fourier_hip_nufft_*)
+#define FOURIER_DEFINE_NUFFT_ABI(T, SUFFIX)                                                                      \
+  FOURIER_DEFINE_HANDLE_ABI(nufft, fourier_nufft_##SUFFIX, NufftPlan<T>, SUFFIX)                                 \
+  extern "C" fc::fourier_nufft_##SUFFIX* fourier_hip_nufft_create_##SUFFIX(size_t n_modes, double eps, int device) { \
+    return (fc::fourier_nufft_##SUFFIX*)create_handle<NufftPlan<T>>(n_modes, eps, device);                       \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft_modes_##SUFFIX(const fc::fourier_nufft_##SUFFIX* h) {                      \
+    return h ? ((const NufftPlan<T>*)h)->modes() : 0;                                                            \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft_points_##SUFFIX(const fc::fourier_nufft_##SUFFIX* h) {                     \
+    return h ? ((const NufftPlan<T>*)h)->points() : 0;                                                           \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft_set_points_##SUFFIX(fc::fourier_nufft_##SUFFIX* h, const double* h_points, size_t m, void* stream) { \
+    NufftPlan<T>* p = (NufftPlan<T>*)h;                                                                          \
+    return guarded_handle(p, [&] { p->set_points(h_points, m, (hipStream_t)stream); });                          \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft_to_modes_batch_##SUFFIX(const fc::fourier_nufft_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                           size_t batch, int sign, int order, void* stream) {    \
+    const NufftPlan<T>* p = (const NufftPlan<T>*)h;                                                              \
+    return guarded_handle(p, [&] { p->to_modes(d_in, d_out, batch, sign, order, (hipStream_t)stream); });        \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft_to_points_batch_##SUFFIX(const fc::fourier_nufft_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                            size_t batch, int sign, int order, void* stream) {   \
+    const NufftPlan<T>* p = (const NufftPlan<T>*)h;                                                              \
+    return guarded_handle(p, [&] { p->to_points(d_in, d_out, batch, sign, order, (hipStream_t)stream); });       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft_set_option_##SUFFIX(fc::fourier_nufft_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<NufftPlan<T>>(h, key, v);                                                           \
+  }
+
+FOURIER_DEFINE_NUFFT_ABI(float, float)
+FOURIER_DEFINE_NUFFT_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

@@ -208,6 +208,7 @@ typedef void (*ResampleKernel)(ResampleArgs);
 typedef void (*XcorrKernel)(XcorrArgs);
 typedef void (*DelayKernel)(DelayArgs);
 typedef void (*CepstrumKernel)(CepstrumArgs);
+typedef void (*NufftKernel)(NufftArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -344,6 +345,13 @@ template <typename T> struct Real {};
   /* composed route's sweeps, which = CEPSTRUM_LOG ... CEPSTRUM_EXP                                                       */ \
   bool get_cepstrum_small_kernel(Real<T>, int k, bool minphase, KernelInfo& info);                                     \
   CepstrumKernel get_cepstrum_kernel(Real<T>, int which);                                                              \
+  /* kernels_nufft.cpp: the non-uniform FFT's spreading gather and interpolation for a kernel width w and a block of rb  */ \
+  /* rows (null outside 2 <= w <= nufft_max_width, 1 <= rb <= NUFFT_RB), its sweeps, which = NUFFT_DECONV / NUFFT_AMPLIFY, */ \
+  /* and the set-up kernel of the tabulated weights                                                                      */ \
+  NufftKernel get_nufft_spread_kernel(Real<T>, int w, int rb);                                                         \
+  NufftKernel get_nufft_interp_kernel(Real<T>, int w, int rb);                                                         \
+  NufftKernel get_nufft_sweep_kernel(Real<T>, int which);                                                              \
+  NufftKernel get_nufft_table_kernel(Real<T>);                                                                         \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

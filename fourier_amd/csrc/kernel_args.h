@@ -555,6 +555,33 @@ struct CepstrumArgs {
   double scale;               // log, exp: the inverse's 1 / l, computed in T
 };
 
+// ---- non-uniform FFT, 1-D, types 1 and 2 (kernels_nufft.h; NufftPlan, nufft_plan.h): m points shared by the rows of a batch, sorted by
+// their fine-grid coordinate; fine-grid rows of l cells, rows of m strengths, rows of n modes, all complex T.
+// nufft_spread_kernel / nufft_interp_kernel: one lane per (row block, cell) / (row block, sorted point); `blocks` row blocks of RB rows
+// from the launch's first row on, `per` workgroups a row block.  Every row has a buffer descriptor of its own (row bytes <= 2^31 - 1).
+// nufft_deconv_kernel / nufft_amplify_kernel: one lane per output value over a flat index; byte offsets are 32-bit (at most
+// REAL_LAUNCH_BYTES of either side per launch).  nufft_table_kernel: one lane per point, w weights each.
+enum { NUFFT_DECONV = 0, NUFFT_AMPLIFY = 1 };
+constexpr int NUFFT_RB = 4;                      // rows a lane of the two hot kernels serves ("Non-uniform FFT")
+constexpr int NUFFT_MIN_W = 2, NUFFT_MAX_W_F32 = 8, NUFFT_MAX_W_F64 = 16;  // the kernel widths with an instance
+struct NufftArgs {
+  const void* in; void* out;  // spread: strengths -> grid; interp: grid -> strengths; deconv: grid -> modes; amplify: modes -> grid
+  const int32_t* i0;          // [m] first cell of sorted point p (may lie outside [0, l): the footprint wraps)
+  const void* d;              // [m] reals T: i0 - xg, in [-w/2, -w/2 + 1)
+  const uint32_t* perm;       // [m] the caller's index of sorted point p
+  const uint32_t* first;      // [l + 2w + 1]: first[e + w] = sorted points with i0 < e, e in [-w, l + w]
+  const void* wtab;           // tabulated route: [w][m] reals T, weight of tap t of sorted point p at t * m + p; null: evaluated
+  const void* inv_phihat;     // [n / 2 + 1] reals T: 1 / phihat(|k|)
+  uint32_t l, m, n, w;
+  uint32_t blocks, per;       // spread, interp: row blocks of this launch; workgroups a row block
+  uint32_t per_m, per_l;      // blk / per = (umulhi(blk, per_m) + blk) >> per_l
+  uint32_t total;             // deconv, amplify: values of this launch; table: m
+  uint32_t div_m, div_l;      // deconv: idx / n; amplify: idx / l
+  uint32_t in_bytes, out_bytes;  // deconv, amplify: descriptor ranges of this launch
+  uint32_t order;             // 0: k ascending from -floor(n/2); 1: FFT order
+  double beta;                // 2.30 w
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

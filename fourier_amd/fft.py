@@ -2154,6 +2154,150 @@ def minimum_phase(x, length=None, outputs=None, half=False, log_floor=0.0, out=N
     return _cepstrum_rows(x, length, outputs, Cepstrum.MINIMUM_PHASE, 0.5 if half else 1.0, log_floor, out)
 
 
+class Nufft(_Handle):
+    """Batched 1-D non-uniform FFT of types 1 and 2 (include/fourier.h, fourier_hip_nufft_*) on device memory, the points shared by
+    the rows of a batch.  For n_modes = N modes k = -floor(N/2) .. ceil(N/2) - 1 and M points x_j (set_points; any finite reals, taken
+    modulo 2 pi):
+        to_modes  (type 1)   f[b, k] = sum_j c[b, j] exp(i isign k x_j)      (..., M) -> (..., N)
+        to_points (type 2)   c[b, j] = sum_k f[b, k] exp(i isign k x_j)      (..., N) -> (..., M)
+    with no scale factor; to_points with isign s is the exact adjoint of to_modes with -s.  `eps` is the requested relative accuracy:
+    the kernel width is w = ceil(log10(1 / eps)) + 1, clamped to 2 .. 8 at f32 and 2 .. 16 at f64, and the relative L2 error of a call
+    is about 10^(1 - w) plus the rounding of the precision.  modeord 0 stores k ascending, 1 in FFT order."""
+
+    _prefix = "fourier_hip_nufft_"
+    _destroy = "fourier_hip_nufft_destroy"
+
+    def __init__(self, n_modes, eps=1e-6, real="f32", device=-1):
+        import math
+
+        n_modes, eps = int(n_modes), float(eps)
+        if n_modes < 1:
+            raise ValueError(f"need n_modes >= 1, got {n_modes}")
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"need a finite eps > 0, got {eps}")
+        self._create(real, f"nufft plan of {n_modes} modes, eps {eps}", n_modes, eps, int(device))
+        self._n, self.eps = n_modes, eps
+
+    def modes(self):
+        return self._n
+
+    def points(self):
+        return int(self._fn("points")(self._h))
+
+    def set_option(self, key, value):
+        """"table": 0 = the weights are evaluated in the kernels, 1 = they are read from a table written once per set_points."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def set_points_ptr(self, h_points, m, stream=0):
+        """`m` float64 values at the HOST address h_points.  Waits for `stream`."""
+        self._call("set_points", h_points, int(m), stream)
+
+    def set_points(self, x):
+        """A numpy array or a torch tensor (any device, any real dtype) of M points: copied to the host as float64.  Every point must be
+        finite.  Replaces the points in use; waits for the current stream."""
+        import numpy as np
+
+        if _is_torch(x):
+            x = x.detach().cpu().numpy()
+        elif not isinstance(x, np.ndarray):
+            raise TypeError("points must be a numpy array or a torch tensor")
+        if x.dtype.kind not in "fiu":
+            raise TypeError(f"points must be real, got {x.dtype}")
+        host = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if not np.isfinite(host).all():
+            raise ValueError("every point must be finite")
+        stream = 0
+        try:
+            import torch
+
+            if torch.cuda.is_available():
+                stream = torch.cuda.current_stream().cuda_stream
+        except Exception:
+            pass
+        self.set_points_ptr(host.ctypes.data if host.size else None, host.size, stream)
+
+    def to_modes_ptr(self, d_in, d_out, batch, isign=-1, modeord=0, stream=0):
+        """`batch` rows of points() complex values at d_in -> `batch` rows of modes() complex values at d_out, enqueued on `stream`."""
+        self._call("to_modes_batch", d_in, d_out, int(batch), int(isign), int(modeord), stream)
+
+    def to_points_ptr(self, d_in, d_out, batch, isign=1, modeord=0, stream=0):
+        """`batch` rows of modes() complex values at d_in -> `batch` rows of points() complex values at d_out, enqueued on `stream`."""
+        self._call("to_points_batch", d_in, d_out, int(batch), int(isign), int(modeord), stream)
+
+    def _run(self, op, x, ivals, ovals, isign, modeord, out):
+        import torch
+
+        cdt = _torch_dtypes(self.real)[1]
+        _require_cuda(x, cdt)
+        if x.dim() == 0 or x.shape[-1] != ivals:
+            raise ValueError(f"last dimension must be {ivals}, got {tuple(x.shape)}")
+        if isign not in (1, -1):
+            raise ValueError(f"isign must be +1 or -1, got {isign}")
+        if modeord not in (0, 1):
+            raise ValueError(f"modeord must be 0 or 1, got {modeord}")
+        shape = tuple(x.shape[:-1]) + (ovals,)
+        batch = 1
+        for s in shape[:-1]:
+            batch *= int(s)
+        if out is None:
+            out = torch.empty(shape, dtype=cdt, device=x.device)
+        else:
+            _require_out(out, shape, cdt, x.device)
+        if batch:
+            self._call(op, x.data_ptr(), out.data_ptr(), batch, int(isign), int(modeord), _stream(x))
+        return out
+
+    def to_modes(self, c, isign=-1, modeord=0, out=None):
+        """A contiguous (..., points()) complex CUDA tensor of the handle's precision -> a new (..., modes()) tensor, or `out` (which may
+        not overlap `c`), on the current stream."""
+        return self._run("to_modes_batch", c, self.points(), self._n, isign, modeord, out)
+
+    def to_points(self, f, isign=1, modeord=0, out=None):
+        """A contiguous (..., modes()) complex CUDA tensor of the handle's precision -> a new (..., points()) tensor, or `out` (which may
+        not overlap `f`), on the current stream."""
+        return self._run("to_points_batch", f, self._n, self.points(), isign, modeord, out)
+
+
+def create_nufft_f32(n_modes, eps=1e-6, device=-1):
+    return Nufft(n_modes, eps, "f32", device)
+
+
+def create_nufft_f64(n_modes, eps=1e-6, device=-1):
+    return Nufft(n_modes, eps, "f64", device)
+
+
+def _nufft_plan(x, v, n_modes, eps):
+    """nufft1 / nufft2: the cached handle of (n_modes, eps, precision, device) with the points `x` set"""
+    if not (_is_torch(v) and v.is_cuda and _precision(v.dtype) is not None and not _precision(v.dtype)[1]):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor")
+    if v.dim() == 0:
+        raise ValueError("expected at least one dimension")
+    plan = _cached_plan(Nufft, int(n_modes), float(eps), _precision(v.dtype)[0], int(_device_index(v)))
+    plan.set_points(x)
+    return plan
+
+
+def nufft1(x, c, n_modes, eps=1e-6, isign=-1):
+    """Type 1 (points to modes): f[..., k] = sum_j c[..., j] exp(i isign k x[j]), k = -floor(n_modes/2) .. ceil(n_modes/2) - 1 ascending,
+    for M points `x` (numpy or torch, any device, copied to the host as float64) and a CUDA complex64 / complex128 tensor `c` of shape
+    (..., M), whose leading dimensions are a batch that shares the points; on the current stream.  Returns a new (..., n_modes) tensor.
+    One cached Nufft handle per (n_modes, eps, dtype, device); every call sets its points, a set-up step that waits for the stream:
+    keep a Nufft of your own where the points stay."""
+    plan = _nufft_plan(x, c, n_modes, eps)
+    return plan.to_modes(c.contiguous(), isign)
+
+
+def nufft2(x, f, eps=1e-6, isign=1):
+    """Type 2 (modes to points): c[..., j] = sum_k f[..., k] exp(i isign k x[j]) for a CUDA complex64 / complex128 tensor `f` of shape
+    (..., N) holding the modes k = -floor(N/2) .. ceil(N/2) - 1 ascending, and M points `x` (as for nufft1); on the current stream.
+    Returns a new (..., M) tensor.  The cached handle and its set-up step are nufft1's."""
+    n_modes = int(f.shape[-1]) if _is_torch(f) and f.dim() else 0
+    if n_modes < 1:
+        raise ValueError("the mode dimension must have length >= 1")
+    plan = _nufft_plan(x, f, n_modes, eps)
+    return plan.to_points(f.contiguous(), isign)
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

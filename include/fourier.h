@@ -1679,6 +1679,79 @@ const char *fourier_hip_cepstrum_describe_double(const FOURIER_STRUCT fourier_ce
 int fourier_hip_cepstrum_last_status_float(const FOURIER_STRUCT fourier_cepstrum_float *);
 int fourier_hip_cepstrum_last_status_double(const FOURIER_STRUCT fourier_cepstrum_double *);
 
+/* ---------------- non-uniform FFT, 1-D, types 1 and 2 (extension; the reference has none) ----------
+ * FINUFFT's 1-D type 1 and type 2 with the points shared by the rows of a batch.  A handle is created for n_modes = N >= 1 and a
+ * requested accuracy eps; fourier_hip_nufft_set_points_* gives it M >= 0 points x_j, any finite reals, taken modulo 2 pi.  The mode
+ * index k runs over -floor(N/2) .. ceil(N/2) - 1.  With s = `sign`, +1 or -1 per call:
+ *   to_modes  (type 1)   f[b][k] = sum_j c[b][j] exp(i s k x_j)     `batch` rows of M complex T in, `batch` rows of N complex T out
+ *   to_points (type 2)   c[b][j] = sum_k f[b][k] exp(i s k x_j)     `batch` rows of N complex T in, `batch` rows of M complex T out
+ * on DEVICE memory, interleaved complex values, row b at element offset b*M or b*N.  `order` 0 stores the modes with k ascending as
+ * above, 1 in FFT order (k = 0 .. ceil(N/2) - 1, -floor(N/2) .. -1).  There is no scale factor; to_points with sign s is the exact
+ * adjoint of to_modes with sign -s.
+ * The algorithm is fixed: the "exponential of semicircle" kernel phi(z) = exp(beta (sqrt(1 - z^2) - 1)) on |z| <= 1, beta = 2.30 w, of
+ * width w = ceil(log10(1 / eps)) + 1 clamped to 2 .. 8 (float) or 2 .. 16 (double), on a fine grid whose length L is the smallest
+ * 2^a 3^b 5^c >= max(2 N, 2 w); a point with grid coordinate xg = (x mod 2 pi) L / (2 pi) touches the cells ceil(xg - w/2) + 0 .. w - 1
+ * modulo L with weight phi(2 (i - xg) / w); the deconvolution factor 1 / phihat(k), phihat(k) the integral over |t| <= w/2 of
+ * phi(2 t / w) cos(2 pi k t / L), is computed on the host in double by a quadrature good to 1e-15.  to_modes spreads onto the grid (a
+ * gather over the sorted points: no atomics), runs the L-point plan (FFT for s = -1, UNSCALED_IFFT for s = +1), picks the N modes
+ * and multiplies by 1 / phihat; to_points writes f / phihat into a zeroed grid, runs the plan and interpolates at the points.  The
+ * relative L2 error of a call against the direct sum is about 10^(1 - w), plus the rounding of T.
+ * fourier_hip_nufft_set_points_*: h_points points to m doubles on the HOST, for both precisions (the fold modulo 2 pi needs them).  A
+ * set-up call like fourier_hip_bandspec_set_bands_*: it waits for `stream`, sorts the points by grid coordinate (stable: equal points
+ * keep the caller's order), uploads the tables and waits again.  Calling it again replaces the points; m == 0 is valid (to_modes then
+ * writes zeros, to_points writes nothing).  A NaN or infinite point, m > 2^31 - 1, m * 2 * sizeof(T) > 2^30, a NULL pointer with m > 0
+ * or one not aligned to 8 bytes give FOURIER_HIP_INVALID_ARGUMENT and leave the points as they were; so does an allocation or copy
+ * that fails (the new tables replace the old ones only when all of them are complete).
+ * A transform call before any set_points, sign other than +1 / -1, order other than 0 / 1, a NULL or misaligned (2*sizeof(T)) buffer
+ * and ANY overlap of input and output give FOURIER_HIP_INVALID_ARGUMENT and write nothing.  batch == 0 is a successful no-op.
+ * n_modes == 0, eps <= 0 or not finite, or a row above 2^30 bytes: create fails.  Stream-ordered on `stream` like
+ * fourier_hip_transform_batch_*.
+ * Option "table" (fourier_hip_nufft_set_option_*): 0 = "nufft evaluated", the weights are evaluated in the two hot kernels with the
+ * accurate exp and sqrt; 1 = "nufft tabulated", a set-up kernel writes the M x w weights once (at set_points, or at set_option on the
+ * null stream when points are set) and the hot kernels read them.  The two routes agree to rounding.  The default is 0: the
+ * tabulated route beat the evaluated one at none of the measured shapes ("Non-uniform FFT").  fourier_hip_nufft_describe_* begins "nufft evaluated: " or
+ * "nufft tabulated: ", then "w <w>, L <L>, " and the inner plan's description.
+ * The plan owns a scratch of fine-grid rows of at most 1 GiB (never less than one row) and walks larger batches in chunks; the first
+ * call with a batch larger than any before allocates it unless fourier_hip_nufft_reserve_* was called for at least that batch.  No
+ * atomics and a summation order fixed by the points: the result is the same on repetition.  A NULL handle gives
+ * FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_nufft_modes_* / _points_* and "" from fourier_hip_nufft_describe_*.  Handles are
+ * Send, not Sync, like the complex ones; status of the last call: fourier_hip_nufft_last_status_*. */
+struct fourier_nufft_float;
+struct fourier_nufft_double;
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_nufft_float *fourier_hip_nufft_create_float(FOURIER_SIZE_TYPE n_modes, double eps, int device);
+struct fourier_nufft_double *fourier_hip_nufft_create_double(FOURIER_SIZE_TYPE n_modes, double eps, int device);
+/* NULL is a no-op. */
+void fourier_hip_nufft_destroy_float(FOURIER_STRUCT fourier_nufft_float *);
+void fourier_hip_nufft_destroy_double(FOURIER_STRUCT fourier_nufft_double *);
+/* N, and the M of the last set_points (0 before any); 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_nufft_modes_float(const FOURIER_STRUCT fourier_nufft_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft_modes_double(const FOURIER_STRUCT fourier_nufft_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft_points_float(const FOURIER_STRUCT fourier_nufft_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft_points_double(const FOURIER_STRUCT fourier_nufft_double *);
+/* m doubles on the host, for both precisions. */
+int fourier_hip_nufft_set_points_float(FOURIER_STRUCT fourier_nufft_float *, const double *h_points, FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft_set_points_double(FOURIER_STRUCT fourier_nufft_double *, const double *h_points, FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft_to_modes_batch_float(const FOURIER_STRUCT fourier_nufft_float *, const void *d_in, void *d_out,
+                                           FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft_to_modes_batch_double(const FOURIER_STRUCT fourier_nufft_double *, const void *d_in, void *d_out,
+                                            FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft_to_points_batch_float(const FOURIER_STRUCT fourier_nufft_float *, const void *d_in, void *d_out,
+                                            FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft_to_points_batch_double(const FOURIER_STRUCT fourier_nufft_double *, const void *d_in, void *d_out,
+                                             FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft_reserve_float(const FOURIER_STRUCT fourier_nufft_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_nufft_reserve_double(const FOURIER_STRUCT fourier_nufft_double *, FOURIER_SIZE_TYPE batch);
+/* "table": 0 / 1.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_nufft_set_option_float(FOURIER_STRUCT fourier_nufft_float *, const char *key, long long value);
+int fourier_hip_nufft_set_option_double(FOURIER_STRUCT fourier_nufft_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_nufft_describe_float(const FOURIER_STRUCT fourier_nufft_float *);
+const char *fourier_hip_nufft_describe_double(const FOURIER_STRUCT fourier_nufft_double *);
+int fourier_hip_nufft_last_status_float(const FOURIER_STRUCT fourier_nufft_float *);
+int fourier_hip_nufft_last_status_double(const FOURIER_STRUCT fourier_nufft_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -2270,6 +2343,54 @@ template <typename T> struct cepstrum;
 FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_CEPSTRUM_WRAPPER
+
+/* non-uniform FFT, 1-D types 1 and 2, on device memory (extension): fourier::nufft<float> / <double> */
+template <typename T> struct nufft;
+
+#define FOURIER_DEFINE_CXX_NUFFT_WRAPPER(T, SUFFIX)                                                \
+  template <> struct nufft<T> {                                                                    \
+    nufft(std::size_t n_modes, double eps = 1e-6, int device = -1)                                 \
+        : impl(::fourier::c::fourier_hip_nufft_create_##SUFFIX(n_modes, eps, device),              \
+               ::fourier::c::fourier_hip_nufft_destroy_##SUFFIX) {}                                \
+    nufft() = delete;                                                                              \
+    nufft(const nufft &) = delete;                                                                 \
+    nufft(nufft &&) = default;                                                                     \
+    nufft &operator=(const nufft &) = delete;                                                      \
+    nufft &operator=(nufft &&) = default;                                                          \
+    ~nufft() = default;                                                                            \
+    std::size_t modes() const { return ::fourier::c::fourier_hip_nufft_modes_##SUFFIX(impl.get()); }\
+    std::size_t points() const { return ::fourier::c::fourier_hip_nufft_points_##SUFFIX(impl.get()); }\
+    /* m doubles on the HOST; a set-up call that waits for `stream` */                             \
+    int set_points(const double *h_points, std::size_t m, void *stream = nullptr) {                \
+      return ::fourier::c::fourier_hip_nufft_set_points_##SUFFIX(impl.get(), h_points, m, stream); \
+    }                                                                                              \
+    /* type 1: `batch` rows of points() strengths -> `batch` rows of modes() */                    \
+    int to_modes_device(const void *d_in, void *d_out, std::size_t batch, int sign = -1,           \
+                        int order = 0, void *stream = nullptr) const {                             \
+      return ::fourier::c::fourier_hip_nufft_to_modes_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    /* type 2: `batch` rows of modes() -> `batch` rows of points() values */                       \
+    int to_points_device(const void *d_in, void *d_out, std::size_t batch, int sign = 1,           \
+                         int order = 0, void *stream = nullptr) const {                            \
+      return ::fourier::c::fourier_hip_nufft_to_points_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_nufft_reserve_##SUFFIX(impl.get(), batch);                  \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_nufft_set_option_##SUFFIX(impl.get(), key, value);          \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_nufft_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_nufft_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_nufft_##SUFFIX,                                        \
+                      void (*)(::fourier::c::fourier_nufft_##SUFFIX *)> impl;                      \
+  };
+FOURIER_DEFINE_CXX_NUFFT_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_NUFFT_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_NUFFT_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
