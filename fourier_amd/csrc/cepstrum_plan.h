@@ -1,5 +1,7 @@
 // cepstrum_plan.h -- the plan behind a cepstrum handle (fourier_hip_cepstrum_*, include/fourier.h): batched rows of n reals,
-// zero-extended to a transform length L >= n; with X = fft(x, L) and the per-call reals log_mult != 0 and log_floor >= 0
+// zero-extended to a transform length L >= n; with X = fft(x, L) and the per-call reals log_mult != 0 and log_floor >= 0 (log_mult
+// finite and not 0 AFTER rounding to T, a positive log_floor a normal number of T after rounding: anything else is an invalid
+// argument; every such floor is honoured, also where its square leaves T)
 //   g[k] = log_mult ln(max(|X[k]|, log_floor)), formed as 0.5 log_mult ln(max(re^2 + im^2, log_floor^2)) with the accurate logarithm
 //   mode CEPSTRUM (0):       c = ifft(g), real and even;  out = c[0 .. m),  m <= L
 //   mode MINIMUM_PHASE (1):  chat[0] = c[0], chat[q] = 2 c[q] for 0 < q < L/2 (odd L: q <= (L - 1) / 2), chat[L/2] = c[L/2] (even L),
@@ -24,6 +26,7 @@
 // launch: at f32 their last bits differ between even and odd rows, DESIGN.md section 4, "Cross-correlation").
 #pragma once
 #include <cmath>
+#include <limits>
 
 #include "plan.h"
 #include "real_plan.h"
@@ -95,17 +98,29 @@ template <typename T> class CepstrumPlan : public HandleBase {
     const int INVALID = ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
     if (!std::isfinite(log_mult) || log_mult == 0) throw EngineError(INVALID, "log_mult is finite and not 0");
     if (!std::isfinite(log_floor) || log_floor < 0) throw EngineError(INVALID, "log_floor is finite and not negative");
+    // in T too: the kernels work with the rounded values, and a floor that rounds to 0 would silently mean "no floor"
+    const T lm = (T)log_mult, fl = (T)log_floor;
+    if (!std::isfinite(lm) || lm == (T)0) throw EngineError(INVALID, "log_mult is finite and not 0 in the handle's precision");
+    if (log_floor > 0 && !std::isnormal(fl)) throw EngineError(INVALID, "a positive log_floor is a normal number of the handle's precision");
     check_buffers(d_in, d_out, batch * n_ * sizeof(T), batch * m_ * sizeof(T), sizeof(T), m_ == n_);
     if (batch == 0) return;
     DeviceGuard g(device_);
     const size_t chunk = prepare(batch);
     const T* in = (const T*)d_in;
     T* out = (T*)d_out;
-    const T lm = (T)log_mult, fl = (T)log_floor;
-    const double floor2 = (double)(fl * fl);  // computed in T
+    // Every normal floor is honoured whatever its square does in T: where fl * fl is no normal number the kernels get it clamped
+    // and take the value of a bin below it from here, rounded to T once (CepstrumFloor, kernel_args.h); where it is one, their
+    // arithmetic is what it always was
+    const T sq = fl * fl;  // computed in T
+    CepstrumFloor floor{(double)sq, 0.0, 0u};
+    if (fl > (T)0 && !std::isnormal(sq)) {
+      floor.floor2 = (double)std::max(sq, std::numeric_limits<T>::min());
+      floor.ln_floor = std::log((double)fl);
+      floor.given = 1u;
+    }
     if (route_ == ONE_LAUNCH) {  // one workgroup a row: launches of less than 2^31 workgroups
       for_chunks(batch, launch_items_, [&](size_t c0, size_t nb) {
-        plan_->exec_cepstrum(in + c0 * n_, out + c0 * m_, nb, n_, m_, mode_, (double)lm, floor2, stream);
+        plan_->exec_cepstrum(in + c0 * n_, out + c0 * m_, nb, n_, m_, mode_, (double)lm, floor, stream);
       });
       return;
     }
@@ -123,13 +138,13 @@ template <typename T> class CepstrumPlan : public HandleBase {
       if (n_ != l_ || (uintptr_t)src % ELEM) { window_sweep(XCORR_PAD, src, pad, nb, stream); src = pad; }
       const bool direct = m_ == l_ && (uintptr_t)oc % ELEM == 0;
       rplan_->run_forward(src, sx, nb, FWD, stream);
-      sweep(CEPSTRUM_LOG, sx, nb, spec * ELEM, (double)lm, floor2, inv_l, stream);
+      sweep(CEPSTRUM_LOG, sx, nb, spec * ELEM, (double)lm, floor, inv_l, stream);
       const bool last = mode_ == CEPSTRUM;
       rplan_->run_inverse(sx, last && direct ? (void*)oc : (void*)rr, nb, INV, stream);
       if (!last) {
-        sweep(CEPSTRUM_FOLD, rr, nb, l_ * sizeof(T), 0.0, 0.0, 1.0, stream);
+        sweep(CEPSTRUM_FOLD, rr, nb, l_ * sizeof(T), 0.0, CepstrumFloor{}, 1.0, stream);
         rplan_->run_forward(rr, sx, nb, FWD, stream);
-        sweep(CEPSTRUM_EXP, sx, nb, spec * ELEM, 0.0, 0.0, inv_l, stream);
+        sweep(CEPSTRUM_EXP, sx, nb, spec * ELEM, 0.0, CepstrumFloor{}, inv_l, stream);
         rplan_->run_inverse(sx, direct ? (void*)oc : (void*)rr, nb, INV, stream);
       }
       if (!direct) window_sweep(XCORR_WINDOW, rr, oc, nb, stream);
@@ -148,7 +163,7 @@ template <typename T> class CepstrumPlan : public HandleBase {
 
   // one of the three in-place sweeps over nb rows of `row` bytes, in launches of whole rows of at most REAL_LAUNCH_BYTES (never less
   // than one row)
-  void sweep(int which, void* data, size_t nb, size_t row, double log_mult, double floor2, double scale, hipStream_t stream) const {
+  void sweep(int which, void* data, size_t nb, size_t row, double log_mult, const CepstrumFloor& floor, double scale, hipStream_t stream) const {
     const size_t vs = which == CEPSTRUM_FOLD ? sizeof(T) : ELEM;
     const size_t per = std::max<size_t>(1, launch_bytes_ / row);
     for (size_t r0 = 0; r0 < nb; r0 += per) {
@@ -159,7 +174,7 @@ template <typename T> class CepstrumPlan : public HandleBase {
       a.total = (uint32_t)(rows * (row / vs));
       divider(a.l, a.div_m, a.div_l);
       a.bytes = (uint32_t)(rows * row);
-      a.log_mult = log_mult; a.floor2 = floor2; a.scale = scale;
+      a.log_mult = log_mult; a.floor2 = floor.floor2; a.g_floor = log_mult * floor.ln_floor / (double)l_; a.floor_given = floor.given; a.scale = scale;
       FOURIER_LAUNCH(get_cepstrum_kernel(Real<T>{}, which), (a.total + 255) / 256, 256, 0, stream, a);
     }
   }

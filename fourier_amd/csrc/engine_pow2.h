@@ -332,8 +332,9 @@ template <typename T> class Pow2Engine {
     cepstrum_small_[mode] = k;
     return true;
   }
-  // in: `batch` rows of n <= n_ reals; out: rows of m <= n_ reals, in == out allowed where m == n; floor2 = log_floor^2 in T
-  void run_cepstrum_small(const void* in, void* out, size_t batch, uint32_t n, uint32_t m, int mode, double log_mult, double floor2,
+  // in: `batch` rows of n <= n_ reals; out: rows of m <= n_ reals, in == out allowed where m == n; fl: the floor as the kernels
+  // take it (CepstrumFloor, kernel_args.h)
+  void run_cepstrum_small(const void* in, void* out, size_t batch, uint32_t n, uint32_t m, int mode, double log_mult, const CepstrumFloor& fl,
                           hipStream_t stream, unsigned nxcd) const {
     if (batch == 0) return;
     const Pass& ps = *passes_[0];
@@ -342,7 +343,7 @@ template <typename T> class Pow2Engine {
     a.in = in; a.out = out;
     a.tw1 = ps.st->tw1.p; a.tw2 = ps.st2->tw1.p;
     a.tw_lo = ps.tw_lo.p; a.tw_hi = ps.tw_hi.p;
-    a.cp_n = n; a.cp_m = m; a.cp_log_mult = log_mult; a.cp_floor2 = floor2;
+    a.cp_n = n; a.cp_m = m; a.cp_log_mult = log_mult; a.cp_floor2 = fl.floor2; a.cp_g_floor = log_mult * fl.ln_floor / (double)n_; a.cp_floor_given = fl.given;
     a.n = n_; a.scale = 1.0; a.nxcd = nxcd & 0xff; a.total_cols = batch;
     const KernelInfo& k = cepstrum_small_[mode];
     launch(nullptr, 0, k.fn, batch, k.NT, k.smem, stream, a);

@@ -82,9 +82,12 @@ struct PassArgs {
   const void* dl_weights;
   uint32_t dl_n;
   // cepstrum_small_kernel (CepstrumPlan, cepstrum_plan.h): rows of cp_n reals in, rows of cp_m reals out;
-  // g = 0.5 cp_log_mult ln(max(|X|^2, cp_floor2)), cp_floor2 = log_floor^2 computed in T
+  // g = 0.5 cp_log_mult ln(max(|X|^2, cp_floor2)), cp_floor2 = log_floor^2 computed in T.  Where that square is no normal number
+  // of T, cp_floor_given is 1, cp_floor2 is the square clamped to [min normal, +inf] and a bin below it takes the finished value
+  // cp_g_floor = cp_log_mult ln(log_floor) / N, computed in double on the host
   uint32_t cp_n, cp_m;
-  double cp_log_mult, cp_floor2;
+  uint32_t cp_floor_given;
+  double cp_log_mult, cp_floor2, cp_g_floor;
 };
 
 
@@ -541,17 +544,28 @@ struct DelayArgs {
 
 // ---- cepstrum and minimum phase (kernels_cepstrum.h; CepstrumPlan, cepstrum_plan.h): the composed route's three sweeps, all in place,
 // one lane per value over a flat index; byte offsets are 32-bit (at most REAL_LAUNCH_BYTES per launch).
-// cepstrum_log_kernel: `total` half-spectrum values X -> {0.5 log_mult ln(max(|X|^2, floor2)) * scale, 0}.
+// cepstrum_log_kernel: `total` half-spectrum values X -> {0.5 log_mult ln(max(|X|^2, floor2)) * scale, 0}; floor_given = 1: a value
+// below floor2 takes the finished value g_floor (CepstrumFloor below).
 // cepstrum_fold_kernel: rows of l reals c -> chat: weight 1 at 0 and (even l) at l / 2, 2 below l / 2, 0 above.
 // cepstrum_exp_kernel: `total` half-spectrum values C -> exp(Re C) (cos Im C, sin Im C) * scale.
 enum { CEPSTRUM_LOG = 0, CEPSTRUM_FOLD = 1, CEPSTRUM_EXP = 2 };
+// The floor of one call as the logarithm kernels of both routes take it.  log_floor == 0, or log_floor^2 a normal number of T:
+// floor2 is that square computed in T and given is 0 -- ln(floor2) is taken on the device.  Otherwise (the square underflows or
+// overflows T) floor2 is the square clamped to [min normal, +inf], ln_floor = ln(log_floor) computed in double, given is 1; a launch
+// hands its kernel log_mult ln_floor / L, the value of a bin below the floor, rounded to T once.
+struct CepstrumFloor {
+  double floor2, ln_floor;
+  uint32_t given;
+};
 struct CepstrumArgs {
   void* data;
   uint32_t l;                 // fold: values per row
   uint32_t total;             // values of this launch
   uint32_t div_m, div_l;      // fold: idx / l = (umulhi(idx, div_m) + idx) >> div_l
   uint32_t bytes;             // descriptor range of this launch
+  uint32_t floor_given;       // log: 1 where floor2 is the clamped square and g_floor the value of a bin below it
   double log_mult, floor2;    // log: log_floor^2, computed in T
+  double g_floor;             // log: log_mult ln(log_floor) / l from the host, read where floor_given
   double scale;               // log, exp: the inverse's 1 / l, computed in T
 };
 

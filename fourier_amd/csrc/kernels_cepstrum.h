@@ -6,7 +6,10 @@
 //                  E[k] = exp(Re C[k]) (cos Im C[k], sin Im C[k]),  h = Re ifft(E),  out = h[0 .. m)
 // (scipy.signal.minimum_phase(method="homomorphic") with the caller's floor and, at even L, weight 1 at quefrency L/2).
 // The floor is applied as `p < f ? f : p`: a NaN bin stays NaN.  log_floor == 0 on a bin that is exactly 0 gives -inf: that row's
-// output is not finite, and nothing else is touched -- no value of a row enters an address.
+// output is not finite, and nothing else is touched -- no value of a row enters an address.  A positive floor whose square is no
+// normal number of T arrives clamped, with the value of a bin below it from the host (cepstrum_g): below sqrt(min normal) every bin whose
+// re^2 + im^2 is less than the smallest normal number -- a zero row, a bin that flushed to zero -- gives log_mult ln(log_floor); above
+// sqrt(max) every bin whose re^2 + im^2 is finite does.
 //
 // cepstrum_small_kernel: the whole chain in ONE launch for L = L1 x L2 = 2^11 ... 2^15 (f64: ... 2^14) on delay_small_kernel's
 // skeleton (kernels_delay.h): its load (n reals, zeros above, the f32 `pairs` rule), forward core, every register -> {g / N, 0} with
@@ -34,10 +37,14 @@ __device__ __forceinline__ double cepstrum_ln(double x) { return log(x); }
 __device__ __forceinline__ float cepstrum_exp(float x) { return expf(x); }
 __device__ __forceinline__ double cepstrum_exp(double x) { return exp(x); }
 
-// half * ln(max(re^2 + im^2, floor2)), half = 0.5 log_mult (times the inverse's 1 / L)
-template <typename T> __device__ __forceinline__ T cepstrum_g(cpx<T> X, T half, T floor2) {
+// half * ln(max(re^2 + im^2, floor2)), half = 0.5 log_mult (times the inverse's 1 / L).  given: floor2 is log_floor^2 clamped to
+// [min normal, +inf] and a bin below it takes g_floor, its finished value from the host (CepstrumFloor, kernel_args.h); the
+// arithmetic of a bin at or above the floor, and of every bin where the square itself is a normal number, is unchanged
+template <typename T> __device__ __forceinline__ T cepstrum_g(cpx<T> X, T half, T floor2, T g_floor, bool given) {
   const T p = X.re * X.re + X.im * X.im;
-  return half * cepstrum_ln(p < floor2 ? floor2 : p);
+  const bool under = p < floor2;
+  const T g = half * cepstrum_ln(under ? floor2 : p);
+  return under && given ? g_floor : g;
 }
 
 // exp(re) (cos im, sin im) * scale
@@ -85,11 +92,12 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
   }
   twolevel_core<T, L1, L2>(x, tid, smem, (const cpx<T>*)a.tw1, (const cpx<T>*)a.tw2, (const cpx<T>*)a.tw_lo, 0);
   {  // X -> {g / N, 0}, then the inverse's leading swap
-    const T half = (T)a.cp_log_mult * ((T)0.5 / (T)N), floor2 = (T)a.cp_floor2;
+    const T half = (T)a.cp_log_mult * ((T)0.5 / (T)N), floor2 = (T)a.cp_floor2, g_floor = (T)a.cp_g_floor;
+    const bool given = a.cp_floor_given != 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) x[v][r] = {(T)0, cepstrum_g<T>(x[v][r], half, floor2)};
+      for (int v = 0; v < VEC; ++v) x[v][r] = {(T)0, cepstrum_g<T>(x[v][r], half, floor2, g_floor, given)};
   }
   __syncthreads();
   {
@@ -171,7 +179,7 @@ __global__ void __launch_bounds__(REAL_THREADS) cepstrum_log_kernel(CepstrumArgs
   const BufRsrc r = make_rsrc(a.data, a.bytes);
   const cpx<T> X = real_load<T>(r, idx * E);
   const T half = (T)a.log_mult * (T)0.5 * (T)a.scale;
-  buf_store_elem<T, BUF_NT>(r, idx * E, cpx<T>{cepstrum_g<T>(X, half, (T)a.floor2), (T)0});
+  buf_store_elem<T, BUF_NT>(r, idx * E, cpx<T>{cepstrum_g<T>(X, half, (T)a.floor2, (T)a.g_floor, a.floor_given != 0), (T)0});
 }
 
 // rows of l reals in place: c -> chat

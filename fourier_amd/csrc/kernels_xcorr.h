@@ -54,6 +54,20 @@ template <typename T> __device__ __forceinline__ int xcorr_exponent(T peak) {
   return e - 1;
 }
 
+// xcorr_phat for spectra of any amplitude (the composed route, whose rows are not balanced): each value is first scaled by the power
+// of two that brings its larger component into [1, 2), so that re^2 + im^2 neither overflows nor vanishes wherever X and Y are
+// normal numbers.  A power of two changes no bit of the square root or of the quotients while nothing leaves the normal range: the
+// result is the unscaled one's bit for bit wherever that one was right.  A zero component stays zero, a zero value gives 0, and a
+// component that is not finite leaves the value as it is (xcorr_exponent returns 0).
+template <typename T> __device__ __forceinline__ cpx<T> xcorr_unit_scale(cpx<T> X) {
+  const T ar = X.re < (T)0 ? -X.re : X.re, ai = X.im < (T)0 ? -X.im : X.im;
+  const int e = xcorr_exponent(ar > ai ? ar : ai);
+  return cpx<T>{(T)ldexp(X.re, -e), (T)ldexp(X.im, -e)};
+}
+template <typename T> __device__ __forceinline__ cpx<T> xcorr_phat_any(cpx<T> X, cpx<T> Y) {
+  return xcorr_phat<T>(xcorr_unit_scale<T>(X), xcorr_unit_scale<T>(Y));
+}
+
 // G[k] / N from Z[k] = (a, b) and Z[(N - k) mod N] = (c, d), with the inverse's leading swap re <-> im
 template <typename T, bool PHAT, int N> __device__ __forceinline__ cpx<T> xcorr_untangle_swapped(T a, T b, T c, T d) {
   if constexpr (PHAT) {
@@ -262,7 +276,7 @@ __global__ void __launch_bounds__(REAL_THREADS) xcorr_mul_kernel(XcorrArgs a) {
   const BufRsrc rx = make_rsrc(a.in, a.in_bytes), ry = make_rsrc(a.in2, a.in_bytes), rout = make_rsrc(a.out, a.out_bytes);
   const cpx<T> X = real_load<T>(rx, idx * E), Y = real_load<T>(ry, idx * E);
   cpx<T> g;
-  if constexpr (PHAT) g = xcorr_phat<T>(X, Y);
+  if constexpr (PHAT) g = xcorr_phat_any<T>(X, Y);
   else g = cpx<T>{X.re * Y.re + X.im * Y.im, X.re * Y.im - X.im * Y.re};
   const T s = (T)a.scale;
   buf_store_elem<T, BUF_NT>(rout, idx * E, cpx<T>{g.re * s, g.im * s});

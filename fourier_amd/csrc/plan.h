@@ -630,17 +630,17 @@ template <typename T> class Plan : public HandleBase {
 
   // ---- the hook of the cepstrum handle (CepstrumPlan, cepstrum_plan.h); exec() is not affected.  A one-launch two-level plan of L
   // points (2^11 ... 2^15, f64 ... 2^14) runs `batch` rows of n <= L reals in one launch of cepstrum_small_kernel: mode 0 the real
-  // cepstrum, mode 1 the minimum-phase row; rows of m <= L reals out, d_out == d_in allowed where m == n.  floor2 is log_floor^2 in T.
+  // cepstrum, mode 1 the minimum-phase row; rows of m <= L reals out, d_out == d_in allowed where m == n.  fl: CepstrumFloor, kernel_args.h.
   // The caller keeps `batch` below 2^31.
   bool enable_cepstrum(int mode) {
     if (blu_ || !eng_) return false;
     DeviceGuard g(device_);
     return eng_->enable_cepstrum_small(mode);
   }
-  void exec_cepstrum(const void* d_in, void* d_out, size_t batch, size_t n, size_t m, int mode, double log_mult, double floor2,
+  void exec_cepstrum(const void* d_in, void* d_out, size_t batch, size_t n, size_t m, int mode, double log_mult, const CepstrumFloor& fl,
                      hipStream_t stream) const {
     DeviceGuard g(device_);
-    eng_->run_cepstrum_small(d_in, d_out, batch, (uint32_t)n, (uint32_t)m, mode, log_mult, floor2, stream, nxcd_);
+    eng_->run_cepstrum_small(d_in, d_out, batch, (uint32_t)n, (uint32_t)m, mode, log_mult, fl, stream, nxcd_);
   }
 
   // ---- the hook of the chirp-z handle (CztPlan, czt_plan.h); exec() is not affected.  A one-launch two-level plan of L points

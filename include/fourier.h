@@ -90,7 +90,10 @@ enum {
  * (FLT_MAX = 2^128 (1 - 2^-24), DBL_MAX = 2^1024 (1 - 2^-53)) and is pinned by tests/amplitude_cases.py:
  *   linear entry points  (the transforms of every handle, convolution in the signal and in the filter, STFT / MDCT / filter banks /
  *                        resampling / chirp-z / analytic signal and their inverses): f(2^k x) = 2^k f(x) BIT FOR BIT while every input,
- *                        intermediate and output stays a normal number of T -- a power of two changes exponents only.
+ *                        intermediate and output stays a normal number of T -- a power of two changes exponents only.  So do
+ *                        fourier_hip_xcorr_* without weighting in x and in y (bilinear: both scaled, 2^2k; x by 2^k and y by 2^-k, no bit
+ *                        changes), fourier_hip_delay_* in the rows and in the weights (never the delays), fourier_hip_convnd_* in the
+ *                        items and in the taps, fourier_hip_nufft_* in the strengths (type 1) and the modes (type 2) (never the points).
  *   power and Welch      (fourier_hip_spectrogram_* at power 2 and welch, fourier_hip_csd_csd_*, the band sums of fourier_hip_bandspec_*):
  *                        scale by exactly 2^2k under the same condition; |X|^2 = re^2 + im^2 and every sum of it (over frames, over the
  *                        bins of a band) must be representable: |X| < sqrt(FLT_MAX) ~ 2^64 (f64: sqrt(DBL_MAX) ~ 2^512).
@@ -104,6 +107,15 @@ enum {
  *                        Cauchy-Schwarz).  |X[b, f, k]| <= max |x| * sum_j |w_j|, so frames * (max |x| * sum |w|)^2 < FLT_MAX is
  *                        sufficient: with a Hann window of 2048 samples and 1000 frames, max |x| < 5.7e14 in f32 -- neither their
  *                        product nor the square of a cross sum is formed (see fourier_hip_csd_coherence_*).
+ *   GCC-PHAT             (fourier_hip_xcorr_* under weighting 1) is degree 0 in x and in y: bit-identical under a power-of-two scaling
+ *                        of either input for EVERY input whose values are normal numbers of T, on every route -- each spectrum value
+ *                        is brought to a larger component in [1, 2) by a power of two before its magnitude is formed (the one-launch
+ *                        route scales whole rows instead), so re^2 + im^2 cannot leave the format.  The tests pin it with x 2^k against
+ *                        y 2^-k at k = +-100 (f64 +-900) and with the largest spectrum value in [2^61, 2^62) (f64 [2^509, 2^510)).
+ *   cepstrum             (fourier_hip_cepstrum_*) has NO exact scaling, a logarithm lies between input and output: scaling x by 2^k
+ *                        moves c[0] by k log_mult ln 2 and h by 2^(k log_mult) within the family's error bound, for
+ *                        sqrt(min normal) < |X| < sqrt(max) (re^2 + im^2 is formed in T).  Its floor is honoured for every normal
+ *                        log_floor, whatever log_floor^2 does in T.
  * Subnormal values may be flushed to zero by the device; nothing above holds where one appears. */
 
 /* Create a plan on a specific device (-1 = current device).  Same plan factory as `create_fft_f32/f64`
@@ -1482,8 +1494,10 @@ int fourier_hip_resample_last_status_double(const FOURIER_STRUCT fourier_resampl
  *                       sweep forms G psi / L, the unscaled inverse follows -- straight into the caller's output where the window is
  *                       the whole row (lag_first == 0, lags == L) --, and a last sweep stores the window.  Complex rows have no
  *                       one-launch route.
- * On every route power-of-two scaling of either input scales the unweighted output exactly and leaves the PHAT output bit-identical
- * while nothing over- or underflows.
+ * On every route power-of-two scaling of either input scales the unweighted output exactly while nothing over- or underflows, and
+ * leaves the PHAT output bit-identical for every input whose values are normal numbers of T: the composed route brings every
+ * spectrum value X[k], Y[k] to a larger component in [1, 2) by a power of two before it forms |X[k]|, |Y[k]| and the quotients, which
+ * changes no bit of them while re^2 + im^2 is normal and keeps them right where it would have left the format ("Amplitude" above).
  * Option "fusion" (fourier_hip_xcorr_set_option_*): 1 = the one-launch route where it exists, the DEFAULT (it took 0.23 - 0.37 of the
  * composed route's time at every measured shape), 0 = the composed route.  The plan owns a scratch of at most
  * 1 GiB (never less than one row pair) and walks larger batches in chunks of it; the first call with a batch larger than any before
@@ -1617,12 +1631,19 @@ int fourier_hip_delay_last_status_double(const FOURIER_STRUCT fourier_delay_doub
  * log_floor == 0 on a bin that is exactly 0 gives -inf there: that row's output is not finite, nothing else is touched, and it is
  * not an error.  No value of a row enters an address.  A NaN in a row makes that row's output NaN.
  * Amplitude range: re^2 + im^2 must neither overflow nor flush to zero in T, so sqrt(min normal) < |X[k]| < sqrt(max):
- * 1.1e-19 .. 1.8e19 in float, 1.5e-154 .. 1.3e154 in double (a bin below the range counts as 0: the floor, or -inf).  Scaling x by
+ * 1.1e-19 .. 1.8e19 in float, 1.5e-154 .. 1.3e154 in double (a bin below the range counts as 0: the floor, or -inf).  The FLOOR is
+ * not bound by that range: every log_floor > 0 that is a normal number of T is honoured, whatever log_floor^2 does in T.  A bin whose
+ * re^2 + im^2 is below log_floor^2 gives log_mult ln(log_floor) -- below sqrt(min normal) that is every bin whose re^2 + im^2 is
+ * less than the smallest normal number, a zero row and a bin that flushed to zero included; above sqrt(max) it is every bin whose
+ * re^2 + im^2 is finite.  Where log_floor^2 is a normal number of T the arithmetic is ln(max(re^2 + im^2, log_floor^2)) as written
+ * above.  (In mode 1 a floored row gives h[0] = log_floor^log_mult, which must itself fit T: exp(Re C) / L is formed in T.)  Scaling x by
  * 2^j moves c[0] by j log_mult ln 2 and h by 2^(j log_mult): bit-exact power-of-two scaling is NOT claimed for this family.
  * The phase of E goes through one accurate sincospi of Im C / pi, the exponential is the accurate one.
  * n == 0, n > L, m == 0, m > L, a mode other than 0 / 1 make create fail; so does L * 2 * sizeof(T) > 2^31 - 1 (as
- * fourier_hip_hilbert_create_*).  log_mult == 0, a log_mult or log_floor that is not finite, log_floor < 0, a NULL buffer, a buffer not
- * aligned to sizeof(T), and an overlap of input and output other than d_out == d_in with m == n give FOURIER_HIP_INVALID_ARGUMENT.
+ * fourier_hip_hilbert_create_*).  log_mult == 0, a log_mult or log_floor that is not finite, log_floor < 0 -- and, AFTER ROUNDING TO T,
+ * a log_mult that is 0 or not finite (float: 1e-50, 1e60) or a log_floor > 0 that is 0, subnormal or inf (float: 1e-200, 1e-40, 1e39)
+ * --, a NULL buffer, a buffer not aligned to sizeof(T), and an overlap of input and output other than d_out == d_in with m == n give
+ * FOURIER_HIP_INVALID_ARGUMENT and write nothing.  log_floor == 0 keeps meaning "no floor".
  * batch == 0 is a successful no-op.  Stream-ordered on `stream` like fourier_hip_transform_batch_*.
  * Routes (fourier_hip_cepstrum_describe_* begins with the route's name):
  *   "cepstrum one-launch"  L = 2^11 ... 2^15 (double: ... 2^14) where the library holds a kernel of the mode: load, FFT, logarithm,

@@ -13,23 +13,42 @@ show (a silent fall-back fails there), the degree d of the output in the input a
 a seeded numpy generator, a runner through the handle's *_ptr entry point and the family's f64 truth (tests/*_truth.py, numpy for the
 core).  Shapes are the smallest that reach each kernel family (a partly empty last tile, more than one workgroup), batch 3, f32 and f64.
 
+The families: the core plans, real / N-D / strided-axis / DCT-DST transforms, circular and linear convolution, STFT, MDCT, the filter
+banks, resampling, chirp-z, analytic signal and envelope, power / magnitude / Welch spectrogram, cross spectrum and coherence, band
+spectrogram; cross-correlation and GCC-PHAT, fractional delay and delay-and-sum, N-D convolution, the non-uniform FFT, cepstrum and
+minimum phase.  The last five state their own conditions on the inputs (kappa of the PHAT and cepstrum rows, the f64 model of the
+NUFFT) and assert them before anything runs.
+
 Assertions (a test prints its worst figures in one line, then asserts every one of them):
   (a) exact scaling   with y0 = f(x): f(2^k x) is BIT-equal to 2^(k d) y0 over the whole output.  2^k x is formed in the working
                       precision, which is exact.  k by precision and degree is K below; these k keep every input, table product and
                       output of the cases normal with a wide margin, so a device that flushes subnormals changes nothing.
                       d = 1: the linear entry points; d = 2: power spectrogram, Welch, cross spectrum, band sums of powers; d = 0: the
-                      coherence, whose k go past the point (2^28 in f32) where a product of two summed powers leaves the format.
+                      coherence, whose k go past the point (2^28 in f32) where a product of two summed powers leaves the format, and
+                      GCC-PHAT.  The bilinear cross-correlation also runs as the kind "opposite": x 2^k against y 2^-k at the k of
+                      OPPOSITE, +-40 and +-100 (f64 +-300, +-900), net degree 0, so no bit of the output may change; 2^100 squared
+                      is beyond FLT_MAX, which is what GCC-PHAT's composed route has to survive there.
   (b) truth           at k = 0 and at the largest and the smallest k of (a): relative L2 against the truth of the scaled, rounded input
                       within the tolerance the family's own GPU test grants (restated below from each tol(); none is new -- relative L2
                       does not change with scale).  A band spectrogram under the log has no degree: exp(out / log_mult) against
-                      maximum(truth, floor) with the floor the median of the truth, the rule of tests/bandspec_cases.py.
+                      maximum(truth, floor) with the floor the median of the truth, the rule of tests/bandspec_cases.py.  The cepstrum
+                      and the minimum-phase row have none either: tests/cepstrum_truth.py's err, which divides by kappa and does not
+                      move with scale, at k = +-40 / +-300 under tests/cepstrum_cases.py's bound, and at EVERY k the identity that
+                      the truths satisfy exactly -- c(2^k x) - k log_mult ln 2 at quefrency 0 against c(x), 2^(-k log_mult) h(2^k x)
+                      against h(x) -- in the same measure under TWICE that bound (two results, each within one bound of its truth).
   (c) integers        f32 only: round(sigma gauss) clipped to the integer type -- sigma 2^13 as int16, 2^21 as int24, 2^28 as int32 --
                       through the power, magnitude and Welch spectrograms, cross spectrum and coherence, the band spectrogram in dB, the
-                      envelope and the real transform, against the truth under the same tolerances; and two full-scale 24-bit tones
+                      envelope and the real transform, the cross-correlation (x alone; x and y, where int32 x int32 x n reaches
+                      about 2^67), the delay, the N-D convolution's items, the NUFFT's strengths and modes (pairs of integers) and
+                      the cepstrum (not the minimum-phase row, whose input is a filter), against the truth under the same
+                      tolerances, every output finite; and two full-scale 24-bit tones
                       (two_tone below), whose coherence must be finite and within tolerance in the bins that hold the tone.
   (d) range edges     spectrogram magnitude and envelope are sqrt(re^2 + im^2): |X|^2 must be representable, |X| < sqrt(FLT_MAX) ~ 2^64
                       (f64: 2^512).  With k chosen so that max |y0| 2^k lies in [2^61, 2^62) (f64 [2^509, 2^510)) the output is finite
-                      and exactly scaled.  The edge is derived from the format, not measured; include/fourier.h states it."""
+                      and exactly scaled.  The edge is derived from the format, not measured; include/fourier.h states it.  GCC-PHAT
+                      and the cepstrum form re^2 + im^2 of the SPECTRUM: k places the largest |X[k]| of the scaled inputs' f64
+                      spectra there; the PHAT output is bit-identical to k = 0 and finite, the cepstrum finite and within its bound.
+                      Nothing is asserted at the lower edge: single bins of a spectrum can be arbitrarily small."""
 import math
 import re
 import types
@@ -37,21 +56,31 @@ import types
 import numpy as np
 
 import bandspec_truth
+import cepstrum_cases
+import cepstrum_truth
+import convnd_cases
+import convnd_truth
 import csd_truth
 import czt_truth
+import delay_cases
+import delay_truth
 import hilbert_truth
 import ipfb_truth
 import mdct_truth
+import nufft_cases
+import nufft_truth
 import pfb_truth
 import r2r_truth
 import resample_truth
 import spectrogram_truth
 import stft_truth
+import xcorr_truth
 from helpers import rel_l2
 
 BATCH = 3
 K = {"f32": {1: (-40, 40), 2: (-24, 24), 0: (-24, 24, 28, 40)},
      "f64": {1: (-300, 300), 2: (-150, 150), 0: (-150, 150)}}
+OPPOSITE = {"f32": (-100, -40, 40, 100), "f64": (-900, -300, 300, 900)}  # (a), kind "opposite": x 2^k against y 2^-k
 EDGE = {"f32": 61, "f64": 509}                       # (d): the binary exponent of the largest scaled magnitude
 INTEGERS = ((13, 16), (21, 24), (28, 32))            # (c): log2 sigma, bits of the integer type
 LOG_MULT = 10.0 / math.log(10.0)                     # dB of a power
@@ -156,22 +185,37 @@ class Case:
     """name; d: the degree (None: no exact scaling, `kd` picks the k of (b)); make(api, real) -> ctx with .plan; routes(real) ->
     ((options, describe prefix or compiled pattern), ...); inputs(ctx, rng) -> unit-variance f64 / c128 arrays; scaled: the inputs
     that carry the amplitude; run(api, ctx, ins) -> numpy; truth(ctx, ins) -> f64; pick(ctx, out): the part of out the truth covers;
-    err(ctx, out, want): the figure held against tol(describe, real)"""
+    err(ctx, out, want): the figure held against tol(describe, real), or against bound(ctx, describe, real) where the family's bound
+    depends on the inputs or on where the handle runs.
+    signs: input -> +1 / -1, the sign of the exponent that input takes (the kind "opposite": x 2^k, y 2^-k; d counts the output's
+    net degree, 0 there); ks: the exponents by precision where they are not K's; conditions(ctx, ins): the family's conditions on
+    its inputs, asserted before anything runs; identity(ctx, k, scaled output, unscaled output, ins) -> a figure held against TWICE
+    the bound at every k (a family with d = None whose truths scale by a known rule: the triangle inequality over two results);
+    edge_of(ctx, ins, y0): the magnitude that (d) places at the range edge (default: the largest |y0|)"""
 
     def __init__(self, name, d, make, routes, inputs, run, truth, tol, scaled=None, pick=None, err=None, kd=None, integers=False,
-                 edge=False, describe=None):
+                 edge=False, describe=None, signs=None, ks=None, conditions=None, bound=None, identity=None, edge_of=None):
         self.name, self.d, self.make, self.inputs, self.run, self.truth, self.tol = name, d, make, inputs, run, truth, tol
         self.routes = routes if callable(routes) else (lambda real: routes)
         self.scaled, self.pick, self.err = scaled, pick or (lambda ctx, out: out), err or (lambda ctx, out, want: rel_l2(out, want))
         self.kd = d if kd is None else kd
         self.integers, self.edge = integers, edge
         self.describe = describe or (lambda ctx: ctx.plan.describe())
+        self.signs, self.ks_of = signs or {}, ks or (lambda real: K[real][self.kd])
+        self.conditions = conditions or (lambda ctx, ins: None)
+        self.bound = bound or (lambda ctx, d, real: self.tol(d, real))
+        self.identity = identity
+        self.edge_of = edge_of or (lambda ctx, ins, y0: float(np.max(np.abs(y0))))
 
     def unit_inputs(self, ctx):
         return self.inputs(ctx, np.random.default_rng(sum(self.name.encode())))
 
     def carries(self, i):
         return self.scaled is None or i in self.scaled
+
+    def at(self, ins, k):
+        """the inputs at amplitude 2^k: every input that carries it, by the sign of its exponent"""
+        return [scale(a, k * self.signs.get(i, 1)) if self.carries(i) else a for i, a in enumerate(ins)]
 
     def select(self, ctx, real, options, prefix):
         for key, value in options.items():
@@ -232,31 +276,46 @@ def check_scaling(api, case, real):
     """(a) and (b)"""
     ctx = case.make(api, real)
     ins = rounded(case.unit_inputs(ctx), real)
-    ks = K[real][case.kd]
+    case.conditions(ctx, ins)
+    ks = case.ks_of(real)
     rep = Report(f"{real} {case.name}, k = {', '.join(f'{k:+d}' for k in ks)}")
+    identity = (0.0, 0.0, 0.0, "")
     try:
         for options, prefix in case.routes(real):
             d = case.select(ctx, real, options, prefix)
             rep.route(d)
-            t = case.tol(d, real)
+            t = case.bound(ctx, d, real)
             y0 = case.run(api, ctx, ins)
             rep.figure(f"{opt(options)}k=0", case.err(ctx, case.pick(ctx, y0), case.truth(ctx, ins)), t)
             for k in ks:
-                sc = [scale(a, k) if case.carries(i) else a for i, a in enumerate(ins)]
+                sc = case.at(ins, k)
                 y = case.run(api, ctx, sc)
                 if case.d is not None:
                     rep.exact(f"{opt(options)}k={k:+d}", y, scale(y0, k * case.d))
+                if case.identity is not None:
+                    fig = case.identity(ctx, k, case.pick(ctx, y), case.pick(ctx, y0), ins)
+                    identity = max(identity, (fig / (2 * t), fig, 2 * t, f"{opt(options)}k={k:+d}"))
+                    rep.figure(f"{opt(options)}k={k:+d} against k=0", fig, 2 * t)
                 if k in (min(ks), max(ks)):
                     rep.figure(f"{opt(options)}k={k:+d}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, sc)), t)
     finally:
+        if identity[3]:
+            rep.notes.append(f"worst identity against k=0 {identity[1]:.3g} of {identity[2]:.3g} ({identity[3]})")
         rep.print()
     rep.check()
 
 
 def integer_samples(ins, case, log2_sigma, bits):
-    """round(sigma g) clipped to the integer type, as f32 (the inputs that carry no amplitude: rounded to f32 as they are)"""
+    """round(sigma g) clipped to the integer type, as f32 (the inputs that carry no amplitude: rounded to f32 as they are); complex
+    samples are a pair of integers"""
     lo, hi = -2.0 ** (bits - 1), 2.0 ** (bits - 1) - 1
-    return [np.ascontiguousarray((np.clip(np.rint(2.0 ** log2_sigma * a), lo, hi) if case.carries(i) else a).astype(np.float32))
+
+    def ints(a):
+        if np.iscomplexobj(a):
+            return ints(a.real) + 1j * ints(a.imag)
+        return np.clip(np.rint(2.0 ** log2_sigma * a), lo, hi)
+
+    return [np.ascontiguousarray((ints(a) if case.carries(i) else a).astype(np.complex64 if np.iscomplexobj(a) else np.float32))
             for i, a in enumerate(ins)]
 
 
@@ -271,11 +330,12 @@ def check_integers(api, case):
             rep.route(d)
             for log2_sigma, bits in INTEGERS:
                 ins = integer_samples(unit, case, log2_sigma, bits)
-                assert all(np.array_equal(a, np.rint(a)) for i, a in enumerate(ins) if case.carries(i))
+                assert all(np.array_equal(a.view(np.float32), np.rint(a.view(np.float32))) for i, a in enumerate(ins) if case.carries(i))
+                case.conditions(ctx, ins)
                 y = case.run(api, ctx, ins)
-                if not np.all(np.isfinite(y)):
-                    rep.failed.append((options, bits, f"{int(np.count_nonzero(~np.isfinite(y)))} non-finite"))
-                rep.figure(f"{opt(options)}int{bits}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, ins)), case.tol(d, "f32"))
+                if not np.all(np.isfinite(y.view(np.float32))):
+                    rep.failed.append((options, bits, f"{int(np.count_nonzero(~np.isfinite(y.view(np.float32))))} non-finite"))
+                rep.figure(f"{opt(options)}int{bits}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, ins)), case.bound(ctx, d, "f32"))
     finally:
         rep.print()
     rep.check()
@@ -285,20 +345,27 @@ def check_edge(api, case, real):
     """(d)"""
     ctx = case.make(api, real)
     ins = rounded(case.unit_inputs(ctx), real)
+    case.conditions(ctx, ins)
     rep = Report(f"{real} {case.name}, range edge")
     try:
         for options, prefix in case.routes(real):
-            rep.route(case.select(ctx, real, options, prefix))
+            d = case.select(ctx, real, options, prefix)
+            rep.route(d)
             y0 = case.run(api, ctx, ins)
-            k = EDGE[real] - int(math.floor(math.log2(float(np.max(np.abs(y0))))))
-            top = math.ldexp(float(np.max(np.abs(y0))), k)
+            largest = case.edge_of(ctx, ins, y0)
+            k = EDGE[real] - int(math.floor(math.log2(largest)))
+            top = math.ldexp(largest, k)
             assert 2.0 ** EDGE[real] <= top < 2.0 ** (EDGE[real] + 1), (k, top)
-            y = case.run(api, ctx, [scale(a, k) if case.carries(i) else a for i, a in enumerate(ins)])
+            sc = case.at(ins, k)
+            y = case.run(api, ctx, sc)
             bad = int(np.count_nonzero(~np.isfinite(y)))
             rep.notes.append(f"{opt(options)}k={k:+d}: largest 2^{math.log2(top):.2f}, {bad} non-finite")
             if bad:
                 rep.failed.append((options, k, f"{bad} non-finite"))
-            rep.exact(f"{opt(options)}k={k:+d}", y, scale(y0, k))
+            if case.d is not None:
+                rep.exact(f"{opt(options)}k={k:+d}", y, scale(y0, k * case.d))
+            else:  # no exact scaling: within the family's bound of the truth at this amplitude
+                rep.figure(f"{opt(options)}k={k:+d}", case.err(ctx, case.pick(ctx, y), case.truth(ctx, sc)), case.bound(ctx, d, real))
     finally:
         rep.print()
     rep.check()
@@ -835,6 +902,278 @@ def band_spectrogram(n_fft, hop, bands):
 
 
 band_spectrogram(256, 64, 20)
+
+
+# ---- the five newer handles.  One proxy serves the families whose cases are several handles at once (two lag windows, two accuracies):
+# set_option goes to every handle, or, for the key `pick`, chooses the one that describe() speaks for
+class Plans:
+    def __init__(self, plans, pick=None):
+        self.plans, self.pick, self.now = list(plans), pick, 0
+
+    def set_option(self, key, value):
+        if key == self.pick:
+            self.now = value
+            return
+        for p in self.plans:
+            p.set_option(key, value)
+
+    def describe(self):
+        return self.plans[self.now].describe()
+
+    @property
+    def plan(self):
+        return self.plans[self.now]
+
+
+# cross-correlation and GCC-PHAT: both lag windows of a shape in one case, the short one and the whole row (the direct store)
+def xcorr_windows(L):
+    return ((-5, 11), (0, L))
+
+
+def xcorr_has_kernel(real, L, phat):
+    """the product's one-launch table, tests/test_gpu_xcorr.py's has_kernel without the development switch"""
+    return L in (2048, 4096, 8192, 16384) and real == "f64" and not phat
+
+
+def xcorr(L, n, cplx, composed_only=False):
+    kind = "complex" if cplx else "real"
+    wins = xcorr_windows(L)
+
+    def make(api, real):
+        return ctx_of(Plans([api.fa.CrossCorrelation(n, L, first, lags, real, not cplx, api.device) for first, lags in wins]))
+
+    def routes_of(phat):
+        def routes(real):
+            fused = not cplx and not composed_only and xcorr_has_kernel(real, L, phat)
+            both = (({"weighting": phat, "fusion": 1}, "xcorr one-launch: "), ({"weighting": phat, "fusion": 0}, "xcorr composed: "))
+            return both if fused else (({"weighting": phat, "fusion": 1}, "xcorr composed: "),)
+        return routes
+
+    def run(api, c, ins):
+        x, y = api.put(ins[0]), api.put(ins[1])
+        dt = ins[0].dtype
+        return np.concatenate([api.run(lambda out: p.correlate_ptr(api.ptr(x), api.ptr(y), out, BATCH), (BATCH * p.lags(),), dt) for p in c.plan.plans])
+
+    def truth_of(phat):
+        return lambda c, ins: xcorr_truth.full(ins[0], ins[1], L, bool(phat))
+
+    def err(c, out, want):
+        """tests/test_gpu_xcorr.py's measure, the worse of the two windows"""
+        worst, at = 0.0, 0
+        for first, lags in wins:
+            worst = max(worst, xcorr_truth.window_err(out[at:at + BATCH * lags].reshape(BATCH, lags), want, first, lags))
+            at += BATCH * lags
+        return worst
+
+    g = cgauss if cplx else gauss
+    white = lambda c, rng: [g(rng, BATCH, n), g(rng, BATCH, n)]  # noqa: E731
+    opposite = dict(signs={1: -1}, ks=lambda real: OPPOSITE[real])
+    where = f"{L} n={n} {kind}" + (" composed" if composed_only else "")
+    add(f"xcorr {where} scaled x", 1, make, routes_of(0), white, run, truth_of(0), THREE, scaled=(0,), err=err, integers=True)
+    add(f"xcorr {where} scaled x and y", 2, make, routes_of(0), white, run, truth_of(0), THREE, err=err, integers=True)
+    add(f"xcorr {where} opposite", 0, make, routes_of(0), white, run, truth_of(0), THREE, err=err, **opposite)
+
+    # PHAT: the spike rows of the family's tests and their bound, base x (sqrt(2 (kx^2 + ky^2)) + 1) under kx, ky <= 3
+    def spikes(c, rng):
+        return list(xcorr_truth.spike_rows(rng, BATCH, n, 2, np.complex128 if cplx else np.float64))
+
+    def conditions(c, ins):
+        c.kx, c.ky = xcorr_truth.kappa(ins[0], L), xcorr_truth.kappa(ins[1], L)
+        assert c.kx <= 3 and c.ky <= 3, (c.kx, c.ky)
+
+    def bound(c, d, real):
+        return base_tol(d, real) * (math.sqrt(2 * (c.kx * c.kx + c.ky * c.ky)) + 1)
+
+    def largest_bin(c, ins, y0):
+        wide = np.complex128 if cplx else np.float64
+        return float(max(np.abs(np.fft.fft(a.astype(wide), L, axis=-1)).max() for a in ins))
+
+    phat = dict(err=err, conditions=conditions, bound=bound)
+    add(f"gcc-phat {where} scaled x and y", 0, make, routes_of(1), spikes, run, truth_of(1), None, edge=True, edge_of=largest_bin, **phat)
+    add(f"gcc-phat {where} opposite", 0, make, routes_of(1), spikes, run, truth_of(1), None, **phat, **opposite)
+
+
+xcorr(2048, 1501, False)
+xcorr(1000, 600, False)
+xcorr(255, 100, True)
+
+
+# fractional delay and delay-and-sum: three groups of C rows; the amplitude in the rows, or in the weights; never in the delays
+def delay(L, n, cplx, channels):
+    rows = BATCH * channels
+    delays = np.array((delay_truth.DELAYS * channels)[:rows])
+
+    def make(api, real):
+        return ctx_of(api.fa.Delay(n, L, real, not cplx, channels, api.device))
+
+    def inputs(c, rng):
+        return [(cgauss if cplx else gauss)(rng, rows, n), delays, rng.uniform(0.5, 2.0, rows)]
+
+    def run(api, c, ins):
+        x, d, w = (api.put(a) for a in ins)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), api.ptr(d), api.ptr(w), out, rows), (BATCH, n), ins[0].dtype)
+
+    def truth(c, ins):
+        c.ins = ins
+        return delay_truth.delay(ins[0], ins[1], L, channels, ins[2])
+
+    def err(c, out, want):
+        return delay_truth.err(out, want, c.ins[0], channels, c.ins[2])
+
+    fused = not cplx and channels == 1 and delay_cases.has_kernel("f64", L) and delay_cases.has_kernel("f32", L)
+    routes = fusion_routes("delay one-launch: ", "delay composed: ", lambda real: fused)
+    where = f"{L} n={n} {'complex' if cplx else 'real'} C={channels}"
+    add(f"delay {where} scaled input", 1, make, routes, inputs, run, truth, THREE, scaled=(0,), err=err, integers=True)
+    add(f"delay {where} scaled weights", 1, make, routes, inputs, run, truth, THREE, scaled=(2,), err=err)
+
+
+delay(2048, 1501, False, 1)
+delay(1000, 600, False, 1)
+delay(1000, 600, False, 3)
+delay(255, 100, True, 1)
+
+
+# N-D convolution: a bank of 2 filters, `correlate` off and on in one case; the amplitude in the items, or in the taps (set again at
+# every k)
+def convnd(shape):
+    taps = tuple(min(3, n) for n in shape)
+
+    def make(api, real):
+        return ctx_of(api.fa.FftConvNd(shape, real, api.device), where="emu" if api.device < 0 else "gpu")
+
+    def run(api, c, ins):
+        x, h = api.put(ins[0]), api.put(ins[1])
+        outs = []
+        for correlate in (False, True):
+            c.plan.set_filters_ptr(api.ptr(h), taps, FILTERS, correlate)
+            outs.append(api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), (BATCH,) + shape, ins[0].dtype))
+        return np.stack(outs)
+
+    def truth(c, ins):
+        return np.stack([convnd_truth.circular(ins[0], ins[1], shape, correlate) for correlate in (False, True)])
+
+    def bound(c, d, real):
+        return convnd_cases.bound(c, c.plan, real)
+
+    routes = fusion_routes("convnd fused untangle: ", "convnd composed: ", lambda real: convnd_cases.has_fused(shape))
+    for what, scaled in (("items", (0,)), ("taps", (1,))):
+        add(f"convnd {list(shape)} scaled {what}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, *shape), gauss(rng, FILTERS, *taps)], run, truth,
+            None, scaled=scaled, bound=bound, integers=what == "items")
+
+
+for _shape in ((4, 6), (4, 7), (3, 4, 10), (3, 5, 9)):
+    convnd(_shape)
+
+
+# non-uniform FFT: both signs and both mode orders in one case; the amplitude in the strengths (type 1) or the modes (type 2); never in
+# the points.  The figure is err / bound with tests/nufft_cases.py's bound of each call, 3 x 10^(1 - w) plus its rounding term, held
+# against 1; terms() asserts the condition on the inputs (the f64 model within 2.5 x 10^(1 - w) of the direct sum) first.
+NUFFT_EPS = {"f32": (1e-6,), "f64": (1e-6, 1e-12)}
+NUFFT_CALLS = tuple((sign, order) for sign in (-1, 1) for order in (0, 1))
+
+
+def nufft(n, point_set):
+    def make(api, real):
+        c = ctx_of(Plans([api.fa.Nufft(n, eps, real, api.device) for eps in NUFFT_EPS[real]], pick="accuracy"), real=real, xs=[])
+        for plan, eps in zip(c.plan.plans, NUFFT_EPS[real]):
+            c.xs.append(nufft_cases.points(point_set, n, eps, real))
+            plan.set_points(c.xs[-1])
+        return c
+
+    def routes(real):
+        out = []
+        for i, eps in enumerate(NUFFT_EPS[real]):
+            w = nufft_truth.width(eps, real)
+            for table in (0, 1):
+                out.append(({"accuracy": i, "table": table}, f"nufft {nufft_cases.ROUTES[table]}: w {w}, L {nufft_truth.grid_length(n, w)}, "))
+        return tuple(out)
+
+    def run_of(typ):
+        def run(api, c, ins):
+            plan = c.plan.plan
+            v = api.put(ins[0])
+            call = plan.to_modes_ptr if typ == 1 else plan.to_points_ptr
+            shape = (BATCH, plan.modes() if typ == 1 else plan.points())
+            return np.stack([api.run(lambda out: call(api.ptr(v), out, BATCH, sign, order), shape, ins[0].dtype) for sign, order in NUFFT_CALLS])
+        return run
+
+    def truth_of(typ):
+        def truth(c, ins):
+            c.v, x = ins[0], c.xs[c.plan.now]
+            return np.stack([nufft_cases.want_of(typ, x, ins[0], n, sign, order) for sign, order in NUFFT_CALLS])
+        return truth
+
+    def err_of(typ):
+        def err(c, out, want):
+            eps, x = NUFFT_EPS[c.real][c.plan.now], c.xs[c.plan.now]
+            return max(rel_l2(out[i], want[i]) / nufft_cases.bound(c.real, n, eps, x, typ, c.v, sign, order, want[i])
+                       for i, (sign, order) in enumerate(NUFFT_CALLS))
+        return err
+
+    one = lambda d, real: 1.0  # noqa: E731
+    m = len(nufft_cases.points(point_set, n, 1e-6, "f64"))
+    add(f"nufft type 1 N={n} {point_set} scaled strengths", 1, make, routes, lambda c, rng: [cgauss(rng, BATCH, m)], run_of(1), truth_of(1), one,
+        err=err_of(1), integers=True)
+    add(f"nufft type 2 N={n} {point_set} scaled modes", 1, make, routes, lambda c, rng: [cgauss(rng, BATCH, n)], run_of(2), truth_of(2), one,
+        err=err_of(2), integers=True)
+
+
+for _n, _set in ((100, "random37"), (101, "random37"), (101, "last_cell")):
+    assert _n in nufft_cases.sizes_for(_set)
+    nufft(_n, _set)
+
+
+# cepstrum and minimum phase: no exact scaling (the logarithm), so (b) at k = +-40 / +-300 in the family's own measure, which divides by
+# kappa and does not change with scale, and the identity between the two results that the truths satisfy exactly:
+#   cepstrum       c(2^k x) = c(x) + k log_mult ln 2 at quefrency 0          minimum phase   h(2^k x) = 2^(k log_mult) h(x)
+def cepstrum(L, n, mode, log_mult):
+    def make(api, real):
+        return ctx_of(api.fa.Cepstrum(n, L, real, n, mode, api.device))
+
+    def conditions(c, ins):
+        """tests/cepstrum_cases.py's conditions (both scale-invariant), without its line of output"""
+        kappa, phase = float(cepstrum_truth.kappa(ins[0], L).max()), cepstrum_truth.max_phase(ins[0], L, log_mult)
+        assert kappa <= 4 and phase <= np.pi, (L, n, kappa, phase)
+
+    def run(api, c, ins):
+        x = api.put(ins[0])
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH, log_mult, 0.0), (BATCH, n), ins[0].dtype)
+
+    def truth(c, ins):
+        c.x = ins[0]
+        return cepstrum_truth.full(mode, ins[0], L, log_mult)[:, :n]
+
+    def err(c, out, want):
+        return cepstrum_truth.err(mode, out, c.x, L, n, log_mult)
+
+    def bound(c, d, real):
+        return (3 if mode == cepstrum_truth.CEPSTRUM else 6) * base_tol(d, real)
+
+    def identity(c, k, s, o, ins):
+        s, o = s.astype(np.float64), o.astype(np.float64)
+        den = abs(log_mult) * cepstrum_truth.kappa(ins[0], L)
+        if mode == cepstrum_truth.CEPSTRUM:
+            s[:, 0] -= k * log_mult * math.log(2.0)
+        else:
+            s = np.ldexp(s, -k * int(log_mult))
+            den = den * np.linalg.norm(cepstrum_truth.full(mode, ins[0], L, log_mult), axis=-1)
+        return float(np.max(np.linalg.norm(s - o, axis=-1) / den))
+
+    def largest_bin(c, ins, y0):
+        return float(np.abs(cepstrum_truth.spectrum(ins[0], L)).max())
+
+    fused = all(cepstrum_cases.has_kernel(real, mode, L) for real in ("f32", "f64"))
+    name = cepstrum_cases.MODE_NAME[mode]
+    routes = fusion_routes(f"cepstrum one-launch ({name}): ", f"cepstrum composed ({name}): ", lambda real: fused)
+    samples = mode == cepstrum_truth.CEPSTRUM  # the minimum-phase input is a filter, not samples
+    add(f"cepstrum {L} n={n} {name} log_mult {log_mult:+d}", None, make, routes, lambda c, rng: [cepstrum_truth.rows(rng, BATCH, n, np.float64)], run, truth,
+        None, kd=1, err=err, bound=bound, conditions=conditions, identity=identity, integers=samples, edge=samples, edge_of=largest_bin)
+
+
+for _L, _n in ((2048, 1501), (1000, 600)):
+    for _mode in cepstrum_cases.MODES:
+        for _log_mult in (1, -1):
+            cepstrum(_L, _n, _mode, _log_mult)
 
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)

@@ -271,6 +271,55 @@ def floor_on_a_zero_row(be, real, fusion):
             note(real, mode, route, f"zero rows, log_floor=1e-3 log_mult={log_mult}", rel, bound(plan, real, mode))
 
 
+FLOORS = {"f32": (1e-18, 1e-19, 1e-25, 1e-37, 1e30, 1e38), "f64": (1e-150, 1e-200, 1e-300, 1e200, 1e300)}
+
+
+def floor_whose_square_leaves_the_format(be, real, fusion):
+    """Every positive floor that is a normal number of T is honoured, whatever log_floor^2 does in T (FLOORS: the first of each
+    precision has a normal square, the small ones after it a square that is subnormal or 0, the large ones a square that is inf).
+    Six rows, rows 1 and 4 zero, both modes, log_mult 1 and 0.5:
+      the zero rows are [log_mult ln floor, 0, ...] (minimum phase [floor^log_mult, 0, ...]) under floor_on_a_zero_row's bound;
+      under a floor whose square is below the smallest normal number the other rows are BIT-equal to the call with log_floor = 0;
+      under a floor whose square is inf every row is the zero row's, under the same bound.
+    Before the handle took the value of a floored bin from the host for such a floor: f32 1e-25 gave -inf / NaN in the zero rows (one-launch
+    [-inf, nan, ...], composed all NaN), 1e30 gave [inf, nan, ...] / NaN in every row; f64 1e-200 and 1e200 the same."""
+    L, n = (2048, 1501) if fusion else (1000, 600)
+    dt = ndt(real)
+    x = truth.rows(np.random.default_rng(29), 6, n, dt)
+    zero, other = [1, 4], [0, 2, 3, 5]
+    x[zero] = 0
+    worst, failed = {}, []
+    for mode in MODES:
+        plan, route = make(be, n, L, n, real, mode, fusion)
+        for log_mult in (1.0, 0.5):
+            free = run(be, plan, x, log_mult, 0.0)
+            for floor in FLOORS[real]:
+                fl = float(dt(floor))
+                with np.errstate(over="ignore", under="ignore"):
+                    square = float(dt(fl) * dt(fl))
+                out = run(be, plan, x, log_mult, floor).astype(np.float64)
+                want = np.zeros(n)
+                want[0] = log_mult * np.log(fl) if mode == truth.CEPSTRUM else fl ** log_mult
+                rows = zero if np.isfinite(square) else [0, 1, 2, 3, 4, 5]
+                with np.errstate(invalid="ignore"):
+                    rel = float(np.linalg.norm((out[rows] - want) / abs(want[0]), axis=-1).max())  # (the quotient first: 1e300^2 overflows)
+                rel = rel if rel == rel else np.inf
+                bnd = bound(plan, real, mode)
+                key = (MODE_NAME[mode], log_mult)
+                if rel / bnd >= worst.get(key, (0.0,))[0]:
+                    worst[key] = (rel / bnd, rel, bnd, floor)
+                if not rel <= bnd:
+                    failed.append((MODE_NAME[mode], log_mult, floor, "floored rows", rel, bnd, out[rows[0], :3].tolist()))
+                if square < np.finfo(dt).tiny and not np.array_equal(out[other].astype(dt), free[other]):
+                    failed.append((MODE_NAME[mode], log_mult, floor, "a row above the floor differs from the call without a floor"))
+    for (name, log_mult), (ratio, rel, bnd, floor) in sorted(worst.items()):
+        print(f"cepstrum {real} {name} {route} floors {FLOORS[real]} log_mult={log_mult}: worst err {rel:.3g} bound {bnd:.3g} ratio {ratio:.3g} (log_floor={floor:g})")
+        key = (real, name, route)
+        if ratio == ratio and ratio != np.inf:
+            WORST[key] = max(WORST.get(key, 0.0), ratio)
+    assert not failed, (real, route, failed)
+
+
 def zero_floor_on_a_zero_row(be, real, mode, fusion):
     """the same row with log_floor = 0, as row 3 of 6: rows 0 - 2 and 4 - 5 are bit-equal to a call without it, row 3 is not finite,
     and nothing outside the output is touched (run checks the guard bands)"""

@@ -1,7 +1,9 @@
 """The amplitude range WITHOUT a GPU: tests/amplitude_cases.py on the CPU emulation (tests/emu) -- the same kernel sources in CPU
 arithmetic, driven through the same C ABI / Python layer as the product.  The `-m gpu` twin is tests/test_gpu_amplitude.py; the two run
-the same cases and make the same assertions: (a) f(2^k x) bit-equal to 2^(k d) f(x), (b) the families' tolerances against the f64 truth
-at the extreme k, (c) integer-valued samples in f32 and the two-tone coherence, (d) the range edge of the magnitude paths."""
+the same cases and make the same assertions: (a) f(2^k x) bit-equal to 2^(k d) f(x) -- and, for the cross-correlation and GCC-PHAT,
+x 2^k against y 2^-k with no bit changed --, (b) the families' tolerances against the f64 truth at the extreme k (the cepstrum also
+against its own k = 0 result at every k), (c) integer-valued samples in f32 and the two-tone coherence, (d) the range edge of the
+magnitude paths, of GCC-PHAT and of the cepstrum."""
 import pytest
 
 import amplitude_cases as cases

@@ -1,7 +1,8 @@
 """The fourier_hip_cepstrum_* family: include/fourier.h, the library's exports and fourier_amd._lib.CEPSTRUM_SYMBOLS name the same
 symbols -- create, destroy, size, length, outputs, mode, apply, reserve, set_option, describe and the last_status that every handle
 family has, for float and double --, every symbol resolves, the NULL-handle contract of every entry point holds, create with
-parameters out of range fails, and create fails without a GPU (no compute calls: this runs without one)."""
+parameters out of range fails, and create fails without a GPU (no compute calls: this runs without one).  The per-call reals that
+are refused AFTER rounding to the handle's precision are checked on the CPU emulation build (tests/emu), where a handle exists."""
 import os
 import re
 import subprocess
@@ -88,3 +89,38 @@ def test_create_fails_without_a_gpu(libpath):
         fourier_amd.create_cepstrum_f64(1000, 1000, 500, mode=1)
     with pytest.raises(ValueError):
         fourier_amd.Cepstrum(0, 8)
+
+
+def test_parameters_that_round_out_of_range_in_float_are_refused_and_write_nothing():
+    """log_floor > 0 that rounds to 0 (1e-200), to a subnormal (1e-40) or to inf (1e39) in float, and log_mult that rounds to 0 (1e-50)
+    or to inf (1e60): FOURIER_HIP_INVALID_ARGUMENT from the call and from last_status, and the output keeps every byte.  The same
+    values are valid for the double handle.  (Before the check: 1e-200 was taken as "no floor", 1e-50 returned zeros and 1e60 NaN,
+    all with status success.)"""
+    import numpy as np
+
+    from emu import build_emu
+
+    lib = build_emu.load()
+    n, L, batch = 600, 1000, 3
+    x = np.ones((batch, n), np.float32)
+    x[:, 1:] = 0.01
+    for suffix, dt, refused in (("float", np.float32, True), ("double", np.float64, False)):
+        fn = lambda op: getattr(lib, f"fourier_hip_cepstrum_{op}_{suffix}")  # noqa: E731
+        for mode in (0, 1):
+            h = fn("create")(n, L, n, mode, -1)
+            assert h
+            xin = np.ascontiguousarray(x.astype(dt))
+            try:
+                for fusion in (1, 0):
+                    assert fn("set_option")(h, b"fusion", fusion) == 0
+                    for log_mult, log_floor in ((1.0, 1e-200), (1.0, 1e-40), (1.0, 1e39), (1e-50, 0.0), (1e60, 0.0), (-1e-50, 1e-3), (-1e60, 1e-3)):
+                        out = np.full((batch, n), 77.0, dt)
+                        st = fn("apply")(h, xin.ctypes.data, out.ctypes.data, batch, log_mult, log_floor, None)
+                        if refused:
+                            assert st == INVALID and fn("last_status")(h) == INVALID, (suffix, mode, log_mult, log_floor, st)
+                            assert np.all(out == 77.0), (suffix, mode, log_mult, log_floor, "the output was written")
+                        else:
+                            assert st == 0 and fn("last_status")(h) == 0, (suffix, mode, log_mult, log_floor, st)
+                    assert fn("apply")(h, xin.ctypes.data, out.ctypes.data, batch, 1.0, 0.0, None) == 0 and fn("last_status")(h) == 0
+            finally:
+                fn("destroy")(h)

@@ -98,6 +98,12 @@ def test_floor_on_a_zero_row(be, real, fusion):
 
 
 @pytest.mark.parametrize("real", ["f32", "f64"])
+@pytest.mark.parametrize("fusion", [1, 0])
+def test_floor_whose_square_leaves_the_format(be, real, fusion):
+    cases.floor_whose_square_leaves_the_format(be, real, fusion)
+
+
+@pytest.mark.parametrize("real", ["f32", "f64"])
 @pytest.mark.parametrize("mode", cases.MODES)
 @pytest.mark.parametrize("fusion", [1, 0])
 def test_zero_floor_on_a_zero_row_touches_nothing_else(be, real, mode, fusion):

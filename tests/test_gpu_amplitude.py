@@ -1,8 +1,10 @@
 """The amplitude range on the MI355X: tests/amplitude_cases.py through the product library.  The CPU twin is
-tests/test_amplitude_emu.py; the two run the same cases and make the same assertions: (a) f(2^k x) bit-equal to 2^(k d) f(x), (b) the
-families' tolerances against the f64 truth at the extreme k, (c) integer-valued samples in f32 and the two-tone coherence, (d) the range
-edge of the magnitude paths.  What the emulation cannot say is whether the device's arithmetic -- contracted multiply-adds, its
-division and square root, its treatment of subnormals -- keeps (a); the k of the cases keep every value normal."""
+tests/test_amplitude_emu.py; the two run the same cases and make the same assertions: (a) f(2^k x) bit-equal to 2^(k d) f(x) -- and,
+for the cross-correlation and GCC-PHAT, x 2^k against y 2^-k with no bit changed --, (b) the families' tolerances against the f64
+truth at the extreme k (the cepstrum also against its own k = 0 result at every k), (c) integer-valued samples in f32 and the
+two-tone coherence, (d) the range edge of the magnitude paths, of GCC-PHAT and of the cepstrum.  What the emulation cannot say is
+whether the device's arithmetic -- contracted multiply-adds, its division and square root, its logf / expf, its treatment of
+subnormals -- keeps (a); the k of the cases keep every value normal."""
 import numpy as np
 import pytest
 
