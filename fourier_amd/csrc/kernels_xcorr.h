@@ -208,14 +208,16 @@ __global__ void __launch_bounds__(FOURIER_TWOLEVEL_NT(T, L1, L2), FOURIER_BLU_SM
     FOURIER_LAUNDER(tb);
     const uint32_t e0 = (uint32_t)((tb / CG1) * L2 + (tb % CG1) * VEC);
     const uint32_t shift = (uint32_t)N - a.xc_first;  // position of lag t: (t - first) mod N
-    {  // the two balancing powers back onto the unweighted result; exact zeros where a row was empty
+    {  // the two balancing powers back onto the unweighted result; exact zeros where a row was empty.  The peak's comparisons are
+       // false for a NaN, so a row of nothing but NaN and zeros counts as empty too: v - v is +0 for every finite v and keeps that
+       // row's result NaN, as the composed route does
       const int* keep = (const int*)(smem + xcorr_core_bytes<T, L1, L2>());
       const int e = PHAT ? 0 : keep[0];
       const bool empty = keep[1] != 0;
 #pragma unroll
       for (int v = 0; v < VEC; ++v)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) x[v][r].im = empty ? (T)0 : ldexp(x[v][r].im, e);
+        for (int r = 0; r < 16; ++r) x[v][r].im = empty ? x[v][r].im - x[v][r].im : ldexp(x[v][r].im, e);
     }
     // f32: an even shift keeps a lane's two lags adjacent and on an even position; rows of an even number of lags at an 8-byte
     // aligned base make that one 8-byte store that lies wholly inside the window or wholly outside (wave-uniform)

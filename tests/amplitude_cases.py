@@ -191,10 +191,12 @@ class Case:
     net degree, 0 there); ks: the exponents by precision where they are not K's; conditions(ctx, ins): the family's conditions on
     its inputs, asserted before anything runs; identity(ctx, k, scaled output, unscaled output, ins) -> a figure held against TWICE
     the bound at every k (a family with d = None whose truths scale by a known rule: the triangle inequality over two results);
-    edge_of(ctx, ins, y0): the magnitude that (d) places at the range edge (default: the largest |y0|)"""
+    edge_of(ctx, ins, y0): the magnitude that (d) places at the range edge (default: the largest |y0|); hold(ctx, ins): fixes every
+    parameter that run() derives from its inputs at its value for `ins`, for the later runs on ctx (tests/isolation_cases.py, whose
+    poisoned inputs have no median: the log band spectrogram's floor)"""
 
     def __init__(self, name, d, make, routes, inputs, run, truth, tol, scaled=None, pick=None, err=None, kd=None, integers=False,
-                 edge=False, describe=None, signs=None, ks=None, conditions=None, bound=None, identity=None, edge_of=None):
+                 edge=False, describe=None, signs=None, ks=None, conditions=None, bound=None, identity=None, edge_of=None, hold=None):
         self.name, self.d, self.make, self.inputs, self.run, self.truth, self.tol = name, d, make, inputs, run, truth, tol
         self.routes = routes if callable(routes) else (lambda real: routes)
         self.scaled, self.pick, self.err = scaled, pick or (lambda ctx, out: out), err or (lambda ctx, out, want: rel_l2(out, want))
@@ -206,6 +208,7 @@ class Case:
         self.bound = bound or (lambda ctx, d, real: self.tol(d, real))
         self.identity = identity
         self.edge_of = edge_of or (lambda ctx, ins, y0: float(np.max(np.abs(y0))))
+        self.hold = hold or (lambda ctx, ins: None)
 
     def unit_inputs(self, ctx):
         return self.inputs(ctx, np.random.default_rng(sum(self.name.encode())))
@@ -878,6 +881,7 @@ def band_spectrogram(n_fft, hop, bands):
         c.W = np.asarray(W).astype(rdt(real)).astype(np.float64)  # what the handle holds: the truth uses the rounded weights
         c.plan.set_bands(c.W)
         assert c.plan.frames(length) == nf and c.plan.bands() == bands
+        c.held_floor = None
         return c
 
     def want(c, ins, power):
@@ -886,7 +890,7 @@ def band_spectrogram(n_fft, hop, bands):
     def forward(power, log):
         def run(api, c, ins):
             # under the log the floor is the median of the truth at this input: about half of the values clamp
-            c.floor = float(np.median(want(c, ins, power))) if log else 0.0
+            c.floor = (float(np.median(want(c, ins, power))) if c.held_floor is None else c.held_floor) if log else 0.0
             x = api.put(ins[0])
             return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH, power, power == 1, LOG_MULT if log else 0.0, c.floor),
                            (BATCH, nf, bands), ins[0].dtype)
@@ -898,7 +902,8 @@ def band_spectrogram(n_fft, hop, bands):
             lambda c, ins, power=power: want(c, ins, power), FOUR)
         add(f"bandspec {n_fft} {bands} bands power {power} log", None, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power, True),
             lambda c, ins, power=power: np.maximum(want(c, ins, power), c.floor), FOUR, kd=power,
-            err=lambda c, out, w: rel_l2(np.exp(out.astype(np.float64) / LOG_MULT), w), integers=power == 2)
+            err=lambda c, out, w: rel_l2(np.exp(out.astype(np.float64) / LOG_MULT), w), integers=power == 2,
+            hold=lambda c, ins, power=power: setattr(c, "held_floor", float(np.median(want(c, ins, power)))))
 
 
 band_spectrogram(256, 64, 20)

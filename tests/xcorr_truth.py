@@ -41,7 +41,7 @@ def full(x, y, L, phat=False):
     Y = np.fft.fft(np.asarray(y, dtype=wide), L, axis=-1)
     if phat:
         ax, ay = np.abs(X), np.abs(Y)
-        ok = (ax > 0) & (ay > 0)
+        ok = ~((ax == 0) | (ay == 0))  # a NaN magnitude is not 0: the bin stays NaN (tests/isolation_cases.py)
         G = np.where(ok, np.conj(X / np.where(ok, ax, 1.0)) * (Y / np.where(ok, ay, 1.0)), 0.0)
     else:
         G = np.conj(X) * Y
