@@ -271,6 +271,7 @@ template <typename T> class Plan : public HandleBase {
     // 0 = always the reference's next power of two (bluesteins.rs:110).  Rebuilds the plan's tables now; not while a transform is in flight.
     if (key == "bluestein_smooth_m" && v >= 0 && v <= 2) {  // (2: wherever a product of two tile lengths exists -- for measurements)
       if (!blu_) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
+      unfused_from_mode_ = -1;  // the caller's own choice of M stands
       if ((int)v != smooth_m_mode_) rebuild_bluestein((int)v);
       return 0;
     }
@@ -278,7 +279,13 @@ template <typename T> class Plan : public HandleBase {
       if (blut_) return 0;  // the smooth-M route has no unfused form
       if (blur_) {          // nor has the register route: the unfused sweeps run on the reference's power-of-two M
         if (v == 1) return 0;
+        unfused_from_mode_ = smooth_m_mode_;
         rebuild_bluestein(0);
+      } else if (v == 1 && unfused_from_mode_ >= 0) {  // ... and 1 brings the register route back: there and back is the plan as created
+        const int mode = unfused_from_mode_;
+        unfused_from_mode_ = -1;
+        rebuild_bluestein(mode);
+        if (blur_) return 0;
       }
       fused_ = (v == 1) && blu_ && eng_->can_fuse_bluestein();
       small_fused_ = (v == 1) && blu_ && eng_->enable_bluestein_small();
@@ -980,6 +987,7 @@ template <typename T> class Plan : public HandleBase {
   std::unique_ptr<BluRegEngine<T>> regf_;         // a length with factors 5 ... 13 as a direct transform on the same register stages
   bool regf_on_request_ = false;                  // ... of a 2^a 3^b length, by plan option "register_stages" (mix_ stays allocated)
   int smooth_m_mode_ = 1;                         // option "bluestein_smooth_m"
+  int unfused_from_mode_ = -1;                    // >= 0: "bluestein_fusion" = 0 took the plan off the register route, from this mode
   std::unique_ptr<MixedEngine<T>> mix_;
   std::unique_ptr<TiledMixedEngine<T>> tiled_;  // 2^a*3^b, a < 12, beyond the LDS kernels: column tiles of mixed length
   std::unique_ptr<GenericEngine<T>> gen_;  // ... and what has no tile factorisation: one global pass per radix

@@ -429,7 +429,17 @@ def window(rng, real, n):
 
 
 def ctx_of(plan, **kw):
-    return types.SimpleNamespace(plan=plan, **kw)
+    """the context of a case: the handle, the batch of the next call -- and, of a frame handle, its length and frame count (restate) --
+    and of a convolution the number of filters (fftconv: and of taps) that run() sets, which inputs, run and truth read from here, so
+    that a caller may state them per call (tests/history_cases.py); likewise `normalized` of the STFT and MDCT calls, the r2r norm, `onesided_fold` and `scale` of Welch and the cross spectrum, `correlate` of
+    the 1-D convolutions, and the window and `filter_first` of the N-D convolution"""
+    return types.SimpleNamespace(plan=plan, batch=BATCH, normalized=False, fold=True, scale=0.37, **kw)
+
+
+def restate(c, length, nf):
+    """the length and the frame count of the next call of a frame handle"""
+    c.length, c.nf = length, nf
+    return c
 
 
 def fusion_routes(fused, composed, has=lambda real: True):
@@ -470,9 +480,9 @@ def core(n, code, name):
 
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, BATCH, code), ins[0].shape, ins[0].dtype)
+        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, c.batch, code), ins[0].shape, ins[0].dtype)
 
-    add(f"fft {n or 'smallest two passes'} {name}", 1, make, (({}, CORE[n] if n else TWO_PASSES),), lambda c, rng: [cgauss(rng, BATCH, c.plan.size())],
+    add(f"fft {n or 'smallest two passes'} {name}", 1, make, (({}, CORE[n] if n else TWO_PASSES),), lambda c, rng: [cgauss(rng, c.batch, c.plan.size())],
         run, lambda c, ins: CORE_TRUTH[code](ins[0].astype(np.complex128)), base_tol)
 
 
@@ -488,15 +498,15 @@ def rfft(n):
 
     def forward(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, BATCH), (BATCH, n // 2 + 1), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, c.batch), (c.batch, n // 2 + 1), cdt(c.plan.real))
 
     def inverse(api, c, ins):
         s = api.put(ins[0])
-        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, BATCH), (BATCH, n), rdt(c.plan.real))
+        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, c.batch), (c.batch, n), rdt(c.plan.real))
 
-    add(f"rfft {n}", 1, make, (({}, "real "),), lambda c, rng: [gauss(rng, BATCH, n)], forward,
+    add(f"rfft {n}", 1, make, (({}, "real "),), lambda c, rng: [gauss(rng, c.batch, n)], forward,
         lambda c, ins: np.fft.rfft(ins[0].astype(np.float64), axis=-1), base_tol, integers=n == 4096)
-    add(f"irfft {n}", 1, make, (({}, "real "),), lambda c, rng: [half_spectrum(rng, (BATCH,), n)], inverse,
+    add(f"irfft {n}", 1, make, (({}, "real "),), lambda c, rng: [half_spectrum(rng, (c.batch,), n)], inverse,
         lambda c, ins: np.fft.irfft(ins[0].astype(np.complex128), n=n, axis=-1), base_tol)
 
 
@@ -513,16 +523,16 @@ def rfftn(shape):
 
     def forward(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, BATCH), (BATCH,) + half, cdt(c.plan.real))
+        return api.run(lambda out: c.plan.forward_batch_ptr(api.ptr(x), out, c.batch), (c.batch,) + half, cdt(c.plan.real))
 
     def inverse(api, c, ins):
         s = api.put(ins[0])
-        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, BATCH), (BATCH,) + shape, rdt(c.plan.real))
+        return api.run(lambda out: c.plan.inverse_batch_ptr(api.ptr(s), out, c.batch), (c.batch,) + shape, rdt(c.plan.real))
 
-    add(f"rfftn {list(shape)}", 1, make, (({}, "realnd "),), lambda c, rng: [gauss(rng, BATCH, *shape)], forward,
+    add(f"rfftn {list(shape)}", 1, make, (({}, "realnd "),), lambda c, rng: [gauss(rng, c.batch, *shape)], forward,
         lambda c, ins: np.fft.rfftn(ins[0].astype(np.float64), axes=axes), realnd_tol)
     add(f"irfftn {list(shape)}", 1, make, (({}, "realnd "),),
-        lambda c, rng: [np.fft.rfftn(gauss(rng, BATCH, *shape), axes=axes) / math.sqrt(np.prod(shape))], inverse,
+        lambda c, rng: [np.fft.rfftn(gauss(rng, c.batch, *shape), axes=axes) / math.sqrt(np.prod(shape))], inverse,
         lambda c, ins: np.fft.irfftn(ins[0].astype(np.complex128), s=shape, axes=axes), realnd_tol)
 
 
@@ -533,11 +543,15 @@ def axis(outer, n, inner):
     def make(api, real):
         return ctx_of(api.fa.Fft(n, real, api.device))
 
+    def outer_of(c):
+        """the outer count is this case's batch: `outer` at the table's batch, in proportion elsewhere"""
+        return outer * c.batch // BATCH
+
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.transform_axis_ptr(api.ptr(x), out, outer, inner, FFT), ins[0].shape, ins[0].dtype)
+        return api.run(lambda out: c.plan.transform_axis_ptr(api.ptr(x), out, outer_of(c), inner, FFT), ins[0].shape, ins[0].dtype)
 
-    add(f"axis [{outer}, {n}, {inner}]", 1, make, (({}, "axis "),), lambda c, rng: [cgauss(rng, outer, n, inner)], run,
+    add(f"axis [{outer}, {n}, {inner}]", 1, make, (({}, "axis "),), lambda c, rng: [cgauss(rng, outer_of(c), n, inner)], run,
         lambda c, ins: np.fft.fft(ins[0].astype(np.complex128), axis=1), axis_tol, describe=lambda c: c.plan.describe_axis(inner))
 
 
@@ -546,15 +560,15 @@ axis(8, 64, 6)
 
 def r2r(n, kind):
     def make(api, real):
-        return ctx_of(api.fa.R2R(n, real, api.device), idx=r2r_truth.want(kind, "ortho", np.zeros((1, n)))[0])
+        return ctx_of(api.fa.R2R(n, real, api.device), idx=r2r_truth.want(kind, "ortho", np.zeros((1, n)))[0], norm="ortho")
 
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, BATCH, r2r_truth.KINDS[kind], r2r_truth.NORMS["ortho"]),
-                       (BATCH, n), ins[0].dtype)
+        return api.run(lambda out: c.plan.transform_batch_ptr(api.ptr(x), out, c.batch, r2r_truth.KINDS[kind], r2r_truth.NORMS[c.norm]),
+                       (c.batch, n), ins[0].dtype)
 
-    add(f"r2r {n} {kind} ortho", 1, make, (({}, "r2r "),), lambda c, rng: [gauss(rng, BATCH, n)], run,
-        lambda c, ins: r2r_truth.want(kind, "ortho", ins[0])[1], TWO, pick=lambda c, out: out[:, c.idx])
+    add(f"r2r {n} {kind} ortho", 1, make, (({}, "r2r "),), lambda c, rng: [gauss(rng, c.batch, n)], run,
+        lambda c, ins: r2r_truth.want(kind, c.norm, ins[0])[1], TWO, pick=lambda c, out: out[:, c.idx])
 
 
 for _n in (1000, 255):
@@ -566,13 +580,14 @@ for _n in (1000, 255):
 FILTERS, TAPS = 2, 33
 
 
-def conv_want(x, h):
-    """numpy in f64; row b with filter b mod F (tests/test_gpu_conv.py's want)"""
+def conv_want(x, h, correlate=False):
+    """numpy in f64; row b with filter b mod F (tests/test_gpu_conv.py's want); correlate: with the conjugated spectrum of the taps"""
     n = x.shape[-1]
     hb = h[np.arange(x.shape[0]) % h.shape[0]]
+    conj = np.conj if correlate else (lambda v: v)
     if np.iscomplexobj(x):
-        return np.fft.ifft(np.fft.fft(x.astype(np.complex128), axis=-1) * np.fft.fft(hb.astype(np.complex128), n, axis=-1), axis=-1)
-    return np.fft.irfft(np.fft.rfft(x.astype(np.float64), axis=-1) * np.fft.rfft(hb.astype(np.float64), n, axis=-1), n=n, axis=-1)
+        return np.fft.ifft(np.fft.fft(x.astype(np.complex128), axis=-1) * conj(np.fft.fft(hb.astype(np.complex128), n, axis=-1)), axis=-1)
+    return np.fft.irfft(np.fft.rfft(x.astype(np.float64), axis=-1) * conj(np.fft.rfft(hb.astype(np.float64), n, axis=-1)), n=n, axis=-1)
 
 
 def fftconv(n, real_data):
@@ -580,20 +595,20 @@ def fftconv(n, real_data):
     kind = "real" if real_data else "complex"
 
     def make(api, real):
-        return ctx_of(api.fa.FftConv(n, real, real_data, api.device))
+        return ctx_of(api.fa.FftConv(n, real, real_data, api.device), filters=FILTERS, taps=TAPS, correlate=False)
 
     def run(api, c, ins):
         x, h = api.put(ins[0]), api.put(ins[1])
-        c.plan.set_filters_ptr(api.ptr(h), TAPS, FILTERS)
-        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), ins[0].shape, ins[0].dtype)
+        c.plan.set_filters_ptr(api.ptr(h), c.taps, c.filters, c.correlate)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, c.batch), ins[0].shape, ins[0].dtype)
 
     if real_data:
         routes = (({"fusion": 1}, "conv real fused untangle: "), ({"fusion": 0}, "conv real composed: "))
     else:
         routes = (({"fusion": 1}, "conv one-launch: "), ({"fusion": 0}, "conv composed: ")) if n == 4096 else (({"fusion": 1}, "conv composed: "),)
     for what, scaled in (("signal", (0,)), ("filter", (1,))):
-        add(f"fftconv {n} {kind} scaled {what}", 1, make, routes, lambda c, rng: [g(rng, BATCH, n), g(rng, FILTERS, TAPS)], run,
-            lambda c, ins: conv_want(ins[0], ins[1]), THREE, scaled=scaled)
+        add(f"fftconv {n} {kind} scaled {what}", 1, make, routes, lambda c, rng: [g(rng, c.batch, n), g(rng, c.filters, c.taps)], run,
+            lambda c, ins: conv_want(ins[0], ins[1], c.correlate), THREE, scaled=scaled)
 
 
 for _n in (4096, 1000):
@@ -606,20 +621,21 @@ def lconv(lx, k, real_data):
     off = (k - 1) // 2  # mode "same"
 
     def make(api, real):
-        return ctx_of(api.fa.LinearConv(lx, k, real, "same", real_data, api.device))
+        return ctx_of(api.fa.LinearConv(lx, k, real, "same", real_data, api.device), filters=FILTERS, correlate=False)
 
     def run(api, c, ins):
         x, h = api.put(ins[0]), api.put(ins[1])
-        c.plan.set_filters_ptr(api.ptr(h), FILTERS)
-        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), (BATCH, c.plan.out_length()), ins[0].dtype)
+        c.plan.set_filters_ptr(api.ptr(h), c.filters, c.correlate)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, c.batch), (c.batch, c.plan.out_length()), ins[0].dtype)
 
     def truth(c, ins):
         wide = np.float64 if real_data else np.complex128
-        return np.array([np.convolve(ins[0][b].astype(wide), ins[1][b % FILTERS].astype(wide))[off:off + lx] for b in range(BATCH)])
+        taps = np.conj(ins[1][:, ::-1]) if c.correlate else ins[1]  # (correlate: set_filters stores conj(h[K - 1 - i]) in place of h[i])
+        return np.array([np.convolve(ins[0][b].astype(wide), taps[b % c.filters].astype(wide))[off:off + lx] for b in range(c.batch)])
 
     for what, scaled in (("signal", (0,)), ("filter", (1,))):
         add(f"lconv {lx} K={k} same {'real' if real_data else 'complex'} scaled {what}", 1, make, (({}, "lconv overlap-save: "),),
-            lambda c, rng: [g(rng, BATCH, lx), g(rng, FILTERS, k)], run, truth, THREE, scaled=scaled)
+            lambda c, rng: [g(rng, c.batch, lx), g(rng, c.filters, k)], run, truth, THREE, scaled=scaled)
 
 
 for _real_data in (False, True):
@@ -654,22 +670,22 @@ def stft(n_fft, hop):
     def make(api, real):
         c = frame_ctx(api, api.fa.Stft, real, n_fft, hop)
         assert c.plan.frames(length) == stft_truth.frames(length, n_fft, hop, "reflect") == nf
-        return c
+        return restate(c, length, nf)
 
     def forward(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, nf, bins), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.length, c.batch, c.normalized), (c.batch, c.nf, bins), cdt(c.plan.real))
 
     def inverse(api, c, ins):
         s = api.put(ins[0])
-        back = c.plan.default_length(nf)
-        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, nf, back, BATCH), (BATCH, back), rdt(c.plan.real))
+        back = c.plan.default_length(c.nf)
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, c.nf, back, c.batch, c.normalized), (c.batch, back), rdt(c.plan.real))
 
     add(f"stft {n_fft} hop {hop}", 1, make, fusion_routes("stft fused rows, istft composed: real ", "stft composed, istft composed: real ", lambda real: fused),
-        lambda c, rng: [gauss(rng, BATCH, length)], forward, lambda c, ins: stft_truth.stft(ins[0], n_fft, hop, n_fft, c.w, "reflect"), TWO)
+        lambda c, rng: [gauss(rng, c.batch, c.length)], forward, lambda c, ins: stft_truth.stft(ins[0], n_fft, hop, n_fft, c.w, "reflect", c.normalized), TWO)
     add(f"istft {n_fft} hop {hop}", 1, make, (({"fusion": 0}, "stft composed, istft composed: real "),),
-        lambda c, rng: [half_spectrum(rng, (BATCH, nf), n_fft)], inverse,
-        lambda c, ins: stft_truth.istft(ins[0], n_fft, hop, c.plan.default_length(nf), n_fft, c.w, "reflect"), FOUR)
+        lambda c, rng: [half_spectrum(rng, (c.batch, c.nf), n_fft)], inverse,
+        lambda c, ins: stft_truth.istft(ins[0], n_fft, hop, c.plan.default_length(c.nf), n_fft, c.w, "reflect", c.normalized), FOUR)
 
 
 stft(256, 64)
@@ -688,20 +704,20 @@ def mdct(n):
         plan.set_window_ptr(api.ptr(dw))
         nf = plan.frames(length)
         assert nf == mdct_truth.frames(length, n, True) == 11
-        return ctx_of(plan, w=w, dw=dw, nf=nf)
+        return ctx_of(plan, w=w, dw=dw, nf=nf, length=length)
 
     def forward(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, c.nf, n), ins[0].dtype)
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.length, c.batch, c.normalized), (c.batch, c.nf, n), ins[0].dtype)
 
     def inverse(api, c, ins):
         s = api.put(ins[0])
-        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, c.nf, length, BATCH), (BATCH, length), ins[0].dtype)
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, c.nf, c.length, c.batch, c.normalized), (c.batch, c.length), ins[0].dtype)
 
-    add(f"mdct {n}", 1, make, fusion_routes(fused, composed, lambda real: fused is not None), lambda c, rng: [gauss(rng, BATCH, length)], forward,
-        lambda c, ins: mdct_truth.mdct(ins[0], n, c.w, True), TWO)
-    add(f"imdct {n}", 1, make, (({"fusion": 0}, composed),), lambda c, rng: [gauss(rng, BATCH, 11, n)], inverse,
-        lambda c, ins: mdct_truth.imdct(ins[0], n, length, c.w, True), FOUR)
+    add(f"mdct {n}", 1, make, fusion_routes(fused, composed, lambda real: fused is not None), lambda c, rng: [gauss(rng, c.batch, c.length)], forward,
+        lambda c, ins: mdct_truth.mdct(ins[0], n, c.w, True, c.normalized), TWO)
+    add(f"imdct {n}", 1, make, (({"fusion": 0}, composed),), lambda c, rng: [gauss(rng, c.batch, c.nf, n)], inverse,
+        lambda c, ins: mdct_truth.imdct(ins[0], n, c.length, c.w, True, c.normalized), FOUR)
 
 
 mdct(256)
@@ -720,26 +736,26 @@ def pfb(P, T, D, real_rows):
             h = np.ascontiguousarray(np.random.default_rng(P + T).standard_normal(P * T).astype(rdt(real)))
             dh = api.put(h)
             plan.set_filter_ptr(api.ptr(dh))
-            return ctx_of(plan, h=h, dh=dh)
+            return ctx_of(plan, h=h, dh=dh, length=length, nf=nf)
         return make
 
     def forward(api, c, ins):
-        assert c.plan.frames(length) == pfb_truth.frames(length, P, T, D) == nf
+        assert c.plan.frames(c.length) == pfb_truth.frames(c.length, P, T, D) == c.nf
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH), (BATCH, nf, bins), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.length, c.batch), (c.batch, c.nf, bins), cdt(c.plan.real))
 
     def inverse(api, c, ins):
-        assert c.plan.length(nf) == ipfb_truth.full(nf, P, T, D) == length
+        assert c.plan.length(c.nf) == ipfb_truth.full(c.nf, P, T, D) == c.length
         s = api.put(ins[0])
-        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, nf, length, BATCH), (BATCH, length),
+        return api.run(lambda out: c.plan.inverse_ptr(api.ptr(s), out, c.nf, c.length, c.batch), (c.batch, c.length),
                        rdt(c.plan.real) if real_rows else cdt(c.plan.real))
 
     add(f"pfb P={P} T={T} D={D} {kind}", 1, make_with(lambda fa: fa.Pfb), fusion_routes("pfb fused rows: ", "pfb composed: "),
-        lambda c, rng: [(gauss if real_rows else cgauss)(rng, BATCH, length)], forward,
+        lambda c, rng: [(gauss if real_rows else cgauss)(rng, c.batch, c.length)], forward,
         lambda c, ins: pfb_truth.pfb(ins[0], c.h, P, T, D, real_rows), TWO)
     add(f"ipfb P={P} T={T} D={D} {kind}", 1, make_with(lambda fa: fa.Ipfb), (({}, "ipfb composed: "),),
-        lambda c, rng: [half_spectrum(rng, (BATCH, nf), P) if real_rows else cgauss(rng, BATCH, nf, P)], inverse,
-        lambda c, ins: ipfb_truth.synth(ins[0], c.h, P, T, D, real_rows, length), TWO)
+        lambda c, rng: [half_spectrum(rng, (c.batch, c.nf), P) if real_rows else cgauss(rng, c.batch, c.nf, P)], inverse,
+        lambda c, ins: ipfb_truth.synth(ins[0], c.h, P, T, D, real_rows, c.length), TWO)
 
 
 pfb(256, 4, 192, True)
@@ -756,11 +772,11 @@ def resample(n, m, complex_rows):
 
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, BATCH), (BATCH, m), ins[0].dtype)
+        return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.batch), (c.batch, m), ins[0].dtype)
 
     routes = (({"fusion": 0}, "resample complex: "),) if complex_rows else fusion_routes("resample real fused untangle: ", "resample real composed: ")
     add(f"resample {n} -> {m} {'complex' if complex_rows else 'real'}", 1, make, routes,
-        lambda c, rng: [(cgauss if complex_rows else gauss)(rng, BATCH, n)], run, lambda c, ins: resample_truth.resample(ins[0], m, c.w), TWO)
+        lambda c, rng: [(cgauss if complex_rows else gauss)(rng, c.batch, n)], run, lambda c, ins: resample_truth.resample(ins[0], m, c.w), TWO)
 
 
 resample(3000, 2756, False)
@@ -773,10 +789,10 @@ def czt(n, m, real_input):
 
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.transform_ptr(api.ptr(x), out, BATCH), (BATCH, m), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.transform_ptr(api.ptr(x), out, c.batch), (c.batch, m), cdt(c.plan.real))
 
     add(f"czt {n} -> {m} {'real' if real_input else 'complex'}", 1, make, fusion_routes("czt one-launch: ", "czt composed: "),
-        lambda c, rng: [(gauss if real_input else cgauss)(rng, BATCH, n)], run, lambda c, ins: czt_truth.czt(ins[0], m, 1.0, -1.0 / m), czt_tol)
+        lambda c, rng: [(gauss if real_input else cgauss)(rng, c.batch, n)], run, lambda c, ins: czt_truth.czt(ins[0], m, 1.0, -1.0 / m), czt_tol)
 
 
 czt(1000, 1000, False)
@@ -789,15 +805,15 @@ def hilbert(n):
 
     def analytic(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.analytic_ptr(api.ptr(x), out, BATCH), (BATCH, n), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.analytic_ptr(api.ptr(x), out, c.batch), (c.batch, n), cdt(c.plan.real))
 
     def envelope(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.envelope_ptr(api.ptr(x), out, BATCH), (BATCH, n), ins[0].dtype)
+        return api.run(lambda out: c.plan.envelope_ptr(api.ptr(x), out, c.batch), (c.batch, n), ins[0].dtype)
 
     routes = fusion_routes("hilbert one-launch: ", "hilbert composed: ", lambda real: n == 2048)
-    add(f"hilbert analytic {n}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, n)], analytic, lambda c, ins: hilbert_truth.analytic(ins[0]), TWO)
-    add(f"hilbert envelope {n}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, n)], envelope, lambda c, ins: hilbert_truth.envelope(ins[0]), TWO,
+    add(f"hilbert analytic {n}", 1, make, routes, lambda c, rng: [gauss(rng, c.batch, n)], analytic, lambda c, ins: hilbert_truth.analytic(ins[0]), TWO)
+    add(f"hilbert envelope {n}", 1, make, routes, lambda c, rng: [gauss(rng, c.batch, n)], envelope, lambda c, ins: hilbert_truth.envelope(ins[0]), TWO,
         integers=n == 2048, edge=True)
 
 
@@ -815,24 +831,24 @@ def spectrogram(n_fft, hop):
     def make(api, real):
         c = frame_ctx(api, api.fa.Spectrogram, real, n_fft, hop)
         assert c.plan.frames(length) == nf
-        return c
+        return restate(c, length, nf)
 
     def forward(power):
         def run(api, c, ins):
             x = api.put(ins[0])
-            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH, power, power == 1), (BATCH, nf, bins), ins[0].dtype)
+            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.length, c.batch, power, power == 1), (c.batch, c.nf, bins), ins[0].dtype)
         return run
 
     def welch(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.welch_ptr(api.ptr(x), out, length, BATCH, True, 0.37), (BATCH, bins), ins[0].dtype)
+        return api.run(lambda out: c.plan.welch_ptr(api.ptr(x), out, c.length, c.batch, c.fold, c.scale), (c.batch, bins), ins[0].dtype)
 
     for power in (2, 1):
-        add(f"spectrogram {n_fft} hop {hop} power {power}", power, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power),
+        add(f"spectrogram {n_fft} hop {hop} power {power}", power, make, routes, lambda c, rng: [gauss(rng, c.batch, c.length)], forward(power),
             lambda c, ins, power=power: spectrogram_truth.spectrogram(ins[0], n_fft, hop, n_fft, c.w, "reflect", power, power == 1), FOUR,
             integers=n_fft == 256, edge=power == 1)
-    add(f"welch {n_fft} hop {hop}", 2, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], welch,
-        lambda c, ins: spectrogram_truth.welch(ins[0], n_fft, hop, n_fft, c.w, "reflect", True, 0.37), FOUR, integers=n_fft == 256)
+    add(f"welch {n_fft} hop {hop}", 2, make, routes, lambda c, rng: [gauss(rng, c.batch, c.length)], welch,
+        lambda c, ins: spectrogram_truth.welch(ins[0], n_fft, hop, n_fft, c.w, "reflect", c.fold, c.scale), FOUR, integers=n_fft == 256)
 
 
 spectrogram(256, 64)
@@ -848,21 +864,21 @@ def cross_spectrum(n_fft, hop):
     def make(api, real):
         c = frame_ctx(api, api.fa.CrossSpectrum, real, n_fft, hop)
         assert c.plan.frames(length) == nf
-        return c
+        return restate(c, length, nf)
 
     def inputs(c, rng):
-        return list(csd_truth.pair(rng, BATCH, length, np.float64))
+        return list(csd_truth.pair(rng, c.batch, c.length, np.float64))
 
     def csd(api, c, ins):
         x, y = api.put(ins[0]), api.put(ins[1])
-        return api.run(lambda out: c.plan.csd_ptr(api.ptr(x), api.ptr(y), out, length, BATCH, True, 0.37), (BATCH, bins), cdt(c.plan.real))
+        return api.run(lambda out: c.plan.csd_ptr(api.ptr(x), api.ptr(y), out, c.length, c.batch, c.fold, c.scale), (c.batch, bins), cdt(c.plan.real))
 
     def coherence(api, c, ins):
         x, y = api.put(ins[0]), api.put(ins[1])
-        return api.run(lambda out: c.plan.coherence_ptr(api.ptr(x), api.ptr(y), out, length, BATCH), (BATCH, bins), ins[0].dtype)
+        return api.run(lambda out: c.plan.coherence_ptr(api.ptr(x), api.ptr(y), out, c.length, c.batch), (c.batch, bins), ins[0].dtype)
 
     add(f"csd {n_fft} hop {hop}", 2, make, routes, inputs, csd,
-        lambda c, ins: csd_truth.csd(ins[0], ins[1], n_fft, hop, n_fft, c.w, "reflect", True, 0.37), csd_tol, integers=n_fft == 256)
+        lambda c, ins: csd_truth.csd(ins[0], ins[1], n_fft, hop, n_fft, c.w, "reflect", c.fold, c.scale), csd_tol, integers=n_fft == 256)
     add(f"coherence {n_fft} hop {hop}", 0, make, routes, inputs, coherence,
         lambda c, ins: csd_truth.coherence(ins[0], ins[1], n_fft, hop, n_fft, c.w, "reflect"), coherence_tol, integers=n_fft == 256)
 
@@ -882,7 +898,7 @@ def band_spectrogram(n_fft, hop, bands):
         c.plan.set_bands(c.W)
         assert c.plan.frames(length) == nf and c.plan.bands() == bands
         c.held_floor = None
-        return c
+        return restate(c, length, nf)
 
     def want(c, ins, power):
         return bandspec_truth.band_spectrogram(ins[0], c.W, n_fft, hop, n_fft, c.w, "reflect", power, power == 1)
@@ -892,15 +908,15 @@ def band_spectrogram(n_fft, hop, bands):
             # under the log the floor is the median of the truth at this input: about half of the values clamp
             c.floor = (float(np.median(want(c, ins, power))) if c.held_floor is None else c.held_floor) if log else 0.0
             x = api.put(ins[0])
-            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, length, BATCH, power, power == 1, LOG_MULT if log else 0.0, c.floor),
-                           (BATCH, nf, bands), ins[0].dtype)
+            return api.run(lambda out: c.plan.forward_ptr(api.ptr(x), out, c.length, c.batch, power, power == 1, LOG_MULT if log else 0.0, c.floor),
+                           (c.batch, c.nf, bands), ins[0].dtype)
         return run
 
     routes = fusion_routes("bandspec fused rows: real ", "bandspec composed: real ")
     for power in (1, 2):
-        add(f"bandspec {n_fft} {bands} bands power {power}", power, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power, False),
+        add(f"bandspec {n_fft} {bands} bands power {power}", power, make, routes, lambda c, rng: [gauss(rng, c.batch, c.length)], forward(power, False),
             lambda c, ins, power=power: want(c, ins, power), FOUR)
-        add(f"bandspec {n_fft} {bands} bands power {power} log", None, make, routes, lambda c, rng: [gauss(rng, BATCH, length)], forward(power, True),
+        add(f"bandspec {n_fft} {bands} bands power {power} log", None, make, routes, lambda c, rng: [gauss(rng, c.batch, c.length)], forward(power, True),
             lambda c, ins, power=power: np.maximum(want(c, ins, power), c.floor), FOUR, kd=power,
             err=lambda c, out, w: rel_l2(np.exp(out.astype(np.float64) / LOG_MULT), w), integers=power == 2,
             hold=lambda c, ins, power=power: setattr(c, "held_floor", float(np.median(want(c, ins, power)))))
@@ -957,7 +973,7 @@ def xcorr(L, n, cplx, composed_only=False):
     def run(api, c, ins):
         x, y = api.put(ins[0]), api.put(ins[1])
         dt = ins[0].dtype
-        return np.concatenate([api.run(lambda out: p.correlate_ptr(api.ptr(x), api.ptr(y), out, BATCH), (BATCH * p.lags(),), dt) for p in c.plan.plans])
+        return np.concatenate([api.run(lambda out: p.correlate_ptr(api.ptr(x), api.ptr(y), out, c.batch), (c.batch * p.lags(),), dt) for p in c.plan.plans])
 
     def truth_of(phat):
         return lambda c, ins: xcorr_truth.full(ins[0], ins[1], L, bool(phat))
@@ -966,12 +982,12 @@ def xcorr(L, n, cplx, composed_only=False):
         """tests/test_gpu_xcorr.py's measure, the worse of the two windows"""
         worst, at = 0.0, 0
         for first, lags in wins:
-            worst = max(worst, xcorr_truth.window_err(out[at:at + BATCH * lags].reshape(BATCH, lags), want, first, lags))
-            at += BATCH * lags
+            worst = max(worst, xcorr_truth.window_err(out[at:at + c.batch * lags].reshape(c.batch, lags), want, first, lags))
+            at += c.batch * lags
         return worst
 
     g = cgauss if cplx else gauss
-    white = lambda c, rng: [g(rng, BATCH, n), g(rng, BATCH, n)]  # noqa: E731
+    white = lambda c, rng: [g(rng, c.batch, n), g(rng, c.batch, n)]  # noqa: E731
     opposite = dict(signs={1: -1}, ks=lambda real: OPPOSITE[real])
     where = f"{L} n={n} {kind}" + (" composed" if composed_only else "")
     add(f"xcorr {where} scaled x", 1, make, routes_of(0), white, run, truth_of(0), THREE, scaled=(0,), err=err, integers=True)
@@ -980,7 +996,7 @@ def xcorr(L, n, cplx, composed_only=False):
 
     # PHAT: the spike rows of the family's tests and their bound, base x (sqrt(2 (kx^2 + ky^2)) + 1) under kx, ky <= 3
     def spikes(c, rng):
-        return list(xcorr_truth.spike_rows(rng, BATCH, n, 2, np.complex128 if cplx else np.float64))
+        return list(xcorr_truth.spike_rows(rng, c.batch, n, 2, np.complex128 if cplx else np.float64))
 
     def conditions(c, ins):
         c.kx, c.ky = xcorr_truth.kappa(ins[0], L), xcorr_truth.kappa(ins[1], L)
@@ -1005,18 +1021,20 @@ xcorr(255, 100, True)
 
 # fractional delay and delay-and-sum: three groups of C rows; the amplitude in the rows, or in the weights; never in the delays
 def delay(L, n, cplx, channels):
-    rows = BATCH * channels
-    delays = np.array((delay_truth.DELAYS * channels)[:rows])
+    def rows_of(c):
+        return c.batch * channels
 
     def make(api, real):
         return ctx_of(api.fa.Delay(n, L, real, not cplx, channels, api.device))
 
     def inputs(c, rng):
+        rows = rows_of(c)
+        delays = np.array((delay_truth.DELAYS * -(-rows // len(delay_truth.DELAYS)))[:rows])
         return [(cgauss if cplx else gauss)(rng, rows, n), delays, rng.uniform(0.5, 2.0, rows)]
 
     def run(api, c, ins):
         x, d, w = (api.put(a) for a in ins)
-        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), api.ptr(d), api.ptr(w), out, rows), (BATCH, n), ins[0].dtype)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), api.ptr(d), api.ptr(w), out, rows_of(c)), (c.batch, n), ins[0].dtype)
 
     def truth(c, ins):
         c.ins = ins
@@ -1044,25 +1062,32 @@ def convnd(shape):
     taps = tuple(min(3, n) for n in shape)
 
     def make(api, real):
-        return ctx_of(api.fa.FftConvNd(shape, real, api.device), where="emu" if api.device < 0 else "gpu")
+        return ctx_of(api.fa.FftConvNd(shape, real, api.device), where="emu" if api.device < 0 else "gpu", filters=FILTERS, window=None, filter_first=0)
 
     def run(api, c, ins):
         x, h = api.put(ins[0]), api.put(ins[1])
+        if c.window is not None:  # (in_shape, out_first, out_shape), stated by the caller; None: the handle as created
+            c.plan.set_window(*c.window)
         outs = []
         for correlate in (False, True):
-            c.plan.set_filters_ptr(api.ptr(h), taps, FILTERS, correlate)
-            outs.append(api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH), (BATCH,) + shape, ins[0].dtype))
+            c.plan.set_filters_ptr(api.ptr(h), taps, c.filters, correlate)
+            outs.append(api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, c.batch, c.filter_first), (c.batch,) + window_of(c)[2], ins[0].dtype))
         return np.stack(outs)
 
+    def window_of(c):
+        return c.window if c.window is not None else (shape, (0,) * len(shape), shape)
+
     def truth(c, ins):
-        return np.stack([convnd_truth.circular(ins[0], ins[1], shape, correlate) for correlate in (False, True)])
+        _, first, size = window_of(c)
+        return np.stack([convnd_truth.window(convnd_truth.circular(ins[0], ins[1], shape, correlate, c.filter_first), first, size)
+                         for correlate in (False, True)])
 
     def bound(c, d, real):
         return convnd_cases.bound(c, c.plan, real)
 
     routes = fusion_routes("convnd fused untangle: ", "convnd composed: ", lambda real: convnd_cases.has_fused(shape))
     for what, scaled in (("items", (0,)), ("taps", (1,))):
-        add(f"convnd {list(shape)} scaled {what}", 1, make, routes, lambda c, rng: [gauss(rng, BATCH, *shape), gauss(rng, FILTERS, *taps)], run, truth,
+        add(f"convnd {list(shape)} scaled {what}", 1, make, routes, lambda c, rng: [gauss(rng, c.batch, *window_of(c)[0]), gauss(rng, c.filters, *taps)], run, truth,
             None, scaled=scaled, bound=bound, integers=what == "items")
 
 
@@ -1098,8 +1123,8 @@ def nufft(n, point_set):
             plan = c.plan.plan
             v = api.put(ins[0])
             call = plan.to_modes_ptr if typ == 1 else plan.to_points_ptr
-            shape = (BATCH, plan.modes() if typ == 1 else plan.points())
-            return np.stack([api.run(lambda out: call(api.ptr(v), out, BATCH, sign, order), shape, ins[0].dtype) for sign, order in NUFFT_CALLS])
+            shape = (c.batch, plan.modes() if typ == 1 else plan.points())
+            return np.stack([api.run(lambda out: call(api.ptr(v), out, c.batch, sign, order), shape, ins[0].dtype) for sign, order in NUFFT_CALLS])
         return run
 
     def truth_of(typ):
@@ -1116,10 +1141,9 @@ def nufft(n, point_set):
         return err
 
     one = lambda d, real: 1.0  # noqa: E731
-    m = len(nufft_cases.points(point_set, n, 1e-6, "f64"))
-    add(f"nufft type 1 N={n} {point_set} scaled strengths", 1, make, routes, lambda c, rng: [cgauss(rng, BATCH, m)], run_of(1), truth_of(1), one,
+    add(f"nufft type 1 N={n} {point_set} scaled strengths", 1, make, routes, lambda c, rng: [cgauss(rng, c.batch, c.plan.plan.points())], run_of(1), truth_of(1), one,
         err=err_of(1), integers=True)
-    add(f"nufft type 2 N={n} {point_set} scaled modes", 1, make, routes, lambda c, rng: [cgauss(rng, BATCH, n)], run_of(2), truth_of(2), one,
+    add(f"nufft type 2 N={n} {point_set} scaled modes", 1, make, routes, lambda c, rng: [cgauss(rng, c.batch, n)], run_of(2), truth_of(2), one,
         err=err_of(2), integers=True)
 
 
@@ -1142,7 +1166,7 @@ def cepstrum(L, n, mode, log_mult):
 
     def run(api, c, ins):
         x = api.put(ins[0])
-        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, BATCH, log_mult, 0.0), (BATCH, n), ins[0].dtype)
+        return api.run(lambda out: c.plan.apply_ptr(api.ptr(x), out, c.batch, log_mult, 0.0), (c.batch, n), ins[0].dtype)
 
     def truth(c, ins):
         c.x = ins[0]
@@ -1171,7 +1195,7 @@ def cepstrum(L, n, mode, log_mult):
     name = cepstrum_cases.MODE_NAME[mode]
     routes = fusion_routes(f"cepstrum one-launch ({name}): ", f"cepstrum composed ({name}): ", lambda real: fused)
     samples = mode == cepstrum_truth.CEPSTRUM  # the minimum-phase input is a filter, not samples
-    add(f"cepstrum {L} n={n} {name} log_mult {log_mult:+d}", None, make, routes, lambda c, rng: [cepstrum_truth.rows(rng, BATCH, n, np.float64)], run, truth,
+    add(f"cepstrum {L} n={n} {name} log_mult {log_mult:+d}", None, make, routes, lambda c, rng: [cepstrum_truth.rows(rng, c.batch, n, np.float64)], run, truth,
         None, kd=1, err=err, bound=bound, conditions=conditions, identity=identity, integers=samples, edge=samples, edge_of=largest_bin)
 
 

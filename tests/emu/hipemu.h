@@ -20,6 +20,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -50,6 +51,7 @@ struct Tls {
   int* shfl = nullptr;  // one slot per thread of the block: cross-lane shuffles
   void** sched = nullptr;  // where the scheduler's stack pointer is parked while a fiber runs
   void** self = nullptr;   // where the running fiber's stack pointer is parked while it waits
+  int why = 0;             // why the running fiber yielded: 0 a block barrier, 1 a wave shuffle (Schedule below)
 };
 inline Tls& tls() {
   static thread_local Tls t;
@@ -132,7 +134,76 @@ __attribute__((naked, noinline, used)) static void hipemu_switch(void** /*save_s
 
 inline void syncthreads() {
   Tls& t = tls();
+  t.why = 0;
   hipemu_switch(t.self, *t.sched);
+}
+// a wave-level rendezvous (the two halves of __shfl_xor).  Under the default schedule the scheduler does not look at `why`: the
+// shuffle is two whole-block barriers, as it always was.
+inline void syncwave() {
+  Tls& t = tls();
+  t.why = 1;
+  hipemu_switch(t.self, *t.sched);
+}
+
+// ---- schedules: the order in which the threads of a block run between two barriers, and the order in which the blocks run.
+// HIPEMU_SCHEDULE="<threads>:<blocks>", read at every launch (tests/schedule_cases.py sets it per run).  Unset, empty or
+// "ascending:ascending" is the default, which is exactly what this file always did: threads in ascending order, blocks handed out in
+// ascending order to one worker per core, __shfl_xor as two block barriers.
+//   threads   ascending | descending | waves-descending (lanes ascending) | permutation-1 | permutation-2
+//   blocks    ascending | descending | permutation      (the last two on ONE worker: the order is then the order of execution)
+// Every other schedule runs wave by wave: a wave runs on through its shuffles -- which wait for its own 64 lanes only, as on the
+// hardware -- to its next block barrier before the next wave starts.  The permutations order the waves and, per wave, the lanes
+// (xorshift64* Fisher-Yates from a fixed seed: the same schedule every time).
+// What this shows: a hazard between two threads, or two blocks, whose two relative orders are both among the schedules and whose
+// stale value differs from the fresh one.  What it cannot show: anything the memory model decides (a missing wait or fence), and
+// blocks that must run at the same time (a kernel that waits on other workgroups hangs under a serial block order).
+struct Schedule {
+  enum Threads { T_ASC, T_DESC, T_WAVES_DESC, T_PERM1, T_PERM2 } threads = T_ASC;
+  enum Blocks { B_ASC, B_DESC, B_PERM } blocks = B_ASC;
+  bool is_default() const { return threads == T_ASC && blocks == B_ASC; }
+};
+inline Schedule schedule() {
+  Schedule s;
+  const char* e = getenv("HIPEMU_SCHEDULE");
+  if (!e || !*e) return s;
+  const char* colon = strchr(e, ':');
+  const std::string th = colon ? std::string(e, colon) : std::string(e), bl = colon ? std::string(colon + 1) : std::string("ascending");
+  static const char* const TH[] = {"ascending", "descending", "waves-descending", "permutation-1", "permutation-2"};
+  static const char* const BL[] = {"ascending", "descending", "permutation"};
+  int ti = -1, bi = -1;
+  for (int i = 0; i < 5; ++i) if (th == TH[i]) ti = i;
+  for (int i = 0; i < 3; ++i) if (bl == BL[i]) bi = i;
+  if (ti < 0 || bi < 0) { fprintf(stderr, "hipemu: HIPEMU_SCHEDULE=%s names no schedule\n", e); abort(); }  // a typo must not pass as the default
+  s.threads = (Schedule::Threads)ti;
+  s.blocks = (Schedule::Blocks)bi;
+  return s;
+}
+inline void permute(std::vector<unsigned>& v, uint64_t seed) {
+  uint64_t x = seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
+  for (size_t i = v.size(); i > 1; --i) {
+    x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+    std::swap(v[i - 1], v[(size_t)((x * 0x2545F4914F6CDD1Dull) >> 33) % i]);
+  }
+}
+// the order of the waves of a block and, flattened wave after wave, of each wave's lanes (thread indices)
+inline void thread_order(Schedule::Threads how, unsigned nthreads, std::vector<unsigned>& waves, std::vector<unsigned>& lanes) {
+  const unsigned nw = (nthreads + 63) / 64;
+  waves.resize(nw);
+  lanes.resize(nthreads);
+  for (unsigned w = 0; w < nw; ++w) waves[w] = w;
+  for (unsigned i = 0; i < nthreads; ++i) lanes[i] = i;
+  const uint64_t seed = how == Schedule::T_PERM1 ? 1 : 2;
+  if (how == Schedule::T_DESC || how == Schedule::T_WAVES_DESC) std::reverse(waves.begin(), waves.end());
+  if (how == Schedule::T_PERM1 || how == Schedule::T_PERM2) permute(waves, seed);
+  for (unsigned w = 0; w < nw; ++w) {
+    const unsigned lo = w * 64, hi = std::min(nthreads, lo + 64);
+    if (how == Schedule::T_DESC) std::reverse(lanes.begin() + lo, lanes.begin() + hi);
+    if (how == Schedule::T_PERM1 || how == Schedule::T_PERM2) {
+      std::vector<unsigned> v(lanes.begin() + lo, lanes.begin() + hi);
+      permute(v, seed * 1000003u + w + 17);
+      std::copy(v.begin(), v.end(), lanes.begin() + lo);
+    }
+  }
 }
 
 struct FiberArg {
@@ -201,6 +272,15 @@ void launch(dim3 grid, dim3 block, size_t smem_bytes, K kernel, A arg) {
   unsigned nworkers = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), nblocks);
   if (getenv("HIPEMU_THREADS")) nworkers = std::min<unsigned>(nworkers, (unsigned)atoi(getenv("HIPEMU_THREADS")));
   if (lds_trace_on()) nworkers = 1;
+  const Schedule sch = lds_trace_on() ? Schedule() : schedule();  // (the LDS trace models the default order)
+  std::vector<unsigned> block_order, wave_order, lane_order;
+  if (sch.blocks != Schedule::B_ASC) {  // one worker: the order below is the order of execution
+    nworkers = 1;
+    block_order.resize(nblocks);
+    for (unsigned b = 0; b < nblocks; ++b) block_order[b] = nblocks - 1 - b;
+    if (sch.blocks == Schedule::B_PERM) permute(block_order, 3);
+  }
+  if (!sch.is_default()) thread_order(sch.threads, nthreads, wave_order, lane_order);
   std::atomic<unsigned> next{0};
   auto worker = [&]() {
     const size_t STACK = 128 * 1024;
@@ -216,6 +296,7 @@ void launch(dim3 grid, dim3 block, size_t smem_bytes, K kernel, A arg) {
     for (;;) {
       unsigned b = next.fetch_add(1);
       if (b >= nblocks) break;
+      if (!block_order.empty()) b = block_order[b];
       Tls& t = tls();
       t.bdim = block; t.gdim = grid;
       t.bid = dim3(b % grid.x, (b / grid.x) % grid.y, b / (grid.x * grid.y));
@@ -228,6 +309,44 @@ void launch(dim3 grid, dim3 block, size_t smem_bytes, K kernel, A arg) {
         ctx[i] = fiber_prepare(stacks.data() + (size_t)i * STACK, STACK, &fargs[i]);
       }
       unsigned remaining = nthreads;
+      if (!sch.is_default()) {
+        // wave by wave up to the next block barrier; inside a wave, sweeps over its lanes in the schedule's order, each lane
+        // running to its next yield.  A sweep that ends with the whole wave at a shuffle releases it; one that ends with part
+        // of the wave there is a shuffle some lanes never reach.
+        enum : uint8_t { RUN, AT_BARRIER, AT_SHUFFLE, DONE };
+        std::vector<uint8_t> state(nthreads, RUN);
+        while (remaining) {
+          unsigned finished = 0;
+          for (unsigned w : wave_order) {
+            const unsigned lo = w * 64, hi = std::min(nthreads, lo + 64);
+            for (;;) {
+              for (unsigned k = lo; k < hi; ++k) {
+                const unsigned i = lane_order[k];
+                if (state[i] != RUN) continue;
+                t.tid = dim3(i % block.x, (i / block.x) % block.y, i / (block.x * block.y));
+                t.self = &ctx[i];
+                hipemu_switch(&sched, ctx[i]);
+                state[i] = fargs[i].done ? DONE : t.why == 1 ? AT_SHUFFLE : AT_BARRIER;
+              }
+              unsigned shuffling = 0;
+              for (unsigned i = lo; i < hi; ++i) shuffling += state[i] == AT_SHUFFLE;
+              if (!shuffling) break;
+              if (shuffling != hi - lo) {
+                fprintf(stderr, "hipemu: divergent __shfl_xor in block %u, wave %u (%u of %u lanes reached it)\n", b, w, shuffling, hi - lo);
+                abort();
+              }
+              for (unsigned i = lo; i < hi; ++i) state[i] = RUN;
+            }
+            for (unsigned i = lo; i < hi; ++i) finished += state[i] == DONE;
+          }
+          if (finished != 0 && finished != remaining) {
+            fprintf(stderr, "hipemu: divergent __syncthreads() in block %u (%u of %u threads exited)\n", b, finished, remaining);
+            abort();
+          }
+          remaining -= finished;
+          for (unsigned i = 0; i < nthreads; ++i) if (state[i] == AT_BARRIER) state[i] = RUN;
+        }
+      }
       while (remaining) {
         unsigned ran = 0, finished = 0;
         for (unsigned i = 0; i < nthreads; ++i) {
@@ -290,14 +409,15 @@ void launch(dim3 grid, dim3 block, size_t smem_bytes, K kernel, A arg) {
 #define blockDim (hipemu::tls().bdim)
 #define gridDim (hipemu::tls().gdim)
 inline void __syncthreads() { hipemu::syncthreads(); }
-// wave shuffle: every thread of the block must reach it (publish, barrier, read the partner's slot, barrier)
+// wave shuffle: publish, rendezvous, read the partner's slot, rendezvous.  The rendezvous is the wave's own under every schedule but
+// the default, where it is the whole block's (hipemu::Schedule)
 inline int __shfl_xor(int v, int lane_mask) {
   hipemu::Tls& t = hipemu::tls();
   const unsigned i = t.tid.x + t.bdim.x * (t.tid.y + t.bdim.y * t.tid.z);
   t.shfl[i] = v;
-  hipemu::syncthreads();
+  hipemu::syncwave();
   const int r = t.shfl[(i & ~63u) | ((i ^ (unsigned)lane_mask) & 63u)];
-  hipemu::syncthreads();
+  hipemu::syncwave();
   return r;
 }
 

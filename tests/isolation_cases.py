@@ -70,11 +70,11 @@ def lines(ctx, a):
 
 
 def lag_windows(ctx, a):
-    """the output of a cross-correlation case: its lag windows one after the other, each cases.BATCH rows"""
+    """the output of a cross-correlation case: its lag windows one after the other, each ctx.batch rows"""
     blocks, at = [], 0
     for p in ctx.plan.plans:
-        blocks.append(a[at:at + cases.BATCH * p.lags()].reshape(cases.BATCH, p.lags()))
-        at += cases.BATCH * p.lags()
+        blocks.append(a[at:at + ctx.batch * p.lags()].reshape(ctx.batch, p.lags()))
+        at += ctx.batch * p.lags()
     assert at == a.size
     return blocks
 
