@@ -596,6 +596,39 @@ struct NufftArgs {
   double beta;                // 2.30 w
 };
 
+// ---- non-uniform FFT, 2-D, types 1 and 2 (kernels_nufft2d.h; Nufft2dPlan, nufft2d_plan.h): m points shared by the items of a batch,
+// bucketed by the wrapped first cell of axis 1 and sorted by the axis-2 grid coordinate within a bucket; fine-grid items of l1 x l2
+// cells, rows of m strengths, items of n1 x n2 modes, all complex T, the last axis contiguous.
+// nufft2d_spread_kernel / nufft2d_interp_kernel: one lane per (item block, cell) / (item block, sorted point); `blocks` item blocks of
+// RB items from the launch's first item on, `per` workgroups an item block.  Every item has a buffer descriptor of its own (item bytes
+// <= 2^31 - 1).  nufft2d_deconv_kernel / nufft2d_amplify_kernel: one lane per output value over a flat index; byte offsets are 32-bit
+// (at most REAL_LAUNCH_BYTES of either side per launch).  nufft2d_table_kernel: one lane per point, 2 w weights each.
+// The row block NUFFT_RB, the widths NUFFT_MIN_W .. NUFFT_MAX_W_* and NUFFT_DECONV / NUFFT_AMPLIFY are the 1-D handle's.
+struct Nufft2dArgs {
+  const void* in; void* out;  // spread: strengths -> grid; interp: grid -> strengths; deconv: grid -> modes; amplify: modes -> grid
+  const uint32_t* r1;         // [m] first cell of axis 1 of sorted point p, modulo l1: its bucket
+  const int32_t* i02;         // [m] first cell of axis 2 (may lie outside [0, l2): the footprint wraps)
+  const void* d1;             // [m] reals T: i0_1 - g_1, in [-w/2, -w/2 + 1)
+  const void* d2;             // [m] reals T: i0_2 - g_2
+  const uint32_t* perm;       // [m] the caller's index of sorted point p
+  const uint32_t* first;      // [l1][ne2]: first[r][e + w] = sorted index of the first point of bucket r with i0_2 >= e, e in [-w, l2 + w]
+  const void* wtab;           // tabulated route: [2][w][m] reals T, weight of tap t of axis d of sorted point p at (d w + t) m + p; null: evaluated
+  const void* inv1;           // [n1 / 2 + 1] reals T: 1 / phihat_1(|k1|)
+  const void* inv2;           // [n2 / 2 + 1] reals T: 1 / phihat_2(|k2|)
+  uint32_t l1, l2, m, n1, n2, w;
+  uint32_t ne2;               // l2 + 2 w + 1: the row length of first[]
+  uint32_t cells;             // l1 l2
+  uint32_t blocks, per;       // spread, interp: item blocks of this launch; workgroups an item block
+  uint32_t per_m, per_l;      // blk / per = (umulhi(blk, per_m) + blk) >> per_l
+  uint32_t l2_m, l2_l;        // spread: cell / l2
+  uint32_t total;             // deconv, amplify: values of this launch; table: m
+  uint32_t item_m, item_l;    // deconv: idx / (n1 n2); amplify: idx / (l1 l2)
+  uint32_t row_m, row_l;      // deconv: rem / n2; amplify: rem / l2
+  uint32_t in_bytes, out_bytes;  // deconv, amplify: descriptor ranges of this launch
+  uint32_t order;             // 0: both axes ascending from -floor(n/2); 1: both in FFT order
+  double beta;                // 2.30 w
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

@@ -24,6 +24,45 @@
 
 namespace fourier_hip {
 
+// 1 / phihat(|k|) for |k| <= n / 2 of the kernel of width w on a grid of l cells, cast to T (NufftPlan, and per axis Nufft2dPlan).
+// With t = (w/2) sin(theta) the integrand is entire in theta,
+//   phihat(k) = w * integral over [0, pi/2] of exp(beta (cos(theta) - 1)) cos(a sin(theta)) cos(theta),  a = pi k w / l,
+// so Gauss-Legendre converges geometrically: q = 32 + floor(beta + pi w / 4) nodes (the integrand's widest oscillation over the
+// interval is (beta + a) pi / 2 radians, a <= pi w / 4).  Nodes, weights and the integrand are formed in long double: in f64 the
+// rounding of a node alone, times the integrand's logarithmic slope of up to beta + a = 50, costs 5e-15 of phihat at w = 16; in
+// long double the rule agrees with itself on 200 nodes within 1e-15 at every width (tests/nufft_truth.py holds the same rule).
+template <typename T> static std::vector<T> nufft_inverse_phihat(size_t n, int w, size_t l) {
+  typedef long double R;
+  const R pi = std::acos((R)-1), beta = (R)2.30 * (R)w;
+  const int q = 32 + (int)(2.30 * (double)w + M_PI * (double)w / 4.0);
+  std::vector<R> st(q), g(q);  // sin(theta_i), and the k-independent factor with the quadrature weight and the interval
+  for (int i = 0; i < q; ++i) {  // Newton's iteration on P_q from the Chebyshev guess
+    R x = std::cos(pi * ((R)i + (R)0.75) / ((R)q + (R)0.5)), dp = 1;
+    for (int it = 0; it < 100; ++it) {
+      R p0 = 1, p1 = x;
+      for (int j = 2; j <= q; ++j) { const R p2 = ((2 * j - 1) * x * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
+      dp = q * (x * p1 - p0) / (x * x - 1);
+      const R dx = p1 / dp;
+      x -= dx;
+      if (std::fabs(dx) < (R)1e-19) break;
+    }
+    R p0 = 1, p1 = x;
+    for (int j = 2; j <= q; ++j) { const R p2 = ((2 * j - 1) * x * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
+    dp = q * (x * p1 - p0) / (x * x - 1);
+    const R weight = 2 / ((1 - x * x) * dp * dp), theta = pi / 4 * (x + 1);
+    st[i] = std::sin(theta);
+    g[i] = pi / 4 * weight * std::exp(beta * (std::cos(theta) - 1)) * std::cos(theta) * (R)w;
+  }
+  std::vector<T> inv(n / 2 + 1);
+  for (size_t k = 0; k < inv.size(); ++k) {
+    const R a = pi * (R)k * (R)w / (R)l;
+    R s = 0;
+    for (int i = 0; i < q; ++i) s += g[i] * std::cos(a * st[i]);
+    inv[k] = (T)(double)(1 / s);
+  }
+  return inv;
+}
+
 // The scratch bound of a NufftPlan is RealPlan's (REAL_SCRATCH_BYTES).  The experiments library and the emulator build read
 // FOURIER_NUFFT_SCRATCH_BYTES at create instead (the chunk-walk test).
 template <typename T> class NufftPlan : public HandleBase {
@@ -47,7 +86,7 @@ template <typename T> class NufftPlan : public HandleBase {
     scratch_cap_ = scratch_bound("FOURIER_NUFFT_SCRATCH_BYTES", REAL_SCRATCH_BYTES);
     launch_bytes_ = launch_bound("FOURIER_LAUNCH_BYTES", REAL_LAUNCH_BYTES);
     launch_items_ = launch_bound("FOURIER_LAUNCH_ITEMS", (size_t)1 << 30);
-    inv_phihat_.upload(deconvolution_factors());
+    inv_phihat_.upload(nufft_inverse_phihat<T>(n_, w_, l_));
     // Which route is the default: the project's rule is that the tabulated route becomes the default only if it beats the evaluated one
     // at every measured shape of both types beyond the larger max - min of the two arms.  It did so at none of the ten lines of the
     // committed run (0.98 - 1.11 of the evaluated route's time; tools/nufft_bench.py, profiles/nufft/nufft_bench.jsonl, DESIGN.md
@@ -217,44 +256,6 @@ template <typename T> class NufftPlan : public HandleBase {
     if (!have_points_) throw EngineError(INVALID, "no points: call set_points first");
     if (batch > ((size_t)1 << 62) / (std::max(ivals, ovals) * ELEM + 1)) throw EngineError(INVALID, "batch too large");
     check_buffers(d_in, d_out, batch * ivals * ELEM, batch * ovals * ELEM, ELEM, false);
-  }
-
-  // 1 / phihat(|k|) for |k| <= n / 2, cast to T.  With t = (w/2) sin(theta) the integrand is entire in theta,
-  //   phihat(k) = w * integral over [0, pi/2] of exp(beta (cos(theta) - 1)) cos(a sin(theta)) cos(theta),  a = pi k w / l,
-  // so Gauss-Legendre converges geometrically: q = 32 + floor(beta + pi w / 4) nodes (the integrand's widest oscillation over the
-  // interval is (beta + a) pi / 2 radians, a <= pi w / 4).  Nodes, weights and the integrand are formed in long double: in f64 the
-  // rounding of a node alone, times the integrand's logarithmic slope of up to beta + a = 50, costs 5e-15 of phihat at w = 16; in
-  // long double the rule agrees with itself on 200 nodes within 1e-15 at every width (tests/nufft_truth.py holds the same rule).
-  std::vector<T> deconvolution_factors() const {
-    typedef long double R;
-    const R pi = std::acos((R)-1), beta = (R)2.30 * (R)w_;
-    const int q = 32 + (int)(2.30 * (double)w_ + M_PI * (double)w_ / 4.0);
-    std::vector<R> st(q), g(q);  // sin(theta_i), and the k-independent factor with the quadrature weight and the interval
-    for (int i = 0; i < q; ++i) {  // Newton's iteration on P_q from the Chebyshev guess
-      R x = std::cos(pi * ((R)i + (R)0.75) / ((R)q + (R)0.5)), dp = 1;
-      for (int it = 0; it < 100; ++it) {
-        R p0 = 1, p1 = x;
-        for (int j = 2; j <= q; ++j) { const R p2 = ((2 * j - 1) * x * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
-        dp = q * (x * p1 - p0) / (x * x - 1);
-        const R dx = p1 / dp;
-        x -= dx;
-        if (std::fabs(dx) < (R)1e-19) break;
-      }
-      R p0 = 1, p1 = x;
-      for (int j = 2; j <= q; ++j) { const R p2 = ((2 * j - 1) * x * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
-      dp = q * (x * p1 - p0) / (x * x - 1);
-      const R weight = 2 / ((1 - x * x) * dp * dp), theta = pi / 4 * (x + 1);
-      st[i] = std::sin(theta);
-      g[i] = pi / 4 * weight * std::exp(beta * (std::cos(theta) - 1)) * std::cos(theta) * (R)w_;
-    }
-    std::vector<T> inv(n_ / 2 + 1);
-    for (size_t k = 0; k < inv.size(); ++k) {
-      const R a = pi * (R)k * (R)w_ / (R)l_;
-      R s = 0;
-      for (int i = 0; i < q; ++i) s += g[i] * std::cos(a * st[i]);
-      inv[k] = (T)(double)(1 / s);
-    }
-    return inv;
   }
 
   NufftArgs base_args() const {

@@ -2298,6 +2298,160 @@ def nufft2(x, f, eps=1e-6, isign=1):
     return plan.to_points(f.contiguous(), isign)
 
 
+class Nufft2d(_Handle):
+    """Batched 2-D non-uniform FFT of types 1 and 2 (include/fourier.h, fourier_hip_nufft2d_*) on device memory, in C order, the points
+    shared by the items of a batch.  For n_modes = (N1, N2) modes k_d = -floor(N_d/2) .. ceil(N_d/2) - 1 and M points (x1_j, x2_j)
+    (set_points; any finite reals, taken modulo 2 pi per coordinate; coordinate d pairs with axis d):
+        to_modes  (type 1)   f[b, k1, k2] = sum_j c[b, j] exp(i isign (k1 x1_j + k2 x2_j))        (..., M) -> (..., N1, N2)
+        to_points (type 2)   c[b, j] = sum_{k1,k2} f[b, k1, k2] exp(i isign (k1 x1_j + k2 x2_j))  (..., N1, N2) -> (..., M)
+    with no scale factor; to_points with isign s is the exact adjoint of to_modes with -s.  `eps` is the requested relative accuracy:
+    the kernel width is w = ceil(log10(1 / eps)) + 1 for both axes, clamped to 2 .. 8 at f32 and 2 .. 16 at f64, and the relative L2
+    error of a call is about 2 x 10^(1 - w) plus the rounding of the precision.  modeord 0 stores both axes with k ascending, 1 both in
+    FFT order."""
+
+    _prefix = "fourier_hip_nufft2d_"
+    _destroy = "fourier_hip_nufft2d_destroy"
+
+    def __init__(self, n_modes, eps=1e-6, real="f32", device=-1):
+        import math
+
+        try:
+            n1, n2 = (int(v) for v in n_modes)
+        except (TypeError, ValueError):
+            raise ValueError(f"need n_modes = (n1, n2), got {n_modes!r}") from None
+        eps = float(eps)
+        if n1 < 1 or n2 < 1:
+            raise ValueError(f"need n1, n2 >= 1, got {(n1, n2)}")
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"need a finite eps > 0, got {eps}")
+        self._create(real, f"nufft2d plan of {n1} x {n2} modes, eps {eps}", n1, n2, eps, int(device))
+        self._n, self.eps = (n1, n2), eps
+
+    def modes(self):
+        return self._n
+
+    def points(self):
+        return int(self._fn("points")(self._h))
+
+    def set_option(self, key, value):
+        """"table": 0 = the weights are evaluated in the kernels, 1 = they are read from a table written once per set_points."""
+        self._call("set_option", key.encode(), int(value), message=f"bad option {key}={value}")
+
+    def set_points_ptr(self, h_x1, h_x2, m, stream=0):
+        """`m` float64 values at each of the HOST addresses h_x1, h_x2.  Waits for `stream`."""
+        self._call("set_points", h_x1, h_x2, int(m), stream)
+
+    def set_points(self, x1, x2):
+        """Two numpy arrays or torch tensors (any device, any real dtype) of M coordinates each: copied to the host as float64.  Every
+        coordinate must be finite.  Replaces the points in use; waits for the current stream."""
+        import numpy as np
+
+        hosts = []
+        for x in (x1, x2):
+            if _is_torch(x):
+                x = x.detach().cpu().numpy()
+            elif not isinstance(x, np.ndarray):
+                raise TypeError("points must be numpy arrays or torch tensors")
+            if x.dtype.kind not in "fiu":
+                raise TypeError(f"points must be real, got {x.dtype}")
+            hosts.append(np.ascontiguousarray(x, dtype=np.float64).ravel())
+        if hosts[0].size != hosts[1].size:
+            raise ValueError(f"x1 and x2 must have the same number of points, got {hosts[0].size} and {hosts[1].size}")
+        if not (np.isfinite(hosts[0]).all() and np.isfinite(hosts[1]).all()):
+            raise ValueError("every point must be finite")
+        stream = 0
+        try:
+            import torch
+
+            if torch.cuda.is_available():
+                stream = torch.cuda.current_stream().cuda_stream
+        except Exception:
+            pass
+        m = hosts[0].size
+        self.set_points_ptr(hosts[0].ctypes.data if m else None, hosts[1].ctypes.data if m else None, m, stream)
+
+    def to_modes_ptr(self, d_in, d_out, batch, isign=-1, modeord=0, stream=0):
+        """`batch` rows of points() complex values at d_in -> `batch` items of N1 x N2 complex values at d_out, enqueued on `stream`."""
+        self._call("to_modes_batch", d_in, d_out, int(batch), int(isign), int(modeord), stream)
+
+    def to_points_ptr(self, d_in, d_out, batch, isign=1, modeord=0, stream=0):
+        """`batch` items of N1 x N2 complex values at d_in -> `batch` rows of points() complex values at d_out, enqueued on `stream`."""
+        self._call("to_points_batch", d_in, d_out, int(batch), int(isign), int(modeord), stream)
+
+    def _run(self, op, x, itail, otail, isign, modeord, out):
+        import torch
+
+        cdt = _torch_dtypes(self.real)[1]
+        _require_cuda(x, cdt)
+        if x.dim() < len(itail) or tuple(x.shape[x.dim() - len(itail):]) != itail:
+            raise ValueError(f"trailing dimensions must be {itail}, got {tuple(x.shape)}")
+        if isign not in (1, -1):
+            raise ValueError(f"isign must be +1 or -1, got {isign}")
+        if modeord not in (0, 1):
+            raise ValueError(f"modeord must be 0 or 1, got {modeord}")
+        lead = tuple(x.shape[:x.dim() - len(itail)])
+        shape = lead + otail
+        batch = 1
+        for s in lead:
+            batch *= int(s)
+        if out is None:
+            out = torch.empty(shape, dtype=cdt, device=x.device)
+        else:
+            _require_out(out, shape, cdt, x.device)
+        if batch:
+            self._call(op, x.data_ptr(), out.data_ptr(), batch, int(isign), int(modeord), _stream(x))
+        return out
+
+    def to_modes(self, c, isign=-1, modeord=0, out=None):
+        """A contiguous (..., points()) complex CUDA tensor of the handle's precision -> a new (..., N1, N2) tensor, or `out` (which may
+        not overlap `c`), on the current stream."""
+        return self._run("to_modes_batch", c, (self.points(),), self._n, isign, modeord, out)
+
+    def to_points(self, f, isign=1, modeord=0, out=None):
+        """A contiguous (..., N1, N2) complex CUDA tensor of the handle's precision -> a new (..., points()) tensor, or `out` (which may
+        not overlap `f`), on the current stream."""
+        return self._run("to_points_batch", f, self._n, (self.points(),), isign, modeord, out)
+
+
+def create_nufft2d_f32(n_modes, eps=1e-6, device=-1):
+    return Nufft2d(n_modes, eps, "f32", device)
+
+
+def create_nufft2d_f64(n_modes, eps=1e-6, device=-1):
+    return Nufft2d(n_modes, eps, "f64", device)
+
+
+def _nufft2d_plan(x1, x2, v, n_modes, eps):
+    """nufft2d1 / nufft2d2: the cached handle of (n_modes, eps, precision, device) with the points (x1, x2) set"""
+    if not (_is_torch(v) and v.is_cuda and _precision(v.dtype) is not None and not _precision(v.dtype)[1]):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor")
+    plan = _cached_plan(Nufft2d, (int(n_modes[0]), int(n_modes[1])), float(eps), _precision(v.dtype)[0], int(_device_index(v)))
+    plan.set_points(x1, x2)
+    return plan
+
+
+def nufft2d1(x1, x2, c, n_modes, eps=1e-6, isign=-1):
+    """2-D type 1 (points to modes): f[..., k1, k2] = sum_j c[..., j] exp(i isign (k1 x1[j] + k2 x2[j])), k_d = -floor(N_d/2) ..
+    ceil(N_d/2) - 1 ascending, n_modes = (N1, N2), for M points (x1, x2) (numpy or torch, any device, copied to the host as float64)
+    and a CUDA complex64 / complex128 tensor `c` of shape (..., M), whose leading dimensions are a batch that shares the points; on the
+    current stream.  Returns a new (..., N1, N2) tensor.  One cached Nufft2d handle per (n_modes, eps, dtype, device); every call sets
+    its points, a set-up step that waits for the stream: keep a Nufft2d of your own where the points stay."""
+    if not (_is_torch(c) and c.dim() >= 1):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor of at least one dimension")
+    plan = _nufft2d_plan(x1, x2, c, n_modes, eps)
+    return plan.to_modes(c.contiguous(), isign)
+
+
+def nufft2d2(x1, x2, f, eps=1e-6, isign=1):
+    """2-D type 2 (modes to points): c[..., j] = sum_{k1,k2} f[..., k1, k2] exp(i isign (k1 x1[j] + k2 x2[j])) for a CUDA complex64 /
+    complex128 tensor `f` of shape (..., N1, N2) holding the modes ascending on both axes, and M points (x1, x2) (as for nufft2d1); on
+    the current stream.  Returns a new (..., M) tensor.  The cached handle and its set-up step are nufft2d1's."""
+    if not (_is_torch(f) and f.dim() >= 2 and f.shape[-1] >= 1 and f.shape[-2] >= 1):
+        raise ValueError("expected a tensor whose two mode dimensions have length >= 1")
+    plan = _nufft2d_plan(x1, x2, f, (int(f.shape[-2]), int(f.shape[-1])), eps)
+    return plan.to_points(f.contiguous(), isign)
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

@@ -1773,6 +1773,84 @@ const char *fourier_hip_nufft_describe_double(const FOURIER_STRUCT fourier_nufft
 int fourier_hip_nufft_last_status_float(const FOURIER_STRUCT fourier_nufft_float *);
 int fourier_hip_nufft_last_status_double(const FOURIER_STRUCT fourier_nufft_double *);
 
+/* ---------------- non-uniform FFT, 2-D, types 1 and 2 (extension; the reference has none) ----------
+ * FINUFFT's 2-D type 1 and type 2 in C order with the points shared by the items of a batch.  A handle is created for n1 x n2 modes
+ * (each >= 1) and a requested accuracy eps; fourier_hip_nufft2d_set_points_* gives it M >= 0 points (x1_j, x2_j), any finite reals,
+ * taken modulo 2 pi per coordinate.  Coordinate d pairs with axis d of the mode array; k_d runs over -floor(n_d/2) .. ceil(n_d/2) - 1.
+ * With s = `sign`, +1 or -1 per call:
+ *   to_modes  (type 1)   f[b][k1][k2] = sum_j c[b][j] exp(i s (k1 x1_j + k2 x2_j))        `batch` rows of M in, `batch` items of n1 x n2 out
+ *   to_points (type 2)   c[b][j] = sum_{k1,k2} f[b][k1][k2] exp(i s (k1 x1_j + k2 x2_j))  `batch` items of n1 x n2 in, `batch` rows of M out
+ * on DEVICE memory, interleaved complex T, the last mode axis contiguous, item b at element offset b*M or b*n1*n2.  `order` 0 stores
+ * both axes with k ascending, 1 both in FFT order (numpy's ifftshift over both axes of order 0).  There is no scale factor; to_points
+ * with sign s is the exact adjoint of to_modes with sign -s.
+ * The algorithm is fourier_hip_nufft_*'s per axis: the same kernel phi with beta = 2.30 w, the same w = ceil(log10(1 / eps)) + 1 clamped
+ * to 2 .. 8 (float) or 2 .. 16 (double), one w for both axes; L_d is the smallest 2^a 3^b 5^c >= max(2 n_d, 2 w); a point's weight on
+ * cell (i1, i2) is the product of its two 1-D weights, and the deconvolution factor is 1 / (phihat_1(|k1|) phihat_2(|k2|)), two 1-D
+ * tables from the same quadrature.  to_modes spreads onto grid items of L1 x L2 (a gather over the points, bucketed by their first
+ * axis-1 cell and sorted by their axis-2 coordinate: no atomics), transforms the rows of L2 and then axis 1 in place (FFT for s = -1,
+ * UNSCALED_IFFT for s = +1), picks the n1 x n2 modes and multiplies by 1 / phihat; to_points writes f / phihat into a zeroed grid,
+ * transforms and interpolates at the points.  The relative L2 error of a call against the direct sum is about 2 x 10^(1 - w), plus
+ * the rounding of T.
+ * fourier_hip_nufft2d_set_points_*: h_x1 and h_x2 each point to m doubles on the HOST, for both precisions.  A set-up call like
+ * fourier_hip_nufft_set_points_*: it waits for `stream`, sorts (stable: equal points keep the caller's order), uploads the tables and
+ * waits again.  Calling it again replaces the points; m == 0 is valid (to_modes then writes zeros, to_points writes nothing).  A NaN
+ * or infinite coordinate in either array, m > 2^31 - 1, m * 2 * sizeof(T) > 2^30, a NULL pointer with m > 0 or one not aligned to 8
+ * bytes give FOURIER_HIP_INVALID_ARGUMENT and leave the points as they were; so does an allocation or copy that fails (the new tables
+ * replace the old ones only when all of them are complete).
+ * A transform call before any set_points, sign other than +1 / -1, order other than 0 / 1, a NULL or misaligned (2*sizeof(T)) buffer
+ * and ANY overlap of input and output give FOURIER_HIP_INVALID_ARGUMENT and write nothing.  batch == 0 is a successful no-op.
+ * n1 == 0 or n2 == 0, eps <= 0 or not finite, n1 * n2 items above 2^30 bytes or a grid item above 2^31 bytes: create fails.
+ * Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Option "table" (fourier_hip_nufft2d_set_option_*): 0 = "nufft2d evaluated", the weights are evaluated in the two hot kernels with
+ * the accurate exp and sqrt; 1 = "nufft2d tabulated", a set-up kernel writes the 2 x w x M weights once (at set_points, or at set_option
+ * on the null stream when points are set) and the hot kernels read them.  The two routes agree to rounding.  The default is 0: the
+ * tabulated route beat the evaluated one at one of the ten measured lines only ("Non-uniform FFT, 2-D").  fourier_hip_nufft2d_describe_* begins "nufft2d evaluated: " or "nufft2d
+ * tabulated: ", then "w <w>, L <L1> x <L2>, " and the descriptions of the row plan and of the axis-1 route.
+ * The plan owns a scratch of fine-grid items of at most 1 GiB (never less than one item) and walks larger batches in chunks; the first
+ * call with a batch larger than any before allocates it unless fourier_hip_nufft2d_reserve_* was called for at least that batch.  No
+ * atomics and a summation order fixed by the points: the result is the same on repetition.  A NULL handle gives
+ * FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_nufft2d_modes1_* / _modes2_* / _points_* and "" from fourier_hip_nufft2d_describe_*.
+ * Handles are Send, not Sync, like the complex ones; status of the last call: fourier_hip_nufft2d_last_status_*. */
+struct fourier_nufft2d_float;
+struct fourier_nufft2d_double;
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_nufft2d_float *fourier_hip_nufft2d_create_float(FOURIER_SIZE_TYPE n1, FOURIER_SIZE_TYPE n2, double eps, int device);
+struct fourier_nufft2d_double *fourier_hip_nufft2d_create_double(FOURIER_SIZE_TYPE n1, FOURIER_SIZE_TYPE n2, double eps, int device);
+/* NULL is a no-op. */
+void fourier_hip_nufft2d_destroy_float(FOURIER_STRUCT fourier_nufft2d_float *);
+void fourier_hip_nufft2d_destroy_double(FOURIER_STRUCT fourier_nufft2d_double *);
+/* n1, n2, and the M of the last set_points (0 before any); 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_modes1_float(const FOURIER_STRUCT fourier_nufft2d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_modes1_double(const FOURIER_STRUCT fourier_nufft2d_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_modes2_float(const FOURIER_STRUCT fourier_nufft2d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_modes2_double(const FOURIER_STRUCT fourier_nufft2d_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_points_float(const FOURIER_STRUCT fourier_nufft2d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft2d_points_double(const FOURIER_STRUCT fourier_nufft2d_double *);
+/* two arrays of m doubles on the host, for both precisions. */
+int fourier_hip_nufft2d_set_points_float(FOURIER_STRUCT fourier_nufft2d_float *, const double *h_x1, const double *h_x2,
+                                         FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft2d_set_points_double(FOURIER_STRUCT fourier_nufft2d_double *, const double *h_x1, const double *h_x2,
+                                          FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft2d_to_modes_batch_float(const FOURIER_STRUCT fourier_nufft2d_float *, const void *d_in, void *d_out,
+                                             FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft2d_to_modes_batch_double(const FOURIER_STRUCT fourier_nufft2d_double *, const void *d_in, void *d_out,
+                                              FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft2d_to_points_batch_float(const FOURIER_STRUCT fourier_nufft2d_float *, const void *d_in, void *d_out,
+                                              FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft2d_to_points_batch_double(const FOURIER_STRUCT fourier_nufft2d_double *, const void *d_in, void *d_out,
+                                               FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft2d_reserve_float(const FOURIER_STRUCT fourier_nufft2d_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_nufft2d_reserve_double(const FOURIER_STRUCT fourier_nufft2d_double *, FOURIER_SIZE_TYPE batch);
+/* "table": 0 / 1.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_nufft2d_set_option_float(FOURIER_STRUCT fourier_nufft2d_float *, const char *key, long long value);
+int fourier_hip_nufft2d_set_option_double(FOURIER_STRUCT fourier_nufft2d_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_nufft2d_describe_float(const FOURIER_STRUCT fourier_nufft2d_float *);
+const char *fourier_hip_nufft2d_describe_double(const FOURIER_STRUCT fourier_nufft2d_double *);
+int fourier_hip_nufft2d_last_status_float(const FOURIER_STRUCT fourier_nufft2d_float *);
+int fourier_hip_nufft2d_last_status_double(const FOURIER_STRUCT fourier_nufft2d_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -2412,6 +2490,55 @@ template <typename T> struct nufft;
 FOURIER_DEFINE_CXX_NUFFT_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_NUFFT_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_NUFFT_WRAPPER
+
+/* non-uniform FFT, 2-D types 1 and 2, on device memory (extension): fourier::nufft2d<float> / <double> */
+template <typename T> struct nufft2d;
+
+#define FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER(T, SUFFIX)                                              \
+  template <> struct nufft2d<T> {                                                                  \
+    nufft2d(std::size_t n1, std::size_t n2, double eps = 1e-6, int device = -1)                    \
+        : impl(::fourier::c::fourier_hip_nufft2d_create_##SUFFIX(n1, n2, eps, device),             \
+               ::fourier::c::fourier_hip_nufft2d_destroy_##SUFFIX) {}                              \
+    nufft2d() = delete;                                                                            \
+    nufft2d(const nufft2d &) = delete;                                                             \
+    nufft2d(nufft2d &&) = default;                                                                 \
+    nufft2d &operator=(const nufft2d &) = delete;                                                  \
+    nufft2d &operator=(nufft2d &&) = default;                                                      \
+    ~nufft2d() = default;                                                                          \
+    std::size_t modes1() const { return ::fourier::c::fourier_hip_nufft2d_modes1_##SUFFIX(impl.get()); }\
+    std::size_t modes2() const { return ::fourier::c::fourier_hip_nufft2d_modes2_##SUFFIX(impl.get()); }\
+    std::size_t points() const { return ::fourier::c::fourier_hip_nufft2d_points_##SUFFIX(impl.get()); }\
+    /* two arrays of m doubles on the HOST; a set-up call that waits for `stream` */               \
+    int set_points(const double *h_x1, const double *h_x2, std::size_t m, void *stream = nullptr) {\
+      return ::fourier::c::fourier_hip_nufft2d_set_points_##SUFFIX(impl.get(), h_x1, h_x2, m, stream);\
+    }                                                                                              \
+    /* type 1: `batch` rows of points() strengths -> `batch` items of modes1() x modes2() */       \
+    int to_modes_device(const void *d_in, void *d_out, std::size_t batch, int sign = -1,           \
+                        int order = 0, void *stream = nullptr) const {                             \
+      return ::fourier::c::fourier_hip_nufft2d_to_modes_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    /* type 2: `batch` items of modes1() x modes2() -> `batch` rows of points() values */          \
+    int to_points_device(const void *d_in, void *d_out, std::size_t batch, int sign = 1,           \
+                         int order = 0, void *stream = nullptr) const {                            \
+      return ::fourier::c::fourier_hip_nufft2d_to_points_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_nufft2d_reserve_##SUFFIX(impl.get(), batch);                \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_nufft2d_set_option_##SUFFIX(impl.get(), key, value);        \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_nufft2d_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_nufft2d_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_nufft2d_##SUFFIX,                                      \
+                      void (*)(::fourier::c::fourier_nufft2d_##SUFFIX *)> impl;                    \
+  };
+FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
