@@ -131,6 +131,7 @@ template <typename T> class Plan : public HandleBase {
       // prime factors up to 13 without an ahead-of-time route: the kernels of an earlier "specialise" from the on-disk cache
     } else {
       init_bluestein();
+      apply_bluestein_options();
     }
     refresh_desc();
   }
@@ -197,7 +198,13 @@ template <typename T> class Plan : public HandleBase {
     else if (gen_) desc_ = "stockham global-pass " + gen_->describe();
     else if (blur_) desc_ = "bluestein M=" + std::to_string(m_) + " " + blur_->describe();
     else if (blut_) desc_ = "bluestein M=" + std::to_string(m_) + " inner " + blut_->describe();
-    else if (blu_) desc_ = "bluestein M=" + std::to_string(m_) + " inner " + eng_->describe() + (small_fused_ ? " fused" : "");
+    else if (blu_) {
+      // "fused": the whole chirp-z in one launch; "separate" (chirp sweeps: blu_pre, blu_post) / "no-conv": a plan that has the fused form /
+      // the conv kernel with it switched off
+      const bool off = (small_ok_ && !small_fused_) || (fuse_ok_ && !fused_);
+      desc_ = "bluestein M=" + std::to_string(m_) + " inner " + eng_->describe() +
+              (small_fused_ ? " fused" : off ? " separate" : (conv_ok_ && !conv_) ? " no-conv" : "");
+    }
     else desc_ = "stockham " + eng_->describe();
     desc_ += sizeof(T) == 4 ? " f32" : " f64";
   }
@@ -271,34 +278,18 @@ template <typename T> class Plan : public HandleBase {
     // 0 = always the reference's next power of two (bluesteins.rs:110).  Rebuilds the plan's tables now; not while a transform is in flight.
     if (key == "bluestein_smooth_m" && v >= 0 && v <= 2) {  // (2: wherever a product of two tile lengths exists -- for measurements)
       if (!blu_) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
-      unfused_from_mode_ = -1;  // the caller's own choice of M stands
-      if ((int)v != smooth_m_mode_) rebuild_bluestein((int)v);
+      want_smooth_m_ = (int)v;
+      apply_bluestein_options();
       return 0;
     }
-    if (key == "bluestein_fusion" && (v == 0 || v == 1)) {
-      if (blut_) return 0;  // the smooth-M route has no unfused form
-      if (blur_) {          // nor has the register route: the unfused sweeps run on the reference's power-of-two M
-        if (v == 1) return 0;
-        unfused_from_mode_ = smooth_m_mode_;
-        rebuild_bluestein(0);
-      } else if (v == 1 && unfused_from_mode_ >= 0) {  // ... and 1 brings the register route back: there and back is the plan as created
-        const int mode = unfused_from_mode_;
-        unfused_from_mode_ = -1;
-        rebuild_bluestein(mode);
-        if (blur_) return 0;
-      }
-      fused_ = (v == 1) && blu_ && eng_->can_fuse_bluestein();
-      small_fused_ = (v == 1) && blu_ && eng_->enable_bluestein_small();
-      return 0;
-    }
-    if (key == "bluestein_conv" && (v == 0 || v == 1)) { conv_ = (v == 1) && conv_ok_; return 0; }
-    if (key == "bluestein_chirp_compute" && (v == 0 || v == 1)) {
-      // (the computed chirp is built on exact exponents: under "bluestein_reference_chirp" it would disagree with the chirp-out table and w by the
-      // reference's own angle error -- the request is remembered for when that option is switched off again, the pass keeps reading the table)
-      if (reference_chirp_) { chirp_compute_saved_ = (v == 1) && chirp_p_.p != nullptr; return 0; }
-      chirp_compute_ = (v == 1) && chirp_p_.p != nullptr;
-      return 0;
-    }
+    // The five Bluestein options only record the caller's request; apply_bluestein_options() derives what the plan runs from the requests
+    // last set, whatever their order (include/fourier.h states the precedence).  "bluestein_fusion" = 0: the tile route has no unfused form
+    // (ignored there), nor has the register route: the unfused sweeps run on the reference's power-of-two M, and 1 brings the route back.
+    if (key == "bluestein_fusion" && (v == 0 || v == 1)) { want_fusion_ = (v == 1); if (blu_) apply_bluestein_options(); return 0; }
+    if (key == "bluestein_conv" && (v == 0 || v == 1)) { want_conv_ = (v == 1); if (blu_) apply_bluestein_options(); return 0; }
+    // (the computed chirp is built on exact exponents: under "bluestein_reference_chirp" it would disagree with the chirp-out table and w by the
+    // reference's own angle error -- the request stands for when that option is switched off again, the pass keeps reading the table)
+    if (key == "bluestein_chirp_compute" && (v == 0 || v == 1)) { want_chirp_compute_ = (int)v; if (blu_) apply_bluestein_options(); return 0; }
     if (key == "host_chunk_bytes" && v > 0) { host_chunk_bytes_ = (size_t)v; return 0; }
     // the two passes of a two-pass power-of-two plan software-pipelined over two internal streams with the intermediate in a small
     // ring (Pow2Engine::run_pipelined): v = transforms per chunk | ring slots << 16 | one-stream control << 24; 0 = off
@@ -312,13 +303,8 @@ template <typename T> class Plan : public HandleBase {
     // table (its computed chirp is built on exact exponents).  Not while a transform is in flight on this handle.
     if (key == "bluestein_reference_chirp" && (v == 0 || v == 1)) {
       if (!blu_) return ::fourier::c::FOURIER_HIP_INVALID_ARGUMENT;
-      if ((v == 1) != reference_chirp_) {
-        HIP_CHECK(hipDeviceSynchronize());  // the tables are replaced in place
-        build_chirp_tables(v == 1);
-        reference_chirp_ = (v == 1);
-        if (reference_chirp_) { chirp_compute_saved_ = chirp_compute_; chirp_compute_ = false; }
-        else chirp_compute_ = chirp_compute_saved_;
-      }
+      want_reference_chirp_ = (v == 1);
+      apply_bluestein_options();
       return 0;
     }
     // "register_stages" = 1: a 2^a 3^b length that runs the LDS kernel on the reference's own schedule (bit-identical to the CPU restatement)
@@ -400,7 +386,8 @@ template <typename T> class Plan : public HandleBase {
   // is larger than anything seen before -- and fourier_hip_reserve_* calls it ahead of time, so that a later
   // transform_batch of at most that batch never allocates (hipMalloc / hipFree synchronise the device) and can be
   // captured into a HIP graph.  Returns the number of transforms per chunk.
-  size_t prepare(size_t batch, bool in_place) const {
+  // `profiled`: the call is a profiled one (exec()'s prof), which a pipelined plan runs on the ordinary route when it is out of place.
+  size_t prepare(size_t batch, bool in_place, bool profiled = false) const {
     if (mix_ || regf_ || batch == 0) return batch;
     if (tiled_) {  // one scratch of a chunk for in-place calls and three-pass plans
       size_t chunk = first_chunk(batch, n_, 8.0);
@@ -414,10 +401,10 @@ template <typename T> class Plan : public HandleBase {
     }
     size_t chunk = first_chunk(batch, blu_ ? m_ : n_, 16.0);
     if (!blu_) {
-      if (pipe_chunk_) { eng_->reserve_pipeline(std::min(pipe_chunk_, batch), pipe_slots_); return batch; }
+      // (only where exec() pipelines: every other call takes the ordinary route below and needs its scratch, within "chunk_bytes")
+      if (pipelines(in_place, profiled)) { eng_->reserve_pipeline(std::min(pipe_chunk_, batch), pipe_slots_); return batch; }
       if (eng_->l2fused_enabled()) { eng_->reserve_l2fused(chunk); return chunk; }
-      const bool need = eng_->needs_scratch(in_place) || (force_scratch_ && eng_->num_passes() >= 2);
-      if (need) reserve(chunk, [&](size_t c) { scratch_.ensure(c * n_ * ELEM); });
+      if (needs_plan_scratch(in_place)) reserve(chunk, [&](size_t c) { scratch_.ensure(c * n_ * ELEM); });
       return chunk;
     }
     if (small_fused_ || blur_) return batch;  // whole chirp-z in one launch: no work array
@@ -450,6 +437,14 @@ template <typename T> class Plan : public HandleBase {
   void reserve_for(size_t batch, bool in_place) const {
     DeviceGuard g(device_);
     (void)prepare(batch, in_place);
+    if (pipe_chunk_ && !in_place) (void)prepare(batch, in_place, true);  // ... and the profiled call of a pipelined plan, which does not pipeline
+  }
+  // a plan with option "stream_pipeline" pipelines every call but the profiled out-of-place one, which times the kernels one by one on
+  // the caller's stream; prepare() and exec() both decide here
+  bool pipelines(bool in_place, bool profiled) const { return pipe_chunk_ != 0 && (!profiled || in_place); }
+  // whether the ordinary route of a plain power-of-two plan sends a pass through the plan's scratch: prepare() sizes it, exec() checks it
+  bool needs_plan_scratch(bool in_place) const {
+    return !eng_->l2fused_enabled() && (eng_->needs_scratch(in_place) || (force_scratch_ && eng_->num_passes() >= 2));
   }
 
   // Batched transform on device memory (the operator behind Fft::transform / transform_in_place).
@@ -474,7 +469,7 @@ template <typename T> class Plan : public HandleBase {
                 scale, stream, prof);
       return;
     }
-    const size_t chunk = prepare(batch, in_place);
+    const size_t chunk = prepare(batch, in_place, prof != nullptr);
 
     cpx<T>* const scratch = (cpx<T>*)scratch_.p;
     if (tiled_) {
@@ -486,10 +481,12 @@ template <typename T> class Plan : public HandleBase {
       return;
     }
     if (!blu_) {
-      if (pipe_chunk_ && (!prof || in_place)) {  // (a profiled out-of-place call times the kernels one by one on the caller's stream)
+      if (pipelines(in_place, prof != nullptr)) {
         eng_->run_pipelined(in, out, batch, pipe_chunk_, pipe_slots_, inverse, scale, stream, nxcd_, nxcd_last_, pipe_one_stream_);
         return;
       }
+      if (!scratch && needs_plan_scratch(in_place))  // prepare() sized it; never a pass through a null pointer
+        throw EngineError(::fourier::c::FOURIER_HIP_RUNTIME_ERROR, "the plan's scratch buffer is missing");
       for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
         eng_->run(in + b0 * n_, out + b0 * n_, scratch, nb, inverse, scale, nullptr, force_scratch_, stream, prof, 0, nxcd_, BluIO(), nxcd_last_);
       });
@@ -801,22 +798,52 @@ template <typename T> class Plan : public HandleBase {
       src = dst; cur ^= 1;
     }
   }
-  // option "bluestein_smooth_m" (and "bluestein_fusion" = 0 on the register route): the Bluestein route chosen again under another rule
-  void rebuild_bluestein(int mode) {
-    HIP_CHECK(hipDeviceSynchronize());
-    smooth_m_mode_ = mode;
-    blur_.reset(); blut_.reset(); eng_.reset(); eng_inv_.reset();
-    init_bluestein();
-    if (reference_chirp_) { build_chirp_tables(true); chirp_compute_saved_ = chirp_compute_; chirp_compute_ = false; }
+  // What a Bluestein plan runs, derived from the caller's requests (want_*) alone -- after init_bluestein(), after every rebuild and after
+  // every Bluestein setter, so that the order of the setters and the values set before do not matter:
+  //   "bluestein_smooth_m" chooses M and the route; "bluestein_fusion" = 0 takes a register-route plan to the reference's power-of-two M
+  //   (the rule of mode 0) and a power-of-two inner plan to the separate sweeps, and is ignored on the three-sweep tile route; the conv
+  //   kernel needs the fused end passes; "bluestein_reference_chirp" = 1 overrides "bluestein_chirp_compute" while it is set.
+  // Rebuilds the route and the tables only where they change (not while a transform is in flight on this handle).
+  void apply_bluestein_options() {
+    const int mode = (!want_fusion_ && register_route_m(want_smooth_m_) != 0) ? 0 : want_smooth_m_;
+    if (mode != smooth_m_mode_) {
+      HIP_CHECK(hipDeviceSynchronize());
+      smooth_m_mode_ = mode;
+      blur_.reset(); blut_.reset(); eng_.reset(); eng_inv_.reset();
+      init_bluestein();
+    }
+    if (tables_reference_ != want_reference_chirp_) {
+      HIP_CHECK(hipDeviceSynchronize());  // the tables are replaced in place
+      build_chirp_tables(want_reference_chirp_);
+    }
+    fused_ = want_fusion_ && fuse_ok_;
+    small_fused_ = want_fusion_ && small_ok_;
+    conv_ = want_conv_ && conv_ok_;
+    chirp_compute_ = !want_reference_chirp_ && chirp_ok_ && (want_chirp_compute_ < 0 ? chirp_default_ : want_chirp_compute_ == 1);
     refresh_desc();
   }
+  // the M of the one-launch register route (kernels_chirpz.h) where rule `mode` of "bluestein_smooth_m" takes it for this length, else 0
+  uint32_t register_route_m(int mode) const {
+    if (mode == 0 || dev_env("FOURIER_NO_SMOOTH_M")) return 0;
+    size_t m2 = 1;
+    while (m2 < 2 * n_ - 1) m2 <<= 1;
+    const uint32_t mr = BluRegEngine<T>::choose_m(n_);
+    // Three stages (M = R1 x R2 x R3, 1296 ... 3072 and 8820 / 9261): where M is at least 1.25 x shorter -- f32 1.13 ... 1.6 x, f64 1.05 ... 1.55 x
+    // the power-of-two one-launch kernels of M = 2048, 4096, 16384 (profiles/r06_s46_chirpz_reg3_ab.jsonl)
+    const bool pays = mr > 1152 ? 5 * (uint64_t)mr <= 4 * (uint64_t)m2
+                                : (sizeof(T) == 8 || mr <= 64 || (mr <= 800 && 11 * (uint64_t)mr <= 10 * (uint64_t)m2) || 17 * (uint64_t)mr <= 10 * (uint64_t)m2);
+    return (mr != 0 && (mode == 2 || pays)) ? mr : 0;
+  }
+  // builds the route of rule smooth_m_mode_ in its fused form, with the chirp tables of the angle the caller wants (once: a rebuild under
+  // "bluestein_reference_chirp" does not build the exact tables first); what the route CAN do goes to
+  // fuse_ok_, small_ok_, conv_ok_, chirp_ok_ and chirp_default_, and apply_bluestein_options() decides what it does
   void init_bluestein() {
     blu_ = true;
     if (n_ > ((size_t)1 << 26)) throw EngineError(::fourier::c::FOURIER_HIP_UNSUPPORTED, "Bluestein sizes above 2^26 are not supported");
     m_ = 1;
     while (m_ < 2 * n_ - 1) m_ <<= 1;  // bluesteins.rs:110
     if (2 * n_ > m_) throw EngineError(::fourier::c::FOURIER_HIP_RUNTIME_ERROR, "Bluestein: M < 2N");  // the fused end passes rely on it
-    fused_ = small_fused_ = conv_ = conv_ok_ = chirp_compute_ = false;
+    fuse_ok_ = small_ok_ = conv_ok_ = chirp_ok_ = chirp_default_ = false;
     // M need only reach 2N - 1 (bluesteins.rs:110 rounds up to a power of two: up to 4N).  Beyond the one-launch kernels (M <= 2^15, f64 2^14)
     // the work array is swept three times: a product of two register-tile lengths instead, where the power-of-two array is at least 1.6 x
     // longer -- f32 +3 ... 43 %, f64 +20 ... 51 % there -- and in f64 from 1.44 x on while the conv kernel stays within 336 points (+5 ... 11 %;
@@ -827,18 +854,11 @@ template <typename T> class Plan : public HandleBase {
     // 1024).  f32 (two transforms per lane, packed arithmetic): where M is at least 1.1 x shorter (1.1 ... 1.55 x up to M = 784; 480 against 512
     // and the stages of 30 and 32 points against 1024: 0.88 ... 0.99), up to M = 64 regardless (1.2 x at 64 against 64), 1152 against 2048
     // (1.37 x) -- profiles/r06_s45_chirpz_reg_ab.jsonl
-    if (smooth_m_mode_ != 0 && !dev_env("FOURIER_NO_SMOOTH_M")) {
-      const uint32_t mr = BluRegEngine<T>::choose_m(n_);
-      // Three stages (M = R1 x R2 x R3, 1296 ... 3072 and 8820 / 9261): where M is at least 1.25 x shorter -- f32 1.13 ... 1.6 x, f64 1.05 ... 1.55 x
-      // the power-of-two one-launch kernels of M = 2048, 4096, 16384 (profiles/r06_s46_chirpz_reg3_ab.jsonl)
-      const bool pays = mr > 1152 ? 5 * (uint64_t)mr <= 4 * (uint64_t)m_
-                                  : (sizeof(T) == 8 || mr <= 64 || (mr <= 800 && 11 * (uint64_t)mr <= 10 * (uint64_t)m_) || 17 * (uint64_t)mr <= 10 * (uint64_t)m_);
-      if (mr != 0 && (smooth_m_mode_ == 2 || pays)) {
-        m_ = mr;
-        blur_.reset(new BluRegEngine<T>(n_, mr));
-        build_chirp_tables(false);
-        return;
-      }
+    if (const uint32_t mr = register_route_m(smooth_m_mode_)) {
+      m_ = mr;
+      blur_.reset(new BluRegEngine<T>(n_, mr));
+      build_chirp_tables(want_reference_chirp_);
+      return;
     }
     if (smooth_m_mode_ != 0 && !dev_env("FOURIER_NO_SMOOTH_M") && m_ > ((size_t)1 << (sizeof(T) == 4 ? 15 : 14))) {
       uint32_t l1 = 0, l2 = 0;
@@ -847,7 +867,7 @@ template <typename T> class Plan : public HandleBase {
       if (ms != 0 && pays) {
         m_ = ms;
         blut_.reset(new BluTiledEngine<T>(n_, l1, l2));
-        build_chirp_tables(false);
+        build_chirp_tables(want_reference_chirp_);
         return;
       }
     }
@@ -857,9 +877,9 @@ template <typename T> class Plan : public HandleBase {
     const bool short_first = dev_env("FOURIER_BLU_SHORT_FIRST") != nullptr;
     eng_.reset(new Pow2Engine<T>(m_, short_first));
     eng_->enable_bluestein_fusion();
-    fused_ = eng_->can_fuse_bluestein();
-    small_fused_ = eng_->enable_bluestein_small();
-    if (fused_ && eng_->can_conv()) {
+    fuse_ok_ = eng_->can_fuse_bluestein();
+    small_ok_ = eng_->enable_bluestein_small();
+    if (fuse_ok_ && eng_->can_conv()) {
       // the inverse inner FFT must begin with the pass length the forward one ends with: the same plan when the
       // lengths read the same in both directions, otherwise its mirror image
       eng_->enable_conv();
@@ -867,11 +887,11 @@ template <typename T> class Plan : public HandleBase {
         eng_inv_.reset(new Pow2Engine<T>(m_, !short_first));
         eng_inv_->enable_bluestein_fusion();
       }
-      conv_ = conv_ok_ = true;
+      conv_ok_ = true;
     }
-    build_chirp_tables(false);
+    build_chirp_tables(want_reference_chirp_);
     const uint64_t two_n = 2 * (uint64_t)n_;
-    if (fused_ && !small_fused_) {
+    if (fuse_ok_ && !small_ok_) {
       // Tables for the chirp-in pass that computes the chirp instead of reading x (a quarter of that pass's traffic):
       // index k = row*cn + b  =>  x[k] = W_2n^{(row*cn)^2} * W_2n^{b^2} * W_n^{cn*row*b}; exact exponents, f64 trig, cast.
       const uint64_t cn = eng_->first_cn(), rows = (uint64_t)eng_->first_len() / 2;
@@ -888,7 +908,8 @@ template <typename T> class Plan : public HandleBase {
       // 2048 on 8-column tiles) 2.76-2.85 vs 2.92-3.08 ms per 512, f64 2.61 vs 2.88; N = 40000 / 65537 (the 0.3-0.5 MB table
       // is L2-resident anyway) and N = 2200000 (first pass of length 256: 32-column tiles, eight times the per-tile table
       // work) are 5-17 % SLOWER.  So: a long first pass and a table beyond an XCD's L2.
-      chirp_compute_ = eng_->first_len() >= 1024 && n_ * ELEM >= ((size_t)4 << 20);
+      chirp_ok_ = true;
+      chirp_default_ = eng_->first_len() >= 1024 && n_ * ELEM >= ((size_t)4 << 20);
     }
   }
   // The chirp x[k] = exp(-i*pi*k^2/n) (bluesteins.rs:51-61) and w = FFT_M(conj chirp, mirrored) (bluesteins.rs:18-48), evaluated in f64 on
@@ -925,6 +946,7 @@ template <typename T> class Plan : public HandleBase {
     const double inv_m = 1.0 / (double)m_;
     for (size_t k = 0; k < m_; ++k) w[k] = {(T)(wr[k] * inv_m), (T)(wi[k] * inv_m)};
     wtab_.upload(w);
+    tables_reference_ = reference_angle;
   }
 
   // pageable <-> pinned copies of a chunk, split over a few threads (one core moves ~10 GB/s, PCIe wants 50+ each way)
@@ -986,16 +1008,21 @@ template <typename T> class Plan : public HandleBase {
   std::unique_ptr<BluRegEngine<T>> blur_;         // ... of a short transform: one launch, transforms in registers (then eng_ is empty)
   std::unique_ptr<BluRegEngine<T>> regf_;         // a length with factors 5 ... 13 as a direct transform on the same register stages
   bool regf_on_request_ = false;                  // ... of a 2^a 3^b length, by plan option "register_stages" (mix_ stays allocated)
-  int smooth_m_mode_ = 1;                         // option "bluestein_smooth_m"
-  int unfused_from_mode_ = -1;                    // >= 0: "bluestein_fusion" = 0 took the plan off the register route, from this mode
+  // the caller's requests, as the Bluestein options were last set (apply_bluestein_options derives everything else from them)
+  int want_smooth_m_ = 1;                         // option "bluestein_smooth_m"
+  bool want_fusion_ = true, want_conv_ = true;    // options "bluestein_fusion", "bluestein_conv"
+  int want_chirp_compute_ = -1;                   // option "bluestein_chirp_compute"; -1: never set, the plan's own default (chirp_default_)
+  bool want_reference_chirp_ = false;             // option "bluestein_reference_chirp"
+  int smooth_m_mode_ = 1;                         // the rule the route was built under (init_bluestein): the request, or 0 for an unfused register-route plan
   std::unique_ptr<MixedEngine<T>> mix_;
   std::unique_ptr<TiledMixedEngine<T>> tiled_;  // 2^a*3^b, a < 12, beyond the LDS kernels: column tiles of mixed length
   std::unique_ptr<GenericEngine<T>> gen_;  // ... and what has no tile factorisation: one global pass per radix
   DevBuf xtab_, wtab_;
   DevBuf chirp_p_, chirp_u_, tn_lo_, tn_hi_;  // chirp-in pass computing the chirp (init_bluestein)
   uint32_t tn_bits_ = 0;
-  bool reference_chirp_ = false, chirp_compute_saved_ = false;  // option "bluestein_reference_chirp"
-  bool chirp_compute_ = false;  // option "bluestein_chirp_compute"
+  bool tables_reference_ = false;  // the x and w tables hold the reference's unreduced chirp angle (build_chirp_tables)
+  bool chirp_ok_ = false, chirp_default_ = false;  // the route has the chirp-in pass that computes the chirp; ... and runs it by default
+  bool chirp_compute_ = false;  // effective: the chirp-in pass computes the chirp
   mutable DevBuf scratch_, work_, hostio_;
   mutable PinnedBuf pinned_;
   mutable hipStream_t legacy_stream_ = nullptr;  // legacy host-buffer calls (exec_host)
@@ -1004,9 +1031,10 @@ template <typename T> class Plan : public HandleBase {
   bool force_scratch_ = false;
   size_t pipe_chunk_ = 0, pipe_slots_ = 0;  // option "stream_pipeline"
   bool pipe_one_stream_ = false;
-  bool fused_ = false;  // Bluestein: chirp steps fused into the inner passes
-  bool small_fused_ = false;  // Bluestein with M <= 2^15: everything in one launch
-  bool conv_ = false, conv_ok_ = false;  // Bluestein: forward LAST + (.)w + inverse FIRST in one launch
+  // effective flags (apply_bluestein_options) and what the route can do (init_bluestein: *_ok_)
+  bool fused_ = false, fuse_ok_ = false;  // Bluestein: chirp steps fused into the inner passes
+  bool small_fused_ = false, small_ok_ = false;  // Bluestein with M <= 2^15: everything in one launch
+  bool conv_ = false, conv_ok_ = false;  // Bluestein: forward LAST + (.)w + inverse FIRST in one launch (runs where fused_ too)
   int conv_route_ = 0;  // enable_conv_bank: the convolution handle's route on this plan (CONV_NONE ...)
   unsigned nxcd_ = 8, nxcd_last_ = 0;
   mutable std::shared_ptr<AxisRoute<T>> axis_;  // (shared_ptr: AxisRoute<T> is incomplete here)

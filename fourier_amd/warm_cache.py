@@ -10,6 +10,8 @@ import sys
 
 
 def smooth13(n):
+    if n < 2:  # (0 is divisible by everything: the loop below would never end)
+        return False
     for p in (2, 3, 5, 7, 11, 13):
         while n % p == 0:
             n //= p

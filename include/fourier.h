@@ -223,6 +223,22 @@ const char *fourier_hip_status_string(int status);
 /* Tunables (return FOURIER_HIP_OK or FOURIER_HIP_INVALID_ARGUMENT; "specialise" and "register_stages" also FOURIER_HIP_UNSUPPORTED).  A handle is Send, not
  * Sync, as in the reference (RefCell scratch, autosort/mod.rs:54): fourier_hip_set_option_* must not run concurrently with a
  * transform or another call on the SAME handle ("specialise" swaps the engine the plan executes with).
+ *
+ * THE RULE: what a plan runs is a function of the option values LAST SET on it, not of the order in which they were set or of values
+ * set before them.  A plan on which every option was set to some value runs the same kernels on the same tables, describes itself
+ * the same way and gives the same bits as a fresh plan on which those values were set once, in any order (tests/option_cases.py).
+ * Where options meet, the precedence among the five "bluestein_*" options is:
+ *   1. "bluestein_smooth_m" chooses M and with it the route (register stages in one launch, three sweeps on tiles, a power-of-two inner plan).
+ *   2. "bluestein_fusion" = 0 takes a plan on a power-of-two inner plan, and a plan on the register route, to the separate sweeps
+ *      (blu_pre, the inner passes, blu_post) on the reference's power-of-two M; describe() then says "separate", never "fused".  It is accepted and
+ *      ignored on the three-sweep tile route, which has no unfused form.  1 brings back what "bluestein_smooth_m" chooses.
+ *   3. "bluestein_conv" needs "bluestein_fusion": it is ignored on an unfused plan, on the one-launch routes and on the tile route.
+ *      describe() ends in "no-conv" for a fused plan that has the conv kernel switched off.
+ *   4. "bluestein_reference_chirp" = 1 overrides "bluestein_chirp_compute" while it is set; set back to 0, the value last set for
+ *      "bluestein_chirp_compute" (or, never set, the plan's default) holds again.  "bluestein_chirp_compute" acts on a fused power-of-two
+ *      inner plan of two or more passes only and is ignored elsewhere.
+ * "scratch", "chunk_bytes", "stream_pipeline", "tile_walk" and "tile_walk_last" never change a bit of the result, in any combination;
+ * after fourier_hip_reserve_* no call of at most that batch allocates under any of them, profiled calls included.
  *   "chunk_bytes"  bytes of one batch chunk pushed through all passes before the next chunk starts
  *                  (keeps the inter-pass intermediate inside the 256 MiB Infinity Cache); 0 = whole batch
  *   "scratch"      1 = always route the intermediate through the plan's reused scratch buffer,

@@ -14,6 +14,7 @@
 
 static int smooth13(size_t n) {
   static const size_t p[] = {2, 3, 5, 7, 11, 13};
+  if (n < 2) return 0; /* (0 is divisible by everything: the loop below would never end) */
   for (size_t i = 0; i < sizeof p / sizeof p[0]; ++i)
     while (n % p[i] == 0) n /= p[i];
   return n == 1;
@@ -38,17 +39,31 @@ static int warm(size_t n, int verbose) {
   return compiled;
 }
 
+/* a length: decimal digits only, all of the argument; 0 where it is anything else (strtoull alone gives 0 for "abc", 12 for "12x") */
+static int parse_length(const char* s, size_t* out) {
+  char* end = NULL;
+  if (*s < '0' || *s > '9') return 0;
+  *out = (size_t)strtoull(s, &end, 10);
+  return end != s && *end == '\0';
+}
+
 int main(int argc, char** argv) {
+  size_t first = 0, v = 0;
+  for (int i = 1; i < argc; ++i)
+    if (!parse_length(argv[i], i == 1 ? &first : &v)) {
+      fprintf(stderr, "fourier_warm_cache: '%s' is not a length\nusage: fourier_warm_cache [max_length | length ...]\n", argv[i]);
+      return 2;
+    }
   if (fourier_hip_set_default_option("specialise_at_create", 2) != 0) {
     fprintf(stderr, "fourier_warm_cache: this libfourier has no run-time specialisation\n");
     return 2;
   }
   size_t plans = 0, lengths = 0;
-  if (argc > 2 || (argc == 2 && !smooth13(0 + strtoull(argv[1], NULL, 10)))) {
+  if (argc > 2 || (argc == 2 && !smooth13(first))) {
     /* an explicit list of lengths (a single argument that is not 13-smooth is taken as a list of one) */
     for (int i = 1; i < argc; ++i) { plans += (size_t)warm(strtoull(argv[i], NULL, 10), 1); ++lengths; }
   } else {
-    const size_t max_n = argc == 2 ? strtoull(argv[1], NULL, 10) : 4096;
+    const size_t max_n = argc == 2 ? first : 4096;
     for (size_t n = 2; n <= max_n; ++n)
       if (smooth13(n)) { plans += (size_t)warm(n, 0); ++lengths; }
   }

@@ -1050,6 +1050,13 @@ def test_cmake_package_builds_and_its_ctest_programs_pass(torch, tmp_path):
     assert "libfourier.so.0" in soname
     r = subprocess.run(["ctest", "--test-dir", b, "--output-on-failure"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "100% tests passed" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
+    # the install tool refuses an argument that is not wholly a length before it touches the library (strtoull alone reads "abc" as 0
+    # and "12x" as 12); 0 is a list of one length that no plan takes, not an endless loop
+    for bad in ("abc", "12x", "-3", ""):
+        r = subprocess.run([os.path.join(b, "fourier_warm_cache"), "1001", bad], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and "is not a length" in r.stderr and not r.stdout, (bad, r.returncode, r.stdout, r.stderr)
+    r = subprocess.run([os.path.join(b, "fourier_warm_cache"), "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "1 lengths, 0 plans" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
 @pytest.mark.parametrize("n,family,per_block", [(8, "tiny_shfl", 256), (16, "tiny_shfl", 256), (32, "tiny_shfl", 256),
