@@ -137,6 +137,13 @@ _NUFFT2D = ("fourier_hip_nufft2d_", {  # non-uniform FFT, 2-D types 1 and 2, poi
     "to_modes_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),  # handle, d_in, d_out, batch, sign, order, stream
     "to_points_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),
     "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
+_NUFFT3D = ("fourier_hip_nufft3d_", {  # non-uniform FFT, 3-D types 1 and 2, points shared by the items of a batch
+    "create": (vp, [sz, sz, sz, ctypes.c_double, ci]),  # n1, n2, n3, eps, device
+    "destroy": (None, [vp]), "modes1": (sz, [vp]), "modes2": (sz, [vp]), "modes3": (sz, [vp]), "points": (sz, [vp]),
+    "set_points": (ci, [vp, vp, vp, vp, sz, vp]),  # handle, h_x1, h_x2, h_x3 (f64 on the host), m, stream
+    "to_modes_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),  # handle, d_in, d_out, batch, sign, order, stream
+    "to_points_batch": (ci, [vp, vp, vp, sz, ci, ci, vp]),
+    "reserve": (ci, [vp, sz]), "set_option": (ci, [vp, cp, ll]), "describe": (cp, [vp]), "last_status": (ci, [vp])})
 _GLOBAL = {  # no handle, no precision suffix
     "fourier_hip_status_string": (cp, [ci]), "fourier_hip_set_default_option": (ci, [cp, ll]),
     "fourier_hip_get_default_option": (ll, [cp])}
@@ -176,13 +183,15 @@ ALL_SYMBOLS = (LEGACY_SYMBOLS + EXT_SYMBOLS + REAL_SYMBOLS + AXIS_SYMBOLS + REAL
 R2R_SYMBOLS = list(_signatures(_R2R))
 # ... and so is the 2-D non-uniform FFT family, for the digit in "nufft2d": tests/test_nufft2d_abi.py holds its three-way check.
 NUFFT2D_SYMBOLS = list(_signatures(_NUFFT2D))
+# ... and the 3-D one, for the same reason: tests/test_nufft3d_abi.py.
+NUFFT3D_SYMBOLS = list(_signatures(_NUFFT3D))
 
 
 def bind(cdll, strict=True):
     """Attach argtypes/restypes for every entry point of include/fourier.h to a loaded CDLL.  strict=False (A/B tools that
     load libraries built from older sources) tolerates entry points added since."""
     signatures = dict(_GLOBAL)
-    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM, _CONVND, _NUFFT, _NUFFT2D):
+    for family in (_LEGACY, _EXT, _REAL, _AXIS, _REALND, _CONV, _LCONV, _R2R, _STFT, _MDCT, _SPECTROGRAM, _CSD, _BANDSPEC, _HILBERT, _CZT, _PFB, _IPFB, _RESAMPLE, _XCORR, _DELAY, _CEPSTRUM, _CONVND, _NUFFT, _NUFFT2D, _NUFFT3D):
         signatures.update(_signatures(family))
     for name, (restype, argtypes) in signatures.items():
         if strict or hasattr(cdll, name):

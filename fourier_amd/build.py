@@ -56,7 +56,7 @@ def mix_shards(name="MIX"):
 
 def translation_units():
     """(object name, source file, extra -D flags, group) for every object of the two libraries.  Groups: 'host', 'env_product',
-    'env_experiments', 'pass', 'onelaunch', 'misc', 'real', 'r2r', 'stft', 'mdct', 'spectrogram', 'csd', 'bandspec', 'conv', 'convnd', 'hilbert', 'czt', 'pfb', 'resample', 'xcorr', 'delay', 'cepstrum', 'nufft', 'nufft2d', 'axis', 'mixed', 'chirpz', 'experiments' (tools/build_variants.py rebuilds by group)."""
+    'env_experiments', 'pass', 'onelaunch', 'misc', 'real', 'r2r', 'stft', 'mdct', 'spectrogram', 'csd', 'bandspec', 'conv', 'convnd', 'hilbert', 'czt', 'pfb', 'resample', 'xcorr', 'delay', 'cepstrum', 'nufft', 'nufft2d', 'nufft3d', 'axis', 'mixed', 'chirpz', 'experiments' (tools/build_variants.py rebuilds by group)."""
     tus = [("engine", "engine.cpp", [], "host"),
            ("rtc", "rtc.cpp", [], "host"),
            ("env_product", "env_product.cpp", [], "env_product"),
@@ -92,6 +92,7 @@ def translation_units():
         tus.append((f"kernels_cepstrum_{tag}", "kernels_cepstrum.cpp", d, "cepstrum"))
         tus.append((f"kernels_nufft_{tag}", "kernels_nufft.cpp", d, "nufft"))
         tus.append((f"kernels_nufft2d_{tag}", "kernels_nufft2d.cpp", d, "nufft2d"))
+        tus.append((f"kernels_nufft3d_{tag}", "kernels_nufft3d.cpp", d, "nufft3d"))
         tus.append((f"kernels_axis_{tag}", "kernels_axis.cpp", d, "axis"))
         for i in range(4):
             tus.append((f"kernels_tiled_{tag}_{i}", "kernels_tiled.cpp", d + [f"-DFOURIER_TILED_SHARD={i}"], "mixed"))

@@ -34,6 +34,7 @@
 #include "cepstrum_plan.h"
 #include "nufft_plan.h"
 #include "nufft2d_plan.h"
+#include "nufft3d_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (declared in include/fourier.h)
@@ -860,6 +861,46 @@ FOURIER_DEFINE_NUFFT_ABI(double, double)
 
 FOURIER_DEFINE_NUFFT2D_ABI(float, float)
 FOURIER_DEFINE_NUFFT2D_ABI(double, double)
+
+// non-uniform FFT, 3-D types 1 and 2 (fourier_hip_nufft3d_*)
+#define FOURIER_DEFINE_NUFFT3D_ABI(T, SUFFIX)                                                                    \
+  FOURIER_DEFINE_HANDLE_ABI(nufft3d, fourier_nufft3d_##SUFFIX, Nufft3dPlan<T>, SUFFIX)                           \
+  extern "C" fc::fourier_nufft3d_##SUFFIX* fourier_hip_nufft3d_create_##SUFFIX(size_t n1, size_t n2, size_t n3, double eps, int device) { \
+    return (fc::fourier_nufft3d_##SUFFIX*)create_handle<Nufft3dPlan<T>>(n1, n2, n3, eps, device);                \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft3d_modes1_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h) {                 \
+    return h ? ((const Nufft3dPlan<T>*)h)->modes1() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft3d_modes2_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h) {                 \
+    return h ? ((const Nufft3dPlan<T>*)h)->modes2() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft3d_modes3_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h) {                 \
+    return h ? ((const Nufft3dPlan<T>*)h)->modes3() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" size_t fourier_hip_nufft3d_points_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h) {                 \
+    return h ? ((const Nufft3dPlan<T>*)h)->points() : 0;                                                         \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft3d_set_points_##SUFFIX(fc::fourier_nufft3d_##SUFFIX* h, const double* h_x1, const double* h_x2, \
+                                                         const double* h_x3, size_t m, void* stream) {           \
+    Nufft3dPlan<T>* p = (Nufft3dPlan<T>*)h;                                                                      \
+    return guarded_handle(p, [&] { p->set_points(h_x1, h_x2, h_x3, m, (hipStream_t)stream); });                  \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft3d_to_modes_batch_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                             size_t batch, int sign, int order, void* stream) {  \
+    const Nufft3dPlan<T>* p = (const Nufft3dPlan<T>*)h;                                                          \
+    return guarded_handle(p, [&] { p->to_modes(d_in, d_out, batch, sign, order, (hipStream_t)stream); });        \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft3d_to_points_batch_##SUFFIX(const fc::fourier_nufft3d_##SUFFIX* h, const void* d_in, void* d_out, \
+                                                              size_t batch, int sign, int order, void* stream) { \
+    const Nufft3dPlan<T>* p = (const Nufft3dPlan<T>*)h;                                                          \
+    return guarded_handle(p, [&] { p->to_points(d_in, d_out, batch, sign, order, (hipStream_t)stream); });       \
+  }                                                                                                              \
+  extern "C" int fourier_hip_nufft3d_set_option_##SUFFIX(fc::fourier_nufft3d_##SUFFIX* h, const char* key, long long v) { \
+    return set_handle_option<Nufft3dPlan<T>>(h, key, v);                                                         \
+  }
+
+FOURIER_DEFINE_NUFFT3D_ABI(float, float)
+FOURIER_DEFINE_NUFFT3D_ABI(double, double)
 
 // ---- library-wide defaults for plans created afterwards
 namespace fourier_hip {

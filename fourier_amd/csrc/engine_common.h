@@ -210,6 +210,7 @@ typedef void (*DelayKernel)(DelayArgs);
 typedef void (*CepstrumKernel)(CepstrumArgs);
 typedef void (*NufftKernel)(NufftArgs);
 typedef void (*Nufft2dKernel)(Nufft2dArgs);
+typedef void (*Nufft3dKernel)(Nufft3dArgs);
 typedef void (*MixKernelFn)(MixArgs);
 typedef void (*TiledKernelFn)(TiledArgs);
 // a tile pass of mixed length L: columns per tile, threads, LDS bytes
@@ -359,6 +360,12 @@ template <typename T> struct Real {};
   Nufft2dKernel get_nufft2d_interp_kernel(Real<T>, int w, int rb);                                                     \
   Nufft2dKernel get_nufft2d_sweep_kernel(Real<T>, int which);                                                          \
   Nufft2dKernel get_nufft2d_table_kernel(Real<T>);                                                                     \
+  /* kernels_nufft3d.cpp: the 3-D non-uniform FFT's spreading gather for a block of rb items (the width is a launch argument), */ \
+  /* its interpolation for a width w and a block of rb items (null outside the 1-D ranges), its sweeps and its set-up kernel */ \
+  Nufft3dKernel get_nufft3d_spread_kernel(Real<T>, int rb);                                                            \
+  Nufft3dKernel get_nufft3d_interp_kernel(Real<T>, int w, int rb);                                                     \
+  Nufft3dKernel get_nufft3d_sweep_kernel(Real<T>, int which);                                                          \
+  Nufft3dKernel get_nufft3d_table_kernel(Real<T>);                                                                     \
   /* kernels_axis.cpp: axis_lane_kernel<T, n> for 1 <= n <= 32 (null otherwise), axis_transpose_kernel<T> (n == 0) */   \
   AxisKernel get_axis_kernel(Real<T>, int n);                                                                          \
   /* kernels_mixed_rt.cpp: the runtime-parameterised LDS kernel (maxp in {3, 7, 13}), null where not instantiated */    \

@@ -629,6 +629,44 @@ struct Nufft2dArgs {
   double beta;                // 2.30 w
 };
 
+// ---- non-uniform FFT, 3-D, types 1 and 2 (kernels_nufft3d.h; Nufft3dPlan, nufft3d_plan.h): m points shared by the items of a batch,
+// bucketed by the pair of wrapped first cells of axes 1 and 2 and sorted by the axis-3 grid coordinate within a bucket; fine-grid items
+// of l1 x l2 x l3 cells, rows of m strengths, items of n1 x n2 x n3 modes, all complex T, the last axis contiguous.
+// nufft3d_spread_kernel / nufft3d_interp_kernel: one lane per (item block, cell) / (item block, sorted point); `blocks` item blocks of
+// RB items from the launch's first item on, `per` workgroups an item block.  Every item has a buffer descriptor of its own (item bytes
+// <= 2^31 - 1).  nufft3d_deconv_kernel / nufft3d_amplify_kernel: one lane per output value over a flat index; byte offsets are 32-bit
+// (at most REAL_LAUNCH_BYTES of either side per launch).  nufft3d_table_kernel: one lane per point, 3 w weights each.
+// The item block NUFFT_RB, the widths NUFFT_MIN_W .. NUFFT_MAX_W_* and NUFFT_DECONV / NUFFT_AMPLIFY are the 1-D handle's.
+struct Nufft3dArgs {
+  const void* in; void* out;  // spread: strengths -> grid; interp: grid -> strengths; deconv: grid -> modes; amplify: modes -> grid
+  const uint32_t* r1;         // [m] first cell of axis 1 of sorted point p, modulo l1
+  const uint32_t* r2;         // [m] first cell of axis 2, modulo l2: the point's bucket is r1 l2 + r2
+  const int32_t* i03;         // [m] first cell of axis 3 (may lie outside [0, l3): the footprint wraps)
+  const void* d1;             // [m] reals T: i0_1 - g_1, in [-w/2, -w/2 + 1)
+  const void* d2;             // [m] reals T: i0_2 - g_2
+  const void* d3;             // [m] reals T: i0_3 - g_3
+  const uint32_t* perm;       // [m] the caller's index of sorted point p
+  const uint32_t* first;      // [l1 l2][ne3]: first[b][e + w] = sorted index of the first point of bucket b with i0_3 >= e, e in [-w, l3 + w]
+  const void* wtab;           // tabulated route: [3][w][m] reals T, weight of tap t of axis d of sorted point p at (d w + t) m + p; null: evaluated
+  const void* inv1;           // [n1 / 2 + 1] reals T: 1 / phihat_1(|k1|)
+  const void* inv2;           // [n2 / 2 + 1] reals T: 1 / phihat_2(|k2|)
+  const void* inv3;           // [n3 / 2 + 1] reals T: 1 / phihat_3(|k3|)
+  uint32_t l1, l2, l3, m, n1, n2, n3, w;
+  uint32_t ne3;               // l3 + 2 w + 1: the row length of first[]
+  uint32_t cells;             // l1 l2 l3
+  uint32_t blocks, per;       // spread, interp: item blocks of this launch; workgroups an item block
+  uint32_t per_m, per_l;      // blk / per = (umulhi(blk, per_m) + blk) >> per_l
+  uint32_t l3_m, l3_l;        // spread: cell / l3
+  uint32_t l2_m, l2_l;        // spread: (cell / l3) / l2
+  uint32_t total;             // deconv, amplify: values of this launch; table: m
+  uint32_t item_m, item_l;    // deconv: idx / (n1 n2 n3); amplify: idx / (l1 l2 l3)
+  uint32_t row_m, row_l;      // deconv: rem / n3; amplify: rem / l3
+  uint32_t mid_m, mid_l;      // deconv: (rem / n3) / n2; amplify: (rem / l3) / l2
+  uint32_t in_bytes, out_bytes;  // deconv, amplify: descriptor ranges of this launch
+  uint32_t order;             // 0: all three axes ascending from -floor(n/2); 1: all in FFT order
+  double beta;                // 2.30 w
+};
+
 // ---- transforms along a strided axis (kernels_axis.h): element (o, j, c) of an [outer][N][inner] array at (o*N + j)*inner + c
 // axis_lane_kernel: one lane per column (o, c) of this launch's outer blocks and column range (`cols` columns from the launch's
 // base); flat index idx < total = blocks * cols, o = idx / cols by multiply-high.  axis_transpose_kernel: `blocks` source matrices of rows x cols

@@ -2452,6 +2452,110 @@ def nufft2d2(x1, x2, f, eps=1e-6, isign=1):
     return plan.to_points(f.contiguous(), isign)
 
 
+class Nufft3d(Nufft2d):
+    """Batched 3-D non-uniform FFT of types 1 and 2 (include/fourier.h, fourier_hip_nufft3d_*) on device memory, in C order, the points
+    shared by the items of a batch.  For n_modes = (N1, N2, N3) modes k_d = -floor(N_d/2) .. ceil(N_d/2) - 1 and M points
+    (x1_j, x2_j, x3_j) (set_points; any finite reals, taken modulo 2 pi per coordinate; coordinate d pairs with axis d):
+        to_modes  (type 1)   f[b, k1, k2, k3] = sum_j c[b, j] exp(i isign (k1 x1_j + k2 x2_j + k3 x3_j))           (..., M) -> (..., N1, N2, N3)
+        to_points (type 2)   c[b, j] = sum_{k1,k2,k3} f[b, k1, k2, k3] exp(i isign (k1 x1_j + k2 x2_j + k3 x3_j))  (..., N1, N2, N3) -> (..., M)
+    with no scale factor; to_points with isign s is the exact adjoint of to_modes with -s.  `eps` is the requested relative accuracy:
+    the kernel width is w = ceil(log10(1 / eps)) + 1 for all three axes, clamped to 2 .. 8 at f32 and 2 .. 16 at f64, and the relative
+    L2 error of a call is about 3 x 10^(1 - w) plus the rounding of the precision.  modeord 0 stores all three axes with k ascending,
+    1 all three in FFT order.  The methods are Nufft2d's with a third coordinate."""
+
+    _prefix = "fourier_hip_nufft3d_"
+    _destroy = "fourier_hip_nufft3d_destroy"
+
+    def __init__(self, n_modes, eps=1e-6, real="f32", device=-1):
+        import math
+
+        try:
+            n1, n2, n3 = (int(v) for v in n_modes)
+        except (TypeError, ValueError):
+            raise ValueError(f"need n_modes = (n1, n2, n3), got {n_modes!r}") from None
+        eps = float(eps)
+        if n1 < 1 or n2 < 1 or n3 < 1:
+            raise ValueError(f"need n1, n2, n3 >= 1, got {(n1, n2, n3)}")
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"need a finite eps > 0, got {eps}")
+        self._create(real, f"nufft3d plan of {n1} x {n2} x {n3} modes, eps {eps}", n1, n2, n3, eps, int(device))
+        self._n, self.eps = (n1, n2, n3), eps
+
+    def set_points_ptr(self, h_x1, h_x2, h_x3, m, stream=0):
+        """`m` float64 values at each of the HOST addresses h_x1, h_x2, h_x3.  Waits for `stream`."""
+        self._call("set_points", h_x1, h_x2, h_x3, int(m), stream)
+
+    def set_points(self, x1, x2, x3):
+        """Three numpy arrays or torch tensors (any device, any real dtype) of M coordinates each: copied to the host as float64.  Every
+        coordinate must be finite.  Replaces the points in use; waits for the current stream."""
+        import numpy as np
+
+        hosts = []
+        for x in (x1, x2, x3):
+            if _is_torch(x):
+                x = x.detach().cpu().numpy()
+            elif not isinstance(x, np.ndarray):
+                raise TypeError("points must be numpy arrays or torch tensors")
+            if x.dtype.kind not in "fiu":
+                raise TypeError(f"points must be real, got {x.dtype}")
+            hosts.append(np.ascontiguousarray(x, dtype=np.float64).ravel())
+        m = hosts[0].size
+        if hosts[1].size != m or hosts[2].size != m:
+            raise ValueError(f"x1, x2 and x3 must have the same number of points, got {[h.size for h in hosts]}")
+        if not all(np.isfinite(h).all() for h in hosts):
+            raise ValueError("every point must be finite")
+        stream = 0
+        try:
+            import torch
+
+            if torch.cuda.is_available():
+                stream = torch.cuda.current_stream().cuda_stream
+        except Exception:
+            pass
+        self.set_points_ptr(*(h.ctypes.data if m else None for h in hosts), m, stream)
+
+
+def create_nufft3d_f32(n_modes, eps=1e-6, device=-1):
+    return Nufft3d(n_modes, eps, "f32", device)
+
+
+def create_nufft3d_f64(n_modes, eps=1e-6, device=-1):
+    return Nufft3d(n_modes, eps, "f64", device)
+
+
+def _nufft3d_plan(x1, x2, x3, v, n_modes, eps):
+    """nufft3d1 / nufft3d2: the cached handle of (n_modes, eps, precision, device) with the points (x1, x2, x3) set"""
+    if not (_is_torch(v) and v.is_cuda and _precision(v.dtype) is not None and not _precision(v.dtype)[1]):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor")
+    plan = _cached_plan(Nufft3d, tuple(int(n) for n in n_modes), float(eps), _precision(v.dtype)[0], int(_device_index(v)))
+    plan.set_points(x1, x2, x3)
+    return plan
+
+
+def nufft3d1(x1, x2, x3, c, n_modes, eps=1e-6, isign=-1):
+    """3-D type 1 (points to modes): f[..., k1, k2, k3] = sum_j c[..., j] exp(i isign (k1 x1[j] + k2 x2[j] + k3 x3[j])),
+    k_d = -floor(N_d/2) .. ceil(N_d/2) - 1 ascending, n_modes = (N1, N2, N3), for M points (x1, x2, x3) (numpy or torch, any device,
+    copied to the host as float64) and a CUDA complex64 / complex128 tensor `c` of shape (..., M), whose leading dimensions are a
+    batch that shares the points; on the current stream.  Returns a new (..., N1, N2, N3) tensor.  One cached Nufft3d handle per
+    (n_modes, eps, dtype, device); every call sets its points, a set-up step that waits for the stream: keep a Nufft3d of your own
+    where the points stay."""
+    if not (_is_torch(c) and c.dim() >= 1):
+        raise TypeError("expected a CUDA complex64 / complex128 tensor of at least one dimension")
+    plan = _nufft3d_plan(x1, x2, x3, c, n_modes, eps)
+    return plan.to_modes(c.contiguous(), isign)
+
+
+def nufft3d2(x1, x2, x3, f, eps=1e-6, isign=1):
+    """3-D type 2 (modes to points): c[..., j] = sum_{k1,k2,k3} f[..., k1, k2, k3] exp(i isign (k1 x1[j] + k2 x2[j] + k3 x3[j])) for a
+    CUDA complex64 / complex128 tensor `f` of shape (..., N1, N2, N3) holding the modes ascending on all three axes, and M points
+    (x1, x2, x3) (as for nufft3d1); on the current stream.  Returns a new (..., M) tensor.  The cached handle and its set-up step are
+    nufft3d1's."""
+    if not (_is_torch(f) and f.dim() >= 3 and min(f.shape[-3:]) >= 1):
+        raise ValueError("expected a tensor whose three mode dimensions have length >= 1")
+    plan = _nufft3d_plan(x1, x2, x3, f, tuple(int(s) for s in f.shape[-3:]), eps)
+    return plan.to_points(f.contiguous(), isign)
+
+
 class Resample(_Handle):
     """Batched Fourier-domain resampling (include/fourier.h, fourier_hip_resample_*) on device memory: rows of n_in values -> rows of
     n_out values, the spectrum cut or zero-padded and transformed back -- scipy.signal.resample(x, n_out, axis=-1, window=W) with W an

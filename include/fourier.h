@@ -1867,6 +1867,90 @@ const char *fourier_hip_nufft2d_describe_double(const FOURIER_STRUCT fourier_nuf
 int fourier_hip_nufft2d_last_status_float(const FOURIER_STRUCT fourier_nufft2d_float *);
 int fourier_hip_nufft2d_last_status_double(const FOURIER_STRUCT fourier_nufft2d_double *);
 
+/* ---------------- non-uniform FFT, 3-D, types 1 and 2 (extension; the reference has none) ----------
+ * FINUFFT's 3-D type 1 and type 2 in C order with the points shared by the items of a batch.  A handle is created for n1 x n2 x n3
+ * modes (each >= 1) and a requested accuracy eps; fourier_hip_nufft3d_set_points_* gives it M >= 0 points (x1_j, x2_j, x3_j), any
+ * finite reals, taken modulo 2 pi per coordinate.  Coordinate d pairs with axis d of the mode array; k_d runs over
+ * -floor(n_d/2) .. ceil(n_d/2) - 1.  With s = `sign`, +1 or -1 per call:
+ *   to_modes  (type 1)   f[b][k1][k2][k3] = sum_j c[b][j] exp(i s (k1 x1_j + k2 x2_j + k3 x3_j))            rows of M in, items of n1 x n2 x n3 out
+ *   to_points (type 2)   c[b][j] = sum_{k1,k2,k3} f[b][k1][k2][k3] exp(i s (k1 x1_j + k2 x2_j + k3 x3_j))   items of n1 x n2 x n3 in, rows of M out
+ * on DEVICE memory, interleaved complex T, the last mode axis contiguous, item b at element offset b*M or b*n1*n2*n3.  `order` 0
+ * stores all three axes with k ascending, 1 all three in FFT order (numpy's ifftshift over the three axes of order 0).  There is no
+ * scale factor; to_points with sign s is the exact adjoint of to_modes with sign -s.
+ * The algorithm is fourier_hip_nufft2d_*'s with one more axis: the same kernel phi with beta = 2.30 w, the same
+ * w = ceil(log10(1 / eps)) + 1 clamped to 2 .. 8 (float) or 2 .. 16 (double), one w for all three axes; L_d is the smallest
+ * 2^a 3^b 5^c >= max(2 n_d, 2 w); a point's weight on cell (i1, i2, i3) is the product of its three 1-D weights, and the
+ * deconvolution factor is the product of three 1-D tables from the same quadrature.  to_modes spreads onto grid items of
+ * L1 x L2 x L3 (a gather over the points, bucketed by their first cells of axes 1 and 2 and sorted by their axis-3 coordinate: no
+ * atomics), transforms the rows of L3, then axis 2, then axis 1 in place (FFT for s = -1, UNSCALED_IFFT for s = +1), picks the
+ * n1 x n2 x n3 modes and multiplies by 1 / phihat; to_points writes f / phihat into a zeroed grid, transforms and interpolates at
+ * the points.  The relative L2 error of a call against the direct sum is about 3 x 10^(1 - w), plus the rounding of T.
+ * fourier_hip_nufft3d_set_points_*: h_x1, h_x2 and h_x3 each point to m doubles on the HOST, for both precisions.  A set-up call like
+ * fourier_hip_nufft2d_set_points_*: it waits for `stream`, sorts (stable: equal points keep the caller's order), uploads the tables
+ * and waits again.  Besides seven arrays of m values the tables hold L1 L2 (L3 + 2w + 1) 32-bit indices, about half of one float grid
+ * item and a quarter of a double one.  Calling it again replaces the points; m == 0 is valid (to_modes then writes zeros, to_points
+ * writes nothing).  A NaN or infinite coordinate in any array, m > 2^31 - 1, m * 2 * sizeof(T) > 2^30, a NULL pointer with m > 0 or
+ * one not aligned to 8 bytes give FOURIER_HIP_INVALID_ARGUMENT and leave the points as they were; so does an allocation or copy that
+ * fails (the new tables replace the old ones only when all of them are complete).
+ * A transform call before any set_points, sign other than +1 / -1, order other than 0 / 1, a NULL or misaligned (2*sizeof(T)) buffer
+ * and ANY overlap of input and output give FOURIER_HIP_INVALID_ARGUMENT and write nothing.  batch == 0 is a successful no-op.
+ * An n_d of 0, eps <= 0 or not finite, items of n1 * n2 * n3 modes above 2^30 bytes or a grid item above 2^31 bytes: create fails.
+ * Stream-ordered on `stream` like fourier_hip_transform_batch_*.
+ * Option "table" (fourier_hip_nufft3d_set_option_*): 0 = "nufft3d evaluated", the weights are evaluated in the two hot kernels with
+ * the accurate exp and sqrt; 1 = "nufft3d tabulated", a set-up kernel writes the 3 x w x M weights once (at set_points, or at set_option
+ * on the null stream when points are set) and the hot kernels read them.  The two routes agree to rounding.  The default is 0
+ * ("Non-uniform FFT, 3-D").  fourier_hip_nufft3d_describe_* begins "nufft3d evaluated: " or "nufft3d
+ * tabulated: ", then "w <w>, L <L1> x <L2> x <L3>, " and the descriptions of the row plan and of the axis-2 and axis-1 routes.
+ * The plan owns a scratch of fine-grid items of at most 1 GiB (never less than one item) and walks larger batches in chunks; the first
+ * call with a batch larger than any before allocates it unless fourier_hip_nufft3d_reserve_* was called for at least that batch.  No
+ * atomics and a summation order fixed by the points: the result is the same on repetition.  A NULL handle gives
+ * FOURIER_HIP_INVALID_ARGUMENT, 0 from fourier_hip_nufft3d_modes1_* / _modes2_* / _modes3_* / _points_* and "" from
+ * fourier_hip_nufft3d_describe_*.  Handles are Send, not Sync, like the complex ones; status of the last call:
+ * fourier_hip_nufft3d_last_status_*. */
+struct fourier_nufft3d_float;
+struct fourier_nufft3d_double;
+
+/* NULL on failure (a parameter outside the ranges above included). */
+struct fourier_nufft3d_float *fourier_hip_nufft3d_create_float(FOURIER_SIZE_TYPE n1, FOURIER_SIZE_TYPE n2, FOURIER_SIZE_TYPE n3,
+                                                               double eps, int device);
+struct fourier_nufft3d_double *fourier_hip_nufft3d_create_double(FOURIER_SIZE_TYPE n1, FOURIER_SIZE_TYPE n2, FOURIER_SIZE_TYPE n3,
+                                                                 double eps, int device);
+/* NULL is a no-op. */
+void fourier_hip_nufft3d_destroy_float(FOURIER_STRUCT fourier_nufft3d_float *);
+void fourier_hip_nufft3d_destroy_double(FOURIER_STRUCT fourier_nufft3d_double *);
+/* n1, n2, n3, and the M of the last set_points (0 before any); 0 for a NULL handle. */
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes1_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes1_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes2_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes2_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes3_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_modes3_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_points_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+FOURIER_SIZE_TYPE fourier_hip_nufft3d_points_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+/* three arrays of m doubles on the host, for both precisions. */
+int fourier_hip_nufft3d_set_points_float(FOURIER_STRUCT fourier_nufft3d_float *, const double *h_x1, const double *h_x2,
+                                         const double *h_x3, FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft3d_set_points_double(FOURIER_STRUCT fourier_nufft3d_double *, const double *h_x1, const double *h_x2,
+                                          const double *h_x3, FOURIER_SIZE_TYPE m, void *stream);
+int fourier_hip_nufft3d_to_modes_batch_float(const FOURIER_STRUCT fourier_nufft3d_float *, const void *d_in, void *d_out,
+                                             FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft3d_to_modes_batch_double(const FOURIER_STRUCT fourier_nufft3d_double *, const void *d_in, void *d_out,
+                                              FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft3d_to_points_batch_float(const FOURIER_STRUCT fourier_nufft3d_float *, const void *d_in, void *d_out,
+                                              FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft3d_to_points_batch_double(const FOURIER_STRUCT fourier_nufft3d_double *, const void *d_in, void *d_out,
+                                               FOURIER_SIZE_TYPE batch, int sign, int order, void *stream);
+int fourier_hip_nufft3d_reserve_float(const FOURIER_STRUCT fourier_nufft3d_float *, FOURIER_SIZE_TYPE batch);
+int fourier_hip_nufft3d_reserve_double(const FOURIER_STRUCT fourier_nufft3d_double *, FOURIER_SIZE_TYPE batch);
+/* "table": 0 / 1.  Anything else: FOURIER_HIP_INVALID_ARGUMENT. */
+int fourier_hip_nufft3d_set_option_float(FOURIER_STRUCT fourier_nufft3d_float *, const char *key, long long value);
+int fourier_hip_nufft3d_set_option_double(FOURIER_STRUCT fourier_nufft3d_double *, const char *key, long long value);
+/* "" for a NULL handle. */
+const char *fourier_hip_nufft3d_describe_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+const char *fourier_hip_nufft3d_describe_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+int fourier_hip_nufft3d_last_status_float(const FOURIER_STRUCT fourier_nufft3d_float *);
+int fourier_hip_nufft3d_last_status_double(const FOURIER_STRUCT fourier_nufft3d_double *);
+
 #ifdef __cplusplus
 } /* extern "C" */
 } /* namespace c */
@@ -2555,6 +2639,57 @@ template <typename T> struct nufft2d;
 FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER(float, float)
 FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER(double, double)
 #undef FOURIER_DEFINE_CXX_NUFFT2D_WRAPPER
+
+/* non-uniform FFT, 3-D types 1 and 2, on device memory (extension): fourier::nufft3d<float> / <double> */
+template <typename T> struct nufft3d;
+
+#define FOURIER_DEFINE_CXX_NUFFT3D_WRAPPER(T, SUFFIX)                                              \
+  template <> struct nufft3d<T> {                                                                  \
+    nufft3d(std::size_t n1, std::size_t n2, std::size_t n3, double eps = 1e-6, int device = -1)    \
+        : impl(::fourier::c::fourier_hip_nufft3d_create_##SUFFIX(n1, n2, n3, eps, device),         \
+               ::fourier::c::fourier_hip_nufft3d_destroy_##SUFFIX) {}                              \
+    nufft3d() = delete;                                                                            \
+    nufft3d(const nufft3d &) = delete;                                                             \
+    nufft3d(nufft3d &&) = default;                                                                 \
+    nufft3d &operator=(const nufft3d &) = delete;                                                  \
+    nufft3d &operator=(nufft3d &&) = default;                                                      \
+    ~nufft3d() = default;                                                                          \
+    std::size_t modes1() const { return ::fourier::c::fourier_hip_nufft3d_modes1_##SUFFIX(impl.get()); }\
+    std::size_t modes2() const { return ::fourier::c::fourier_hip_nufft3d_modes2_##SUFFIX(impl.get()); }\
+    std::size_t modes3() const { return ::fourier::c::fourier_hip_nufft3d_modes3_##SUFFIX(impl.get()); }\
+    std::size_t points() const { return ::fourier::c::fourier_hip_nufft3d_points_##SUFFIX(impl.get()); }\
+    /* three arrays of m doubles on the HOST; a set-up call that waits for `stream` */             \
+    int set_points(const double *h_x1, const double *h_x2, const double *h_x3, std::size_t m,      \
+                   void *stream = nullptr) {                                                       \
+      return ::fourier::c::fourier_hip_nufft3d_set_points_##SUFFIX(impl.get(), h_x1, h_x2, h_x3, m, stream);\
+    }                                                                                              \
+    /* type 1: `batch` rows of points() strengths -> `batch` items of modes1() x modes2() x modes3() */\
+    int to_modes_device(const void *d_in, void *d_out, std::size_t batch, int sign = -1,           \
+                        int order = 0, void *stream = nullptr) const {                             \
+      return ::fourier::c::fourier_hip_nufft3d_to_modes_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    /* type 2: `batch` items of modes1() x modes2() x modes3() -> `batch` rows of points() values */\
+    int to_points_device(const void *d_in, void *d_out, std::size_t batch, int sign = 1,           \
+                         int order = 0, void *stream = nullptr) const {                            \
+      return ::fourier::c::fourier_hip_nufft3d_to_points_batch_##SUFFIX(impl.get(), d_in, d_out, batch, sign, order, stream);\
+    }                                                                                              \
+    int reserve(std::size_t batch) const {                                                         \
+      return ::fourier::c::fourier_hip_nufft3d_reserve_##SUFFIX(impl.get(), batch);                \
+    }                                                                                              \
+    int set_option(const char *key, long long value) {                                             \
+      return ::fourier::c::fourier_hip_nufft3d_set_option_##SUFFIX(impl.get(), key, value);        \
+    }                                                                                              \
+    const char *describe() const { return ::fourier::c::fourier_hip_nufft3d_describe_##SUFFIX(impl.get()); }\
+    int last_status() const { return ::fourier::c::fourier_hip_nufft3d_last_status_##SUFFIX(impl.get()); }\
+    explicit operator bool() const { return static_cast<bool>(impl); }                             \
+                                                                                                   \
+  private:                                                                                         \
+    ::std::unique_ptr<::fourier::c::fourier_nufft3d_##SUFFIX,                                      \
+                      void (*)(::fourier::c::fourier_nufft3d_##SUFFIX *)> impl;                    \
+  };
+FOURIER_DEFINE_CXX_NUFFT3D_WRAPPER(float, float)
+FOURIER_DEFINE_CXX_NUFFT3D_WRAPPER(double, double)
+#undef FOURIER_DEFINE_CXX_NUFFT3D_WRAPPER
 
 /* chirp-z transform on device memory (extension): fourier::czt<float> / <double> */
 template <typename T> struct czt;
